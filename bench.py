@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- translator training throughput on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1: either form works -- plain `python bench.py --gpus N` starts its N ranks itself by re-executing under
      torch.distributed.run on 127.0.0.1 and relays rank 0's JSON line as the LAST line of stdout;
      `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...` is used as launched.)
@@ -11,6 +11,12 @@ synthetic (src, ctx, tgt) frame triples that are already resident in HBM (BASELI
 configs[1]; weak scaling: every rank has its own 256).  With N > 1 the gradient arena is
 sum-all-reduced over RCCL between backward and Adam (the path has one exchange step).
 Prints ONE JSON line on rank 0.  PyTorch is plumbing only: device buffers, the stream, RCCL.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the step's rates from the measured
+time).  Everything that takes runs of its own -- the sustained and sampled legs, measured peaks, the per-kernel profile and roofline,
+the communication block, host buffers, the bf16x3 leg, the secondary workloads and the CPU baseline -- runs only with --full.
+--dump-outputs DIR writes what the timed path computed in its last step as .npy files (see dump_outputs); the inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -198,6 +204,35 @@ def secondary_legs(device, steps=40):
     return out
 
 
+DUMP_BUDGET = 64 << 20                             # bytes, all files of --dump-outputs together
+DUMP_PARAM_SAMPLE = 1 << 21                        # parameters / gradients: a fixed seeded sample of the flat arena
+
+
+def dump_outputs(trainer, scal, out_dir):
+    """--dump-outputs: what the caller of the timed step receives after its last step, as float32 / float64 .npy files in out_dir.
+      scalars.npy       float64 [4]: loss, simloss, recon1, recon2 (global over ranks)
+      out.npy, out2.npy float32 [b, H, W, 3]: the decoder outputs of the last training forward, the first b frames of the batch
+                        (as many as DUMP_BUDGET leaves room for: all 256 of the default batch)
+      params_sample.npy float32 [n]: the parameters after the last Adam update at n = DUMP_PARAM_SAMPLE fixed positions of the flat
+                        arena (np.random.default_rng(0), sorted)
+      grads_sample.npy  float32 [n]: the last step's gradients at the same positions
+    Written by rank 0 (its own shard's out / out2; parameters are identical on every rank)."""
+    os.makedirs(out_dir, exist_ok=True)
+    tr = trainer.translator
+    tr.sync()
+    np.save(os.path.join(out_dir, "scalars.npy"),
+            np.array([scal["loss"], scal["simloss"], scal["recon1"], scal["recon2"]], np.float64))
+    n = tr.n_params
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_PARAM_SAMPLE), replace=False))
+    np.save(os.path.join(out_dir, "params_sample.npy"), tr.get_params_flat()[idx])
+    np.save(os.path.join(out_dir, "grads_sample.npy"), tr.get_grads_flat()[idx])
+    out, out2, _ = tr.last_outputs(out=True, out2=True)
+    per_frame = 2 * out[0].nbytes
+    keep = max(1, min(out.shape[0], (DUMP_BUDGET - 2 * idx.size * 4 - (1 << 16)) // per_frame))
+    np.save(os.path.join(out_dir, "out.npy"), np.ascontiguousarray(out[:keep]))
+    np.save(os.path.join(out_dir, "out2.npy"), np.ascontiguousarray(out2[:keep]))
+
+
 def _median_min(ts):
     ts = sorted(ts)
     return ts[len(ts) // 2], ts[0]
@@ -381,21 +416,27 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch (BASELINE config: 256)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every extra measurement (sustained, sampled, peaks, per-kernel roofline, comm block, bf16x3, secondary "
+                         "legs, CPU baseline); the --no-* switches below turn single legs off again.  Off: the timed steps and the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed to DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--kernel-iters", type=int, default=5)
     ap.add_argument("--host-buffers", action="store_true",
-                    help="also time ctx_train_step on host (numpy) frames: the PCIe-inclusive rate quoted in DESIGN.md")
+                    help="with --full: also time ctx_train_step on host (numpy) frames: the PCIe-inclusive rate quoted in DESIGN.md")
     ap.add_argument("--precision", choices=["f32", "bf16x3"], default=os.environ.get("CTX_PRECISION", "f32"),
                     help="arithmetic of the contractions: exact f32 MFMA (default) or split-bf16 products (DESIGN.md section 6b)")
     ap.add_argument("--no-split-leg", action="store_true",
-                    help="skip the extra bf16x3 measurement that a default (f32) run appends as line['bf16x3']")
+                    help="skip the extra bf16x3 measurement that a --full f32 run appends as line['bf16x3']")
     ap.add_argument("--sustained-s", type=float, default=3.0,
-                    help="after the timed run, keep stepping for at least this many seconds and report sustained_ms_per_step (0 = skip)")
+                    help="with --full: after the timed run, keep stepping for at least this many seconds and report sustained_ms_per_step "
+                         "(0 = skip)")
     ap.add_argument("--no-sampled", action="store_true",
-                    help="skip the extra leg that runs the trainer's own step (ctx_train_step_sampled / ctx_dp_train_step_sampled: the batch "
+                    help="skip the --full leg that runs the trainer's own step (ctx_train_step_sampled / ctx_dp_train_step_sampled: the batch "
                          "gathered on the device from a resident uint8 demo tensor, global index arrays from the host) -- line['sampled']")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary legs (ContextAEReal 36x64 B=256, config-4 share) a default 1-GPU run appends as line['secondary']")
+                    help="skip the secondary legs (ContextAEReal 36x64 B=256, config-4 share) a --full 1-GPU run appends as line['secondary']")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:       # plain `python bench.py --gpus N`: start the ranks ourselves
@@ -507,11 +548,13 @@ def main():
         return dt_, tr_.scalars(), ev_
 
     dt, scal, step_events = timed(trainer)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(trainer, scal, args.dump_outputs)
 
     # Sustained leg (never `value`): the K timed steps are a fraction of a second; clocks settle to the power budget over seconds
     # (MI355X_MICROARCH.md, DVFS), so the same step is run on for >= --sustained-s seconds and reported beside the contract's figure.
     sustained = None
-    if args.sustained_s > 0:
+    if args.full and args.sustained_s > 0:
         n_sus = max(args.steps, int(args.sustained_s / (dt / args.steps)) + 1)
         barrier()
         t0 = time.perf_counter()
@@ -529,7 +572,7 @@ def main():
     # the two GLOBAL index arrays (np.random.choice, train_script.py:154-155) and every rank gathers its rows on the device.  Includes the
     # host-side enqueue of each step and the 2 x 4 B x world bytes of indices.
     sampled = None
-    if not args.no_sampled and dp_client in ("cabi", "single") and args.precision == "f32":
+    if args.full and not args.no_sampled and dp_client in ("cabi", "single") and args.precision == "f32":
         try:
             trl = trainer.translator
             rng = np.random.default_rng(5)
@@ -570,7 +613,7 @@ def main():
         "metric": "frames/sec fwd+bwd+Adam, 64x64x3, batch 256 per GPU",
         "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": args.precision, "data": "synthetic",
+        "dtype": args.precision, "data": "synthetic", "full": args.full,
         "config": {"workload": "ContextSkipNew 64x64x3 fwd+bwd+Adam, batch 256/GPU (BASELINE configs[1])",
                    "precision": ("exact f32 MFMA" if args.precision == "f32" else
                                  "split-bf16: a*b = hi*hi + hi*lo + lo*hi on bf16 MFMA, f32 accumulate; f32 everywhere else"),
@@ -601,7 +644,7 @@ def main():
             "ridge_flop_per_byte": PEAK_F32_MFMA / PEAK_HBM,
         },
     }
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         # "confirm on the box with a copy kernel and an FMA loop and report measured peaks too".  tools/libpeaks.so (built by
         # __graft_entry__.build(), not part of the product): an f32 matrix-core loop and a stream copy, outside the timed region.
         try:
@@ -618,7 +661,7 @@ def main():
                 "step_useful_frac_of_measured_mfma": (line["step_rates"]["tflops_useful"] / mf) if mf > 0 else None}
         except OSError:
             line["peaks_measured"] = None
-    if dist.is_initialized():
+    if args.full and dist.is_initialized():
         # Outside the timed region: what one step spends in compute and what the gradient all-reduce costs alone, so that the
         # per-N values can be read (exposed communication = ms_per_step - compute_ms; an overlapped schedule can hide at most
         # min(allreduce_ms, backward time)).  Every rank runs it; rank 0 reports its own clock.
@@ -672,7 +715,7 @@ def main():
                             "client": dp_client, "overlap": dp_client == "cabi" or os.environ.get("CTX_DP_OVERLAP", "0") == "1"}
         except Exception as e:                      # diagnostics must never cost the bench line
             line["comm"] = {"error": repr(e)}
-    if rank == 0:
+    if args.full and rank == 0:
         # dominant kernel: timed with HIP events on the handle's stream
         tr = trainer.translator
         ents = tr.profile_step(src.data_ptr(), ctx.data_ptr(), tgt.data_ptr(), B, lr=1e-4, iters=args.kernel_iters)
@@ -757,6 +800,7 @@ def main():
             line["secondary"] = secondary_legs(local_rank)
         if not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(batch=32, steps=10)
+    if rank == 0:
         import ctypes
         ctypes.CDLL(None).fflush(None)
         sys.stdout.flush()

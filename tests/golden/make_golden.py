@@ -15,6 +15,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 from oracle import ctx_oracle as o  # noqa: E402
+from tests._golden import save_fixture  # noqa: E402  (a fixture over 1 MiB continues in <tag>.part2.npz)
 
 N_HEAD = 64
 
@@ -82,7 +83,7 @@ def make(tag, cfg, B, pseed, stddev, frames, steps, lr=1e-4):
         [int(np.prod(s)) for _, s in o.param_specs(cfg)])[:-1])])
     fx["delta_head"] = delta[:N_HEAD]
     path = os.path.join(HERE, f"{tag}.npz")
-    np.savez_compressed(path, **fx)
+    save_fixture(path, fx)
     print(tag, os.path.getsize(path), "bytes; loss", res["loss"])
 
 
@@ -122,7 +123,7 @@ def make_real(tag, cfg, B, pseed, stddev, frames, steps, lr=1e-4):
     fx["delta_digest"] = np.stack([digest(dd)[0] for dd in np.split(delta, np.cumsum(
         [int(np.prod(s)) for _, s in r.param_specs(cfg)])[:-1])])
     path = os.path.join(HERE, f"{tag}.npz")
-    np.savez_compressed(path, **fx)
+    save_fixture(path, fx)
     print(tag, os.path.getsize(path), "bytes; loss", res["loss"])
 
 
@@ -161,7 +162,7 @@ def make_incep2(tag, cfg, B, pseed, stddev, fseed, steps, lr=1e-4):
         traj.append([rr["loss"], rr["simloss"], rr["recon1"], rr["recon2"]])
     fx["train_scalars"] = np.array(traj)
     path = os.path.join(HERE, f"{tag}.npz")
-    np.savez_compressed(path, **fx)
+    save_fixture(path, fx)
     print(tag, os.path.getsize(path), "bytes; loss", res["loss"])
 
 
@@ -178,7 +179,7 @@ def make_inception_v3(tag, pseed, fseed, B, S):
               endpoint_head=np.stack([digest(v)[1] for v in ep.values()]))
     fx["param_digest"], _ = digest(np.concatenate([np.asarray(v).reshape(-1) for v in p.values()]))
     path = os.path.join(HERE, f"{tag}.npz")
-    np.savez_compressed(path, **fx)
+    save_fixture(path, fx)
     print(tag, os.path.getsize(path), "bytes")
 
 
@@ -305,7 +306,7 @@ def make_b256(chunk=16):
     fx["act_negative"] = np.array([act_stats[k][0] for k in sorted(act_stats)], np.int64)
     fx["act_near_zero"] = np.array([act_stats[k][1] for k in sorted(act_stats)], np.int64)
     path = os.path.join(HERE, f"{B256_TAG}.npz")
-    np.savez_compressed(path, **fx)
+    save_fixture(path, fx)
     print(B256_TAG, os.path.getsize(path), "bytes; loss", fx["scalars"][0], f"{time.time() - t0:.0f}s")
 
 
@@ -411,7 +412,7 @@ def make_ref299():
     rr, cc = ci.forward(p, src, ctx, tgt, cfg)
     fx["train_scalars"] = np.array([fx["scalars"], [rr["loss"], rr["simloss"], rr["recon1"], rr["recon2"]]])
     path = os.path.join(HERE, f"{REF299_TAG}.npz")
-    np.savez_compressed(path, **fx)
+    save_fixture(path, fx)
     print(REF299_TAG, os.path.getsize(path), "bytes; loss", fx["scalars"][0], "->", rr["loss"], f"{time.time() - t0:.0f}s")
 
 
@@ -429,7 +430,7 @@ def make_inception_v3_299():
               endpoint_head=np.stack([digest(v)[1] for v in ep.values()]))
     fx["param_digest"], _ = digest(np.concatenate([np.asarray(v).reshape(-1) for v in p.values()]))
     path = os.path.join(HERE, f"{REF299_FRONT_TAG}.npz")
-    np.savez_compressed(path, **fx)
+    save_fixture(path, fx)
     print(REF299_FRONT_TAG, os.path.getsize(path), "bytes")
 
 
@@ -575,7 +576,7 @@ def make_big(tag):
     scalars2, _, _, _ = _big_pass(mod, cfg, p, x, B, chunk, want_grads=False)
     fx["train_scalars"] = np.stack([scalars, scalars2])
     path = os.path.join(HERE, f"{tag}.npz")
-    np.savez_compressed(path, **fx)
+    save_fixture(path, fx)
     print(tag, os.path.getsize(path), "bytes; loss", scalars[0], "->", scalars2[0], f"{time.time() - t0:.0f}s", flush=True)
 
 

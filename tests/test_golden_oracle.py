@@ -112,7 +112,8 @@ def test_incep2_oracle_reproduces_the_reference_size_golden():
     are guarded by the generator run; a backward pass here would double the test's 10 GB)."""
     from oracle import ctx_oracle_incep as ci
     from tests.golden import make_golden as mg
-    z = np.load(os.path.join(os.path.dirname(__file__), "golden", mg.REF299_TAG + ".npz"))
+    from tests import _golden
+    z = _golden.load(mg.REF299_TAG)
     cfg, p32, feats = mg.ref299_case()
     np.testing.assert_allclose(digest(ci.flatten(p32, cfg)), z["param_digest"], rtol=1e-12)
     assert ci.param_count(cfg) == 153_111_040

@@ -51,7 +51,8 @@ def test_config1_batch256_against_the_float64_oracle_fixture(T):
     lrelu' branch flips (activations the f32 pass puts on the other side of zero than float64 does) are COUNTED and printed
     per buffer, not aligned away; the gradient bounds below are what holds with them in."""
     from tests.golden import make_golden as mg
-    z = np.load(os.path.join(os.path.dirname(__file__), "golden", mg.B256_TAG + ".npz"))
+    from tests import _golden
+    z = _golden.load(mg.B256_TAG)
     cfg, p, frames = mg.b256_case()
     np.testing.assert_allclose(mg.digest(o.flatten(p, cfg))[0], z["param_digest"], rtol=1e-12)      # RNG drift guard
     B = int(z["B"])

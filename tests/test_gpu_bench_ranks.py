@@ -25,7 +25,7 @@ def run_bench(n, extra=(), timeout=900):
     assert os.path.exists(FAKE), "tests/fake_rccl/libfakerccl.so is not built (python -c 'import __graft_entry__ as g; g.build()')"
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(BENCH_ONE_GPU="1", CTX_RCCL_LIB=FAKE, FAKE_RCCL_TIMEOUT_S="300")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1", "--batch", "8",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(n), "--steps", "3", "--warmup", "1", "--batch", "8",
            "--no-cpu-baseline", "--no-split-leg", "--no-secondary", "--sustained-s", "0.2", "--kernel-iters", "1", *extra]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-4000:]

@@ -40,7 +40,8 @@ def _open(T, kind, cfg, B):
 @pytest.mark.parametrize("tag", ["real_f100_36x64_b100", "real_f100_36x64_b256", "real_f100_64x64_b256", "incep2_2x2x2048_f1024_b64"])
 def test_bench_launch_shape_against_the_float64_fixture(T, tag):
     from tests.golden import make_golden as mg
-    z = np.load(os.path.join(GOLD, tag + ".npz"))
+    from tests import _golden
+    z = _golden.load(tag)
     kind = mg.BIG_CASES[tag][0]
     mod, cfg, p32, (src, ctx, tgt) = mg.big_case(tag)
     np.testing.assert_allclose(mg.digest(mod.flatten(p32, cfg))[0], z["param_digest"], rtol=1e-12)         # RNG drift guards

@@ -71,7 +71,8 @@ def test_inception_front_end_at_299x299_matches_the_fixture_and_the_oracle(T):
 
 def _ref299_fixture():
     from tests.golden import make_golden as mg
-    z = np.load(os.path.join(GOLD, mg.REF299_TAG + ".npz"))
+    from tests import _golden
+    z = _golden.load(mg.REF299_TAG)
     cfg, p32, feats = mg.ref299_case()
     from oracle import ctx_oracle_incep as ci
     np.testing.assert_allclose(digest(ci.flatten(p32, cfg)), z["param_digest"], rtol=1e-12)      # RNG drift guard

@@ -33,7 +33,7 @@ for N in $NS; do
     python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29600 + N)) tools/dp_world_check.py > $OUT/world_$N.txt 2>&1 \
       && echo "N=$N: ctx_dp_world ok on every rank: $(grep -c 'world ok' $OUT/world_$N.txt) ranks" || { echo "N=$N: ctx_dp_world check FAILED (see $OUT/world_$N.txt)"; tail -5 $OUT/world_$N.txt; }
   fi
-  python bench.py --gpus $N --steps ${STEPS:-30} --warmup 10 --no-cpu-baseline --no-secondary --no-split-leg $EXTRA > $OUT/bench_$N.json 2> $OUT/bench_$N.err || { echo "N=$N: bench.py failed"; tail -5 $OUT/bench_$N.err; }
+  python bench.py --full --gpus $N --steps ${STEPS:-30} --warmup 10 --no-cpu-baseline --no-secondary --no-split-leg $EXTRA > $OUT/bench_$N.json 2> $OUT/bench_$N.err || { echo "N=$N: bench.py failed"; tail -5 $OUT/bench_$N.err; }
 done
 python - <<'PY'
 import glob, json, os

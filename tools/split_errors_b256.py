@@ -15,9 +15,10 @@ sys.path.insert(0, ROOT)
 from imitation_from_observation_amd import Translator  # noqa: E402
 from oracle import ctx_oracle as o  # noqa: E402
 from tests.golden import make_golden as mg  # noqa: E402
+from tests import _golden  # noqa: E402
 
 label = sys.argv[1] if len(sys.argv) > 1 else "split build"
-z = np.load(os.path.join(ROOT, "tests", "golden", mg.B256_TAG + ".npz"))
+z = _golden.load(mg.B256_TAG)
 cfg, p, frames = mg.b256_case()
 B = int(z["B"])
 src, ctx, tgt = (o.preprocess_u8(f) for f in frames)
