@@ -27,6 +27,13 @@ CTX_LOSS_RECON1, CTX_LOSS_RECON2, CTX_LOSS_SIM = 1, 2, 4
 LOSS_ABLATIONS = {"None": 7, "L2": 3, "L2L3": 1, "L1": 6}
 
 
+class CtxVjpArgs(ctypes.Structure):
+    """ctx_vjp_args of include/ctxtrans.h: device pointers (None = zero cotangent / frame gradient not wanted)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("d_out", "d_out2", "d_input_z", "d_translated_z")] + \
+               [("loss_weight", ctypes.c_float), ("sim_batch", ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in ("d_src_frames", "d_ctx_frames", "d_tgt_frames")]
+
+
 class CtxProfEntry(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 56), ("kernel", ctypes.c_char * 40), ("flops", ctypes.c_double),
                 ("ms", ctypes.c_float), ("useful_frac", ctypes.c_float)]
@@ -96,6 +103,9 @@ SIGNATURES = {
     "ctx_dev_frames": (_c.c_int, [_P, _c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p)]),
     "ctx_dev_forward": (_c.c_int, [_P, _P, _P, _P, _c.c_int]),
     "ctx_dev_train_step": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_float]),
+    "ctx_dev_forward_vjp": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_int, _c.c_int64, _c.POINTER(_c.c_uint64)]),
+    "ctx_dev_backward_vjp": (_c.c_int, [_P, _c.c_uint64, _c.POINTER(CtxVjpArgs)]),
+    "ctx_params_written": (_c.c_int, [_P]),
     "ctx_set_grad_bucket_callback": (_c.c_int, [_P, _P, _P]),
     "ctx_dev_adam": (_c.c_int, [_P, _c.c_float]),
     "ctx_dev_scalars": (_c.c_int, [_P, _F]),

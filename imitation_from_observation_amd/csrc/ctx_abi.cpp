@@ -428,6 +428,63 @@ int ctx_dev_forward(ctx_handle* h, const float* d_src, const float* d_ctx, const
     return CTX_OK;
 }
 
+int ctx_dev_forward_vjp(ctx_handle* h, const float* d_src, const float* d_ctx, const float* d_tgt, int B, int dropout, int64_t drop_step,
+                        uint64_t* token) {
+    TRY(check_B(h, B));
+    if (!d_src || !d_ctx || !d_tgt || !token) return fail(h, CTX_E_INVALID, "NULL input");
+    if (drop_step < -1) return fail(h, CTX_E_INVALID, "drop_step must be >= 0, or -1 (the handle's Adam step count)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    TRY(stage_frames(h, d_src, d_ctx, d_tgt, B));
+    h->drop_on = dropout != 0;
+    h->drop_step = drop_step;
+    forward(h, B, MODE_TRAIN);
+    h->drop_on = false;
+    h->drop_step = -1;
+    losses(h->stream, h->out, h->img, nullptr, h->npi, B, h->Z, h->Z + (int64_t)B * h->Fp, nullptr, h->Fp, B, h->scratch, h->scalars, h->F, loss_terms_of(h));
+    h->last_B = B;
+    h->vjp_token = h->act_serial;    // (forward bumped it: never 0)
+    h->vjp_B = B;
+    h->vjp_drop = dropout != 0;
+    *token = h->vjp_token;
+    HIP_TRY(h, hipGetLastError());
+    return CTX_OK;
+}
+
+int ctx_dev_backward_vjp(ctx_handle* h, uint64_t token, const ctx_vjp_args* a) {
+    if (!h || !a) return h ? fail(h, CTX_E_INVALID, "NULL args") : CTX_E_INVALID;
+    if (token == 0 || token != h->vjp_token || token != h->act_serial)
+        return fail(h, CTX_E_STATE, "VJP token %llu is not the live forward: a later call overwrote its activations, or its backward has run "
+                    "(one forward_vjp per backward_vjp, one live graph per handle)", (unsigned long long)token);
+    if (a->sim_batch < 0) return fail(h, CTX_E_INVALID, "sim_batch < 0");
+    const int B = h->vjp_B;
+    if (a->d_src_frames || a->d_ctx_frames || a->d_tgt_frames) {      // frame gradients of a 3-channel first layer: convt3's direct kernel
+        int c = 0, hs = 0, ws = 0, s = 2;
+        if (h->gen) { const GenState& r = *h->gen; if (r.C0 == 3) { c = r.cp[0]; hs = r.gh[0]; ws = r.gw[0]; s = r.se[0]; } }
+        else { c = h->d; hs = h->hh[1]; ws = h->ww[1]; }
+        if (c && !convt3_direct_ok(c, 0, hs, ws, s))
+            return fail(h, CTX_E_INVALID, "frame gradients: the direct transposed conv is not built for %d channels on a %dx%d grid", c, hs, ws);
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const ctx_bucket_fn fn = h->bucket_fn;
+    h->bucket_fn = nullptr;
+    h->vjp = a;
+    h->drop_on = h->vjp_drop;
+    backward(h, B, a->sim_batch ? a->sim_batch : B);
+    h->drop_on = false;
+    h->vjp = nullptr;
+    h->bucket_fn = fn;
+    h->vjp_token = 0;
+    { char msg[256]; if (take_launch_error(msg, sizeof msg)) return fail(h, CTX_E_DEVICE, "%s", msg); }
+    HIP_TRY(h, hipGetLastError());
+    return CTX_OK;
+}
+
+int ctx_params_written(ctx_handle* h) {
+    if (!h) return CTX_E_INVALID;
+    h->pack.version++;               // packed filters go stale; graphs captured on them are dropped at their next call (forward_inference)
+    return CTX_OK;
+}
+
 int ctx_dev_frames(ctx_handle* h, int B, float** d_src, float** d_ctx, float** d_tgt) {
     TRY(check_B(h, B));
     if (d_tgt) *d_tgt = h->img;

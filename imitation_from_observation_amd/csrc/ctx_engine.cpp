@@ -532,6 +532,53 @@ void encoder_fwd(ctx_handle* h, const std::string& scn, const Scope& sc, const f
 }
 
 
+// The seeds of the backward: d loss / d out of the 2B decoder rows into h->dout and d simloss / d [trans_z ; tgt_z] into dsim2 (row
+// stride ldz, F_real code columns; 0 = ldz).  Under a VJP (h->vjp) they are  loss_weight * those + the caller's cotangents; with
+// loss_weight 1 and no cotangents they ARE the losses kernel's values, the second pass is not launched.
+void seed_grads(ctx_handle* h, int B, int sim_batch, float* dsim2, int ldz, int F_real) {
+    ProfScope ps(h, "losses", K_EW, 0.0);
+    losses(h->stream, h->out, h->img, h->dout, h->npi, B, h->Z, h->Z + (int64_t)B * ldz, dsim2, ldz, sim_batch, h->scratch, h->scalars, F_real, loss_terms_of(h));
+    const ctx_vjp_args* a = h->vjp;
+    if (!a || (a->loss_weight == 1.f && !a->d_out && !a->d_out2 && !a->d_translated_z)) return;
+    const int64_t half = (int64_t)B * h->npi;
+    const int F = F_real > 0 ? F_real : ldz;
+    vjp_seed(h->stream, h->dout, half, a->loss_weight, a->d_out, half, 1, half);
+    vjp_seed(h->stream, h->dout + half, half, a->loss_weight, a->d_out2, half, 1, half);
+    if (a->loss_weight != 1.f || a->d_translated_z) vjp_seed(h->stream, dsim2, ldz, a->loss_weight, a->d_translated_z, F, B, F);
+    if (a->loss_weight != 1.f) vjp_seed(h->stream, dsim2 + (int64_t)B * ldz, ldz, a->loss_weight, nullptr, 0, B, ldz);
+}
+
+// VJP: the caller's d input_z joins the gradient of src_z (row block 2 of dZ, stride ldz) before src_z's lrelu' is applied
+void seed_input_z(ctx_handle* h, int B, int ldz) {
+    if (h->vjp && h->vjp->d_input_z) vjp_seed(h->stream, h->dZ + 2ll * B * ldz, ldz, 1.f, h->vjp->d_input_z, h->F, B, h->F);
+}
+
+// VJP frame gradients of a 3-channel first layer: d frames = conv2d_transpose(dA0, W_h0) with the h0 filter in its own layout
+// [5,5,3,c] -- the SAME geometry d_h4's forward computes (convt3.hip), with one operand (c2 = 0) and a zero bias.  dA0 holds the
+// image slots [slot0, slot0 + nimg / B) of [tgt | src | ctx]; each slot goes to the caller's buffer, or nowhere if it gave none.
+float* vjp_frame_out(const ctx_handle* h, int slot) {
+    const ctx_vjp_args* a = h->vjp;
+    return !a ? nullptr : slot == 0 ? a->d_tgt_frames : slot == 1 ? a->d_src_frames : a->d_ctx_frames;
+}
+// the tgt frames are also recon1 / recon2's target: their frame gradient gets loss_weight x that direct term on top
+void recon_tgt_term(ctx_handle* h, float* d_tgt) {
+    const int B = h->vjp_B, terms = loss_terms_of(h);
+    const float lw = h->vjp->loss_weight;
+    if (lw == 0.f || !(terms & 3)) return;
+    const int64_t n = (int64_t)B * h->npi;
+    vjp_recon_tgt(h->stream, d_tgt, h->out, h->out + n, h->img, n, terms & 1 ? lw : 0.f, terms & 2 ? lw : 0.f);
+}
+void frame_grads3(ctx_handle* h, const float* dA0, int c, int slot0, int nimg, int hs, int ws, int stride, const float* w) {
+    const int B = h->vjp_B;
+    for (int j = 0; j < nimg / B; ++j) {
+        float* o = vjp_frame_out(h, slot0 + j);
+        if (!o) continue;
+        ProfScope ps(h, "frames dx", K_CONVT3D, 2.0 * B * hs * ws * 25 * c * 3, tap_frac(hs * stride, ws * stride, 5, stride));
+        convt3_direct(h->stream, dA0 + (int64_t)j * B * hs * ws * c, c, dA0, 0, 1, B, hs, ws, stride, w, h->zeros, o);
+        if (slot0 + j == 0) recon_tgt_term(h, o);
+    }
+}
+
 }  // namespace ctxi
 #include "ctxtrans_gen.inc"
 namespace ctxi {
@@ -541,6 +588,7 @@ namespace ctxi {
 // pass 1) -- the subgraph TF would run for base.py:216-218.  ENCODE: `conv` encoder on src only.
 void forward(ctx_handle* h, int B, Mode mode) {
     OptScope os(&h->opt);
+    h->act_serial++;
     if (h->gen) { gen_forward(h, B, mode); return; }
     g_zeros = h->zeros;
     const int d = h->d, F = h->F;
@@ -623,17 +671,15 @@ void forward(ctx_handle* h, int B, Mode mode) {
 // scripts/train_script.py:128).  Every gradient tensor is written exactly once.
 void backward(ctx_handle* h, int B, int sim_batch) {
     OptScope os(&h->opt);
+    h->act_serial++;
     if (h->gen) { gen_backward(h, B, sim_batch); return; }
     g_zeros = h->zeros;
     const int d = h->d, F = h->F;
     const int64_t npi = h->npi;
     float* tgt_z = h->Z + (int64_t)B * F;
     float* src_z = h->Z + 2ll * B * F;
-    {
-        ProfScope ps(h, "losses", K_EW, 0.0);
-        losses(h->stream, h->out, h->img, h->dout, npi, B, h->Z, tgt_z, h->dsim2, F, sim_batch, h->scratch, h->scalars, 0, loss_terms_of(h));
-        if (!use_dc3(h)) pack_c4(h, h->dout, 2ll * B * h->H * h->W);
-    }
+    seed_grads(h, B, sim_batch, h->dsim2, F, 0);
+    if (!use_dc3(h)) pack_c4(h, h->dout, 2ll * B * h->H * h->W);
 
     // ---- decoder, both passes at once (batch 2B)
     const float* dy = h->dout;
@@ -715,11 +761,12 @@ void backward(ctx_handle* h, int B, int sim_batch) {
         Epi e2;   // d concat: cols < F -> d src_z (row block 2 of dZ), cols >= F -> d ctx_z
         e2.out1 = h->dZ + 2ll * B * F; e2.ld1 = F; e2.nsplit = F; e2.out2 = h->dcz; e2.ld2 = F;
         fc_dx(h, "translate/trans_h0", h->dth0, B, F, h->Wp("translate/trans_h0/Matrix"), 2 * F, e2);
+        seed_input_z(h, B, F);
     }
     fire_bucket(h, h->find("translate/trans_h0/Matrix"));
     // ---- encoders
     auto encoder_bwd = [&](const std::string& scn, const Scope& sc, const float* x, int nimg, float* const act[5], float* dzp, float* const dA[5],
-                           bool with_skips, int dw_lane) {
+                           bool with_skips, int dw_lane, int slot0) {
         const int K3 = h->hh[4] * h->ww[4] * 8 * d;
         { Side sd(h, dw_lane); fc_dw(h, scn + "/hz_lin", nm(act[4], F, F, nimg), F, dzp, nimg, F, sc.gwz, sc.gbz); }
         Epi e4;
@@ -746,6 +793,7 @@ void backward(ctx_handle* h, int B, int sim_batch) {
             Epi eg;
             eg.out1 = sc.gw[k]; eg.ld1 = cb;
             if (k == 0) {
+                {
                 Side sd(h, dw_lane);
                 if (!use_dc3(h)) bias_grad(h, ln, dA[k], R, cb, sc.gb[k]);       // (dconv_wgrad returns the column sums of its small operand too)
                 if (use_dc3(h)) {
@@ -759,7 +807,9 @@ void backward(ctx_handle* h, int B, int sim_batch) {
                     ProfScope ps(h, ln + " dw", K_C3WGRAD, fl, uf);
                     conv3_wgrad(h->stream, NmC3WgradBig{c4of(h, xin), hb, wb, make_pixdiv(hs, wsm), R, g_zeros}, small, eg, cb, ws_of(h));
                 }
-                break;   // no gradient w.r.t. the frame
+                }
+                if (h->vjp) frame_grads3(h, dA[0], cb, slot0, nimg, hs, wsm, 2, sc.w[0]);   // (the training step has no frame gradient)
+                break;
             }
             { Side sd(h, dw_lane);
               bias_grad(h, ln, dA[k], R, cb, sc.gb[k]);
@@ -796,12 +846,12 @@ void backward(ctx_handle* h, int B, int sim_batch) {
         // everything it reads (dcz, dSk[*], c[*]) was produced before this point
         fork(h, LANE_CTX);
         LaneSwap sw(h, LANE_CTX);
-        encoder_bwd("conv_context", scope_of(h, "conv_context"), h->img + 2 * B * npi, B, h->c, h->dcz, h->dC, true, -1);
+        encoder_bwd("conv_context", scope_of(h, "conv_context"), h->img + 2 * B * npi, B, h->c, h->dcz, h->dC, true, -1, 2);
     }
     { ProfScope ps(h, "conv/hz_lin lrelu'", K_EW, 0.0); lrelu_mask(h->stream, dSz, tgt_z, 2ll * B * F); }
-    encoder_bwd("conv", scope_of(h, "conv"), h->img, 2 * B, h->s, dSz, h->dS, false, LANE_DW);
+    encoder_bwd("conv", scope_of(h, "conv"), h->img, 2 * B, h->s, dSz, h->dS, false, LANE_DW, 0);
     if (lanes) { join(h, LANE_CTX); join(h, LANE_DW); }
-    else encoder_bwd("conv_context", scope_of(h, "conv_context"), h->img + 2 * B * npi, B, h->c, h->dcz, h->dC, true, -1);
+    else encoder_bwd("conv_context", scope_of(h, "conv_context"), h->img + 2 * B * npi, B, h->c, h->dcz, h->dC, true, -1, 2);
     h->have_grads = true;
 
 }
@@ -811,6 +861,7 @@ void backward(ctx_handle* h, int B, int sim_batch) {
 // B = 25: 1.7 -> 0.9 ms per call).  All buffers are owned by the handle, so the captured pointers stay valid; parameters are
 // read through the arena pointer at replay.  CTX_GRAPHS=0 keeps plain launches.
 int forward_inference(ctx_handle* h, int B, Mode mode) {
+    h->act_serial++;                 // (a replayed graph overwrites the activations too)
     if (!h->use_graphs || h->prof_on || B > 64) { forward(h, B, mode); return CTX_OK; }
     ctx_handle::GraphSlot& g = h->graphs[(int)mode * (1 << 20) + (mode == MODE_TRANSLATE && h->ctx_single ? 1 << 19 : 0) + B];
     // A graph captured while every packed filter it uses was stale holds all its pack nodes ("self-packing": right after a training step)

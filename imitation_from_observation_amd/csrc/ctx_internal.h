@@ -181,6 +181,14 @@ struct ctx_handle {
     // tf.nn.dropout (CTX_VARIANT_REAL with keep_prob < 1): on only while a TRAINING step (forward + backward) is being enqueued
     bool drop_on = false;
     uint64_t drop_seed = 0;
+    int64_t drop_step = -1;       // >= 0: the mask hash's step for the forward being enqueued (ctx_dev_forward_vjp); -1: adam_t
+
+    // vector-Jacobian products (ctx_dev_forward_vjp / ctx_dev_backward_vjp): every forward and backward bumps act_serial; a token is
+    // the serial right after its forward and is good while nothing else has run.  `vjp` is set only while a VJP backward is enqueued.
+    uint64_t act_serial = 0, vjp_token = 0;
+    int vjp_B = 0;
+    bool vjp_drop = false;
+    const ctx_vjp_args* vjp = nullptr;
 
     // per-op profiling (ctx_profile_step): HIP events around every launch group
     bool prof_on = false;

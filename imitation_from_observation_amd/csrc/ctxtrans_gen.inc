@@ -289,7 +289,7 @@ void gen_forward(ctx_handle* h, int B, Mode mode) {
         const float kp = h->cfg.keep_prob;
         // data parallel: every rank draws its OWN masks (rank mixed into the seed; rank 0 = the single-device stream), so the global
         // batch sees B * world distinct masks instead of the same B on every shard
-        const uint32_t seed = (uint32_t)h->drop_seed ^ (h->dp_comm ? 0x9E3779B9u * (uint32_t)h->dp_rank : 0u), step = (uint32_t)h->adam_t;
+        const uint32_t seed = (uint32_t)h->drop_seed ^ (h->dp_comm ? 0x9E3779B9u * (uint32_t)h->dp_rank : 0u), step = (uint32_t)(h->drop_step >= 0 ? h->drop_step : h->adam_t);
         const int F = h->F, f3 = r.nf[3], c3 = r.cp[3], D0 = r.gh[3] * r.gw[3] * f3;
         drop_factors(h->stream, r.dM[1], 3 * B, D0p, c3, f3, D0, kp, seed, step, 1);
         drop_factors(h->stream, r.dM[2], 3 * B, Fp, Fp, F, F, kp, seed, step, 2);
@@ -386,20 +386,38 @@ void gen_forward(ctx_handle* h, int B, Mode mode) {
     }
 }
 
+// VJP frame / feature-map gradients, one launch per image slot [tgt | src | ctx] the caller asked for.  3-channel frames
+// (ContextAEReal): the direct transposed conv of frame_grads3.  Feature maps (ContextAEInception2, C a multiple of 32): the
+// implicit-GEMM dx path of the deeper layers (`dx`), no lrelu'; out = decode + tgtctx adds d out + d out2 to the ctx maps.  The tgt
+// slot adds the recon terms' direct gradient w.r.t. their target (recon_tgt_term) in either case.
+struct GenPart { int img0, nimg, set; bool skips; };   // images [img0, img0 + nimg) of [tgt | src | ctx] through encoder `set`
+template <class DX>
+void gen_frame_grads(ctx_handle* h, int B, const DX& dx) {
+    const GenState& r = *h->gen;
+    if (r.C0 == 3) {
+        frame_grads3(h, r.dA[0], r.cp[0], 0, 3 * B, r.gh[0], r.gw[0], r.se[0], h->arena + r.w[0][0]);
+        return;
+    }
+    for (int j = 0; j < 3; ++j) {
+        float* o = vjp_frame_out(h, j);
+        if (!o) continue;
+        Epi ed;
+        ed.out1 = o; ed.ld1 = r.C0;
+        if (j == 2 && r.residual) { ed.add1 = h->dout; ed.lda1 = r.C0; ed.add2 = h->dout + (int64_t)B * h->npi; ed.lda2 = r.C0; }
+        dx(GenPart{j * B, B, j == 2 ? r.nset - 1 : 0, false}, ed, std::string(j == 0 ? "tgt" : j == 1 ? "src" : "ctx") + " frames dx");
+        if (j == 0) recon_tgt_term(h, o);
+    }
+}
+
 void gen_backward(ctx_handle* h, int B, int sim_batch) {
     g_zeros = h->zeros;
     GenState& r = *h->gen;
     const float* P = h->arena;
     float* G = h->arena + h->Ppad;
     const int Fp = r.Fp, D0p = (int)r.D0p, F = h->F;
-    const int64_t npi = h->npi;
     const bool drop = gen_drop(h);
-    float* tgt_z = h->Z + (int64_t)B * Fp;
-    {
-        ProfScope ps(h, "losses", K_EW, 0.0);
-        losses(h->stream, h->out, h->img, h->dout, npi, B, h->Z, tgt_z, r.dsim2, Fp, sim_batch, h->scratch, h->scalars, F, loss_terms_of(h));
-        if (r.C0 == 3 && !r.narrow) pack_c4(h, h->dout, 2ll * B * h->H * h->W);
-    }
+    seed_grads(h, B, sim_batch, r.dsim2, Fp, F);
+    if (r.C0 == 3 && !r.narrow) pack_c4(h, h->dout, 2ll * B * h->H * h->W);
     // ---- decoder, both passes (2B)
     const float* dy = h->dout;
     for (int k = 4; k >= 1; --k) {
@@ -476,13 +494,13 @@ void gen_backward(ctx_handle* h, int B, int sim_batch) {
     if (drop) ew_mul(h->stream, r.dDz, D0p, r.dDz, D0p, r.dM[6], D0p, 2 * B, D0p);       // site 6
     // image ranges.  Weights (and filter gradients): one encoder -> all 3B rows at once; two -> `conv` on [0,2B), `conv_context`
     // on [2B,3B).  Input gradients: rows of tgt/src images have no skip term, ctx rows add both decoder passes' skip gradients.
-    struct Part { int img0, nimg, set; bool skips; };
+    using Part = GenPart;
     const Part wparts2[2] = {{0, 2 * B, 0, false}, {2 * B, B, 1, true}};
     const Part wparts1[1] = {{0, 3 * B, 0, false}};
     const Part* wparts = r.nset == 2 ? wparts2 : wparts1;
     const Part xparts[2] = {{0, 2 * B, 0, false}, {2 * B, B, r.nset - 1, true}};
     auto scn = [](int set) { return std::string(set == 1 ? "conv_context" : "conv"); };
-    const bool chain = gen_rchain(h, B);
+    const bool chain = gen_rchain(h, B) && !(h->vjp && h->vjp->d_input_z);   // (rchain_bwd has no entry for a d input_z term)
     if (chain) {
         // d_h0_lin .. h4_lin: the input-gradient chain in one launch, then every Matrix / bias gradient in one grouped launch on the side lane
         const float* W[10];
@@ -526,6 +544,7 @@ void gen_backward(ctx_handle* h, int B, int sim_batch) {
             ew_mul(h->stream, h->dZ + 2ll * B * Fp, Fp, h->dZ + 2ll * B * Fp, Fp, r.dM[3], 2 * Fp, B, Fp);
             ew_mul(h->stream, h->dZ + 3ll * B * Fp, Fp, h->dZ + 3ll * B * Fp, Fp, r.dM[3] + Fp, 2 * Fp, B, Fp);
         }
+        seed_input_z(h, B, Fp);
     }
     fire_bucket(h, r.th0w);
     // ---- encoders over [tgt | src | ctx] (3B); every z has an lrelu
@@ -606,16 +625,12 @@ void gen_backward(ctx_handle* h, int B, int sim_batch) {
                 }
             }
         }
-        if (k == 0) break;                                       // nothing flows into the frames / features
-        // input gradient = conv2d_transpose of dA[k] with the filter read [K,K,ca,cb]
-        for (const Part& q : xparts) {
-            const int64_t so = (int64_t)q.img0 * hs * wsm * cb, bo = (int64_t)q.img0 * hb * wb * ca;
+        // input gradient = conv2d_transpose of dA[k] with the filter read [K,K,ca,cb], images [q.img0, q.img0 + q.nimg) into ed
+        auto dx = [&](const Part& q, const Epi& ed, const std::string& label) {
+            const int64_t so = (int64_t)q.img0 * hs * wsm * cb;
             const int Rp = q.nimg * hs * wsm;
             const float* w = P + r.w[q.set][k];
-            Epi ed;
-            ed.out1 = r.dA[k - 1] + bo; ed.ld1 = ca; ed.mask = r.a[k - 1] + bo; ed.ldm = ca;
-            if (q.skips) { ed.add1 = r.dSk[k - 1]; ed.lda1 = ca; ed.add2 = r.dSk[k - 1] + (int64_t)B * hb * wb * ca; ed.lda2 = ca; }
-            ProfScope ps(h, scn(q.set) + "/h" + std::to_string(k) + "_conv dx", r.narrow ? K_DCFWD : s == 2 ? K_CONVT : K_CONVT1, 2.0 * Rp * K2 * ca * cb, tap_frac_p(hb, wb, hs, wsm, Ke, s, pad));
+            ProfScope ps(h, label, r.narrow ? K_DCFWD : s == 2 ? K_CONVT : K_CONVT1, 2.0 * Rp * K2 * ca * cb, tap_frac_p(hb, wb, hs, wsm, Ke, s, pad));
             if (r.narrow) {                                      // conv2d_transpose of dA[k] with the filter read [5,5,ca,cb]: n = ca, k = cb
                 DcFwd D{};
                 D.x1 = r.dA[k] + so; D.ld1 = cb; D.c1 = cb; D.CI = cb; D.hin = hs; D.win = wsm; D.nimg = q.nimg;
@@ -640,6 +655,17 @@ void gen_backward(ctx_handle* h, int B, int sim_batch) {
                 bw.flip25 = 1; bw.K = Ke;
                 convt1_fwd(h->stream, ga, bw, ed, Rp, ca, ws_of(h));
             }
+        };
+        if (k == 0) {                                            // the training step has no gradient w.r.t. the frames / features
+            if (h->vjp) gen_frame_grads(h, B, dx);
+            break;
+        }
+        for (const Part& q : xparts) {
+            const int64_t bo = (int64_t)q.img0 * hb * wb * ca;
+            Epi ed;
+            ed.out1 = r.dA[k - 1] + bo; ed.ld1 = ca; ed.mask = r.a[k - 1] + bo; ed.ldm = ca;
+            if (q.skips) { ed.add1 = r.dSk[k - 1]; ed.lda1 = ca; ed.add2 = r.dSk[k - 1] + (int64_t)B * hb * wb * ca; ed.lda2 = ca; }
+            dx(q, ed, scn(q.set) + "/h" + std::to_string(k) + "_conv dx");
         }
     }
     if (use_lanes(h)) join(h, LANE_DW);

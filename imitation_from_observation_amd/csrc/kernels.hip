@@ -846,6 +846,33 @@ void drop_fin(hipStream_t s, float* out, const float* raw, const float* M, const
     hipLaunchKernelGGL(drop_fin_kernel, dim3(ew_blocks(n)), dim3(NTHREADS), 0, s, out, raw, M, add1, add2, act, n);
 }
 
+// Seeds of a caller-driven backward (ctx_dev_backward_vjp): y = w * y + x over a [rows, cols] block with own row strides, x nullable
+// (= 0).  One row per blockIdx.y, so no division per element.
+__global__ __launch_bounds__(NTHREADS) void vjp_seed_kernel(float* __restrict__ y, int64_t ldy, float w, const float* __restrict__ x,
+                                                            int64_t ldx, int64_t cols) {
+    float* yr = y + (int64_t)blockIdx.y * ldy;
+    const float* xr = x ? x + (int64_t)blockIdx.y * ldx : nullptr;
+    for (int64_t c = (int64_t)blockIdx.x * NTHREADS + threadIdx.x; c < cols; c += (int64_t)gridDim.x * NTHREADS)
+        yr[c] = w * yr[c] + (xr ? xr[c] : 0.f);
+}
+void vjp_seed(hipStream_t s, float* y, int64_t ldy, float w, const float* x, int64_t ldx, int rows, int64_t cols) {
+    if (rows <= 0 || cols <= 0) return;
+    unsigned bx = ew_blocks(cols);
+    const unsigned cap = (unsigned)std::max<int64_t>(1, 2048 / rows);     // ~2048 blocks in all
+    if (bx > cap) bx = cap;
+    hipLaunchKernelGGL(vjp_seed_kernel, dim3(bx, (unsigned)rows), dim3(NTHREADS), 0, s, y, ldy, w, x, ldx, cols);
+}
+
+// The tgt frames are also the recon terms' TARGET: d (c1 recon1 + c2 recon2) / d tgt = c1 (tgt - out) + c2 (tgt - out2), added to g
+__global__ __launch_bounds__(NTHREADS) void vjp_recon_tgt_kernel(float* __restrict__ g, const float* __restrict__ out, const float* __restrict__ out2,
+                                                                 const float* __restrict__ tgt, int64_t n, float c1, float c2) {
+    for (int64_t i = (int64_t)blockIdx.x * NTHREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * NTHREADS)
+        g[i] += c1 * (tgt[i] - out[i]) + c2 * (tgt[i] - out2[i]);
+}
+void vjp_recon_tgt(hipStream_t s, float* g, const float* out, const float* out2, const float* tgt, int64_t n, float c1, float c2) {
+    hipLaunchKernelGGL(vjp_recon_tgt_kernel, dim3(ew_blocks(n)), dim3(NTHREADS), 0, s, g, out, out2, tgt, n, c1, c2);
+}
+
 void lrelu_mask(hipStream_t s, float* g, const float* act, int64_t n) {
     hipLaunchKernelGGL(lrelu_mask_kernel, dim3(ew_blocks(n / 4)), dim3(NTHREADS), 0, s, g, act, n);
 }

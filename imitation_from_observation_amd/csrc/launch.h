@@ -182,6 +182,12 @@ void drop_factors(hipStream_t s, float* M, int rows, int ld, int gp, int gr, int
 void ew_mul(hipStream_t s, float* out, int ldo, const float* x, int ldx, const float* M, int ldm, int rows, int cols);
 void drop_fin(hipStream_t s, float* out, const float* raw, const float* M, const float* add1, const float* add2, const float* act, int64_t n);
 
+// y[r][c] = w * y[r][c] + x[r][c] (x nullable: 0) for r < rows, c < cols: the caller's cotangents on top of the losses' seeds
+void vjp_seed(hipStream_t s, float* y, int64_t ldy, float w, const float* x, int64_t ldx, int rows, int64_t cols);
+
+// g[i] += c1 (tgt[i] - out[i]) + c2 (tgt[i] - out2[i]): the recon terms' gradient w.r.t. their target frames
+void vjp_recon_tgt(hipStream_t s, float* g, const float* out, const float* out2, const float* tgt, int64_t n, float c1, float c2);
+
 // g *= (act >= 0 ? 1 : 0.2)
 void lrelu_mask(hipStream_t s, float* g, const float* act, int64_t n);
 

@@ -460,6 +460,30 @@ class Translator:
         self._ck(self._lib.ctx_dev_forward_backward(self._h, ctypes.c_void_p(d_src), ctypes.c_void_p(d_ctx),
                                                      ctypes.c_void_p(d_tgt), B, sim_batch))
 
+    def dev_forward_vjp(self, d_src, d_ctx, d_tgt, B, dropout=False, drop_step=-1):
+        """Training-mode forward (as dev_forward) whose activations are kept for ONE later dev_backward_vjp; returns its token.
+        dropout: apply the training graph's dropout masks (variant "real" with keep_prob < 1); drop_step: the mask hash's step,
+        -1 = the handle's Adam step count.  Asynchronous on the handle's stream."""
+        tok = ctypes.c_uint64()
+        self._ck(self._lib.ctx_dev_forward_vjp(self._h, ctypes.c_void_p(d_src), ctypes.c_void_p(d_ctx), ctypes.c_void_p(d_tgt), B,
+                                                int(bool(dropout)), int(drop_step), ctypes.byref(tok)))
+        return int(tok.value)
+
+    def dev_backward_vjp(self, token, d_out=None, d_out2=None, d_input_z=None, d_translated_z=None, loss_weight=1.0, sim_batch=0,
+                         d_src_frames=None, d_ctx_frames=None, d_tgt_frames=None):
+        """Backward of the forward `token` names, seeded with the caller's cotangents (integer device addresses, None = zero) plus
+        loss_weight x the gradient of the built-in `loss`.  Parameter gradients overwrite the gradient arena (dev grads); frame
+        gradients [B,H,W,C] go to the d_*_frames addresses given (None: not computed).  No Adam.  Raises CtxError (CTX_E_STATE)
+        when a later call overwrote the token's activations or its backward has already run."""
+        a = _lib.CtxVjpArgs(d_out, d_out2, d_input_z, d_translated_z, float(loss_weight), int(sim_batch), d_src_frames, d_ctx_frames,
+                            d_tgt_frames)
+        self._ck(self._lib.ctx_dev_backward_vjp(self._h, ctypes.c_uint64(token), ctypes.byref(a)))
+
+    def params_written(self):
+        """Tell the handle that parameters were changed through the device pointer (a torch optimiser, a copy_): packed filters
+        and captured inference graphs made from the old values are dropped."""
+        self._ck(self._lib.ctx_params_written(self._h))
+
     def dev_frames(self, B):
         """(d_src, d_ctx, d_tgt): integer device addresses of the handle's OWN frame slots for a batch of B.  A caller that writes its
         frames there and passes these addresses to dev_forward_backward / dev_train_step / dp_train_step saves the 3 B-frame copy."""

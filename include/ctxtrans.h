@@ -22,6 +22,9 @@
  *                         an RCCL gradient all-reduce between backward and Adam (new: the
  *                         reference has no multi-GPU path)
  *   ctx_dp_*              that all-reduce itself, on RCCL, behind this ABI (no torch needed)
+ *   ctx_dev_forward_vjp / ctx_dev_backward_vjp / ctx_params_written
+ *                         the translator as a differentiable function of its parameters and frames, for a
+ *                         caller's own loss or a torch.autograd graph (new: the reference has no equivalent)
  *
  * Conventions: every function returns 0 on success or a negative CTX_E_* code; the message is
  * available from ctx_last_error().  No C++ exception crosses the ABI.  Host buffers are caller
@@ -41,7 +44,8 @@ extern "C" {
 #endif
 
 #define CTX_ABI_VERSION 4   /* 2: ctx_config carries strides / kernels / filters / keep_prob / loss_mode; 3: per-handle options,
-                               ctx_dp_train_step_sampled / ctx_dp_eval_sampled, ctx_prof_entry.useful_frac; 4: ctx_dev_frames */
+                               ctx_dp_train_step_sampled / ctx_dp_eval_sampled, ctx_prof_entry.useful_frac; 4: ctx_dev_frames;
+                               still 4 (additions only): ctx_vjp_args, ctx_dev_forward_vjp, ctx_dev_backward_vjp, ctx_params_written */
 
 enum {
     CTX_OK = 0,
@@ -288,6 +292,39 @@ int ctx_dev_outputs(ctx_handle* h, const float** out, const float** out2, const 
  * losses; rows are de-padded (the device keeps them at a stride of featsize rounded up to 32 for CTX_VARIANT_REAL).
  * Either pointer may be NULL; *B (nullable) receives the batch of that forward. */
 int ctx_last_codes(ctx_handle* h, float* input_z, float* translated_z, int* B);
+
+/* ---- vector-Jacobian products: the translator under a caller's loss (new: the reference has no equivalent) ---------
+ * ctx_dev_forward_vjp runs the training-mode forward of ctx_dev_forward (frames, outputs and scalars alike) and keeps its
+ * activations for ONE later ctx_dev_backward_vjp, identified by *token.  dropout != 0 applies the training graph's dropout masks
+ * (CTX_VARIANT_REAL with keep_prob < 1; ignored otherwise); drop_step is the `t` of the mask hash (ctx_set_dropout_seed), -1 = the
+ * handle's Adam step count, i.e. the masks ctx_dev_forward_backward would draw.  Asynchronous on the handle's stream. */
+int ctx_dev_forward_vjp(ctx_handle* h, const float* d_src, const float* d_ctx, const float* d_tgt, int B, int dropout,
+                        int64_t drop_step, uint64_t* token);
+/* Cotangents of a VJP.  All pointers are DEVICE pointers and may be NULL: an input NULL means a zero cotangent, an output NULL
+ * skips that frame gradient's launches.  d_out / d_out2 and the frame gradients are [B,H,W,C]; d_input_z / d_translated_z are
+ * dense [B, featsize] (the library handles the padded row stride of CTX_VARIANT_REAL).  loss_weight is the cotangent of the
+ * scalar `loss` (the handle's loss_terms); sim_batch as in ctx_dev_forward_backward (0 = B). */
+typedef struct ctx_vjp_args {
+    const float* d_out;
+    const float* d_out2;
+    const float* d_input_z;
+    const float* d_translated_z;
+    float loss_weight;
+    int sim_batch;
+    float* d_src_frames;
+    float* d_ctx_frames;
+    float* d_tgt_frames;
+} ctx_vjp_args;
+/* The backward of the forward `token` names, seeded with  d out = loss_weight * d loss / d out + [d_out ; d_out2]  and
+ * d translated_z = loss_weight * d loss / d translated_z + d_translated_z  (d_input_z joins the gradient of input_z).  Parameter
+ * gradients OVERWRITE the gradient arena (ctx_dev_grads) as ctx_dev_forward_backward's do; frame gradients go to the caller's
+ * buffers.  No Adam, no bucket callback, no host synchronisation.  With loss_weight = 1 and no cotangents the gradient arena is
+ * bit-identical to ctx_dev_forward_backward's.  A token is good for ONE backward: any later forward or backward (this call
+ * included -- a second VJP on the same token, torch's retain_graph) overwrites the activations and returns CTX_E_STATE. */
+int ctx_dev_backward_vjp(ctx_handle* h, uint64_t token, const ctx_vjp_args* a);
+/* The caller has changed parameters through ctx_dev_params: packed filters of the direct kernels and captured inference graphs
+ * made from the old values are dropped (re-packed / re-captured at their next use).  Cheap: call it after every external update. */
+int ctx_params_written(ctx_handle* h);
 
 /* ---- data parallel over RCCL (new: the reference is single-device) ------------------------------
  * One process per GPU, each with a full replica + Adam state; per step: local forward/backward on the rank's shard with
