@@ -62,7 +62,7 @@ class CnnOp(ctypes.Structure):
                [(n, ctypes.c_int32) for n in ("src_ch0", "src_c", "nsplit", "dst2", "dst2_ch0", "reserved")]
 
 
-CTX_CNN_CONV, CTX_CNN_MAXPOOL, CTX_CNN_AVGPOOL = 0, 1, 2
+CTX_CNN_CONV, CTX_CNN_MAXPOOL, CTX_CNN_AVGPOOL, CTX_CNN_AVGPOOL_VALID, CTX_CNN_CONV_LINEAR = 0, 1, 2, 3, 4
 BUCKET_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64)
 
 SIGNATURES = {
@@ -144,6 +144,12 @@ SIGNATURES = {
     "ctx_cnn_profile": (_c.c_int, [_P, _c.c_int, _c.c_int, _F, _c.c_int]),
     "ctx_cnn_stream": (_P, [_P]),
     "ctx_cnn_sync": (_c.c_int, [_P]),
+    "ctx_cnn_stats_reset": (_c.c_int, [_P, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32), _c.c_int, _c.c_int]),
+    "ctx_cnn_stats_add_u8": (_c.c_int, [_P, _U8, _c.c_int, _c.c_int]),
+    "ctx_cnn_stats_finish": (_c.c_int, [_P, _c.c_int]),
+    "ctx_cnn_stats_read": (_c.c_int, [_P, _c.c_int, _F, _F, _c.POINTER(_c.c_int)]),
+    "ctx_cnn_reward_set_stats": (_c.c_int, [_P, _c.c_int, _F, _F, _c.c_int]),
+    "ctx_cnn_reward_costs": (_c.c_int, [_P, _U8, _c.c_int, _F]),
 }
 
 _lib = None

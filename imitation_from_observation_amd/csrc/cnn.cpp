@@ -7,6 +7,8 @@
 //            kernel, stride, SAME/VALID padding x NmPlain filter rows), epilogue bias + ReLU, written into a CHANNEL
 //            SLICE of the destination tensor -- tf.concat never copies.
 //   maxpool  3x3 stride 2 VALID;  avgpool  3x3 stride 1 SAME (mean over the taps inside the image).
+//   head     (nets/inception_v3.py:510-523, when the host builds it) avgpool_valid kh x kw stride s = PreLogits, and a linear conv
+//            (bias, no ReLU) = Logits.  The Inception-feature reward's statistics and costs (incep_reward.hip) read the buffers in place.
 // Activations are NHWC with the channel count rounded up to 32 (the 3-channel frames, the 80- and 48-wide tensors);
 // padded channels are zero because nothing ever writes them and the matching filter rows are zero.
 #include <hip/hip_runtime.h>
@@ -51,6 +53,12 @@ struct ctx_cnn {
     struct GraphSlot { int calls = 0; hipGraphExec_t exec = nullptr; };
     std::map<int, GraphSlot> graphs;                  // one captured pass per image count (run_cached)
     bool use_graphs = true;
+    // Inception-feature reward (ctx_cnn_stats_* / ctx_cnn_reward_*): per-slot accumulators, means and stds [F, h, w, c]
+    struct StatSlot { int buf = 0, c = 0; int64_t n = 0; float *acc = nullptr, *mean = nullptr, *std = nullptr; };
+    std::vector<StatSlot> stats;
+    int stats_frames = 0, stats_stage = -1, stats_count[2] = {0, 0};   // stage: 0 pass 0 open, 1 mean done / pass 1 open, 2 std done
+    float *r_mean = nullptr, *r_std = nullptr, *r_cost = nullptr;
+    int r_frames = 0, r_c = 0;
     std::string err;
 };
 
@@ -73,6 +81,8 @@ int cfail(ctx_cnn* h, int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return cfail(h, CTX_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_));   \
     } while (0)
 
+bool is_conv(int kind) { return kind == CTX_CNN_CONV || kind == CTX_CNN_CONV_LINEAR; }
+
 void out_dims(const ctx_cnn_buf& in, const ctx_cnn_op& op, int& ho, int& wo) {
     if (op.same) { ho = (in.h + op.stride - 1) / op.stride; wo = (in.w + op.stride - 1) / op.stride; }
     else { ho = (in.h - op.kh) / op.stride + 1; wo = (in.w - op.kw) / op.stride + 1; }
@@ -90,7 +100,7 @@ bool stem4_ok(const std::vector<ctx_cnn_buf>& bufs, const std::vector<ctx_cnn_op
     for (const ctx_cnn_op& op : ops) {
         if (op.dst == 0) return false;
         if (op.src != 0) continue;
-        if (op.kind != CTX_CNN_CONV || op.kh != op.kw || (op.kh != 3 && op.kh != 5)) return false;
+        if (!is_conv(op.kind) || op.kh != op.kw || (op.kh != 3 && op.kh != 5)) return false;
         if (op.same && same_before(bufs[0].h, op.kh, op.stride) != same_before(bufs[0].w, op.kw, op.stride)) return false;
         any = true;
     }
@@ -113,13 +123,17 @@ int validate(const std::vector<ctx_cnn_buf>& bufs, const std::vector<ctx_cnn_op>
         const ctx_cnn_buf &in = bufs[op.src], &out = bufs[op.dst];
         int ho, wo;
         ctx_cnn_op o = op;
-        if (op.kind != CTX_CNN_CONV) { o.kh = o.kw = 3; o.stride = op.kind == CTX_CNN_MAXPOOL ? 2 : 1; o.same = op.kind == CTX_CNN_AVGPOOL; }
+        if (op.kind == CTX_CNN_AVGPOOL_VALID) {
+            if (op.kh < 1 || op.kw < 1 || op.kh > in.h || op.kw > in.w || op.stride < 1)
+                return cfail(nullptr, CTX_E_INVALID, "op %zu: avgpool %dx%d stride %d on a %dx%d map", i, op.kh, op.kw, op.stride, in.h, in.w);
+            o.same = 0;
+        } else if (!is_conv(op.kind)) { o.kh = o.kw = 3; o.stride = op.kind == CTX_CNN_MAXPOOL ? 2 : 1; o.same = op.kind == CTX_CNN_AVGPOOL; }
         out_dims(in, o, ho, wo);
         if (ho != out.h || wo != out.w) return cfail(nullptr, CTX_E_INVALID, "op %zu: output grid %dx%d but buffer %d is %dx%d", i, ho, wo, op.dst, out.h, out.w);
-        const int cw = op.kind == CTX_CNN_CONV ? (op.nsplit ? op.nsplit : op.cout) : in.c;
+        const int cw = is_conv(op.kind) ? (op.nsplit ? op.nsplit : op.cout) : in.c;
         if (op.dst_ch0 < 0 || op.dst_ch0 % 4 || op.dst_ch0 + cw > out.c) return cfail(nullptr, CTX_E_INVALID, "op %zu: channel slice [%d,%d) outside buffer %d", i, op.dst_ch0, op.dst_ch0 + cw, op.dst);
-        if (op.kind != CTX_CNN_CONV && (op.src_c || op.nsplit)) return cfail(nullptr, CTX_E_INVALID, "op %zu: channel slices / merged outputs are conv-only", i);
-        if (op.kind == CTX_CNN_CONV) {
+        if (!is_conv(op.kind) && (op.src_c || op.nsplit)) return cfail(nullptr, CTX_E_INVALID, "op %zu: channel slices / merged outputs are conv-only", i);
+        if (is_conv(op.kind)) {
             if (op.kh < 1 || op.kw < 1 || op.kh * op.kw > 25 || op.cout <= 0 || op.cout % 4 || (op.stride != 1 && op.stride != 2))
                 return cfail(nullptr, CTX_E_INVALID, "op %zu: unsupported conv %dx%d stride %d cout %d", i, op.kh, op.kw, op.stride, op.cout);
             if (op.src_c && (op.src_c % 32 || op.src_ch0 % 32 || op.src_ch0 < 0 || op.src_ch0 + op.src_c > in.c || op.src == 0))
@@ -134,7 +148,7 @@ int validate(const std::vector<ctx_cnn_buf>& bufs, const std::vector<ctx_cnn_op>
             const int64_t nw = (int64_t)op.kh * op.kw * (op.src_c ? op.src_c : in.c) * op.cout;
             if (op.w_off < 0 || op.w_off % 4 || op.w_off + nw > weight_floats || op.b_off < 0 || op.b_off + op.cout > weight_floats)
                 return cfail(nullptr, CTX_E_INVALID, "op %zu: weights outside the blob", i);
-        } else if (op.kind != CTX_CNN_MAXPOOL && op.kind != CTX_CNN_AVGPOOL) return cfail(nullptr, CTX_E_INVALID, "op %zu: unknown kind %d", i, op.kind);
+        } else if (op.kind != CTX_CNN_MAXPOOL && op.kind != CTX_CNN_AVGPOOL && op.kind != CTX_CNN_AVGPOOL_VALID) return cfail(nullptr, CTX_E_INVALID, "op %zu: unknown kind %d", i, op.kind);
     }
     return CTX_OK;
 }
@@ -158,16 +172,17 @@ int run(ctx_cnn* h, int n, std::vector<hipEvent_t>* ev = nullptr) {
         if (par) for (int j : h->deps[oi]) (void)hipStreamWaitEvent(st, h->done[j], 0);
         const SplitWs ws{h->slab[L], h->slab_floats, h->precision};
         const ctx_cnn_buf &in = h->bufs[op.src], &out = h->bufs[op.dst];
-        const float* x = h->dbuf[op.src] + (op.kind == CTX_CNN_CONV ? op.src_ch0 : 0);
-        const int cin = op.kind == CTX_CNN_CONV && op.src_c ? op.src_c : in.c;      // channels the conv reads (row stride stays in.c)
+        const float* x = h->dbuf[op.src] + (is_conv(op.kind) ? op.src_ch0 : 0);
+        const int cin = is_conv(op.kind) && op.src_c ? op.src_c : in.c;      // channels the conv reads (row stride stays in.c)
         float* y = h->dbuf[op.dst] + op.dst_ch0;
         if (op.kind == CTX_CNN_MAXPOOL) maxpool3x3s2(st, x, y, n, in.h, in.w, in.c, out.c);
         else if (op.kind == CTX_CNN_AVGPOOL) avgpool3x3s1(st, x, y, n, in.h, in.w, in.c, out.c);
+        else if (op.kind == CTX_CNN_AVGPOOL_VALID) avgpool_valid(st, x, y, n, in.h, in.w, in.c, op.kh, op.kw, op.stride, out.c);
         else {
             const int R = n * out.h * out.w;
             const float* w = h->weights + op.w_off;
             Epi ep;
-            ep.out1 = y; ep.ld1 = out.c; ep.bias = h->weights + op.b_off; ep.lrelu = 2;
+            ep.out1 = y; ep.ld1 = out.c; ep.bias = h->weights + op.b_off; ep.lrelu = op.kind == CTX_CNN_CONV_LINEAR ? 0 : 2;
             if (op.nsplit) { ep.nsplit = op.nsplit; ep.out2 = h->dbuf[op.dst2] + op.dst2_ch0; ep.ld2 = h->bufs[op.dst2].c; }
             const int pady = op.same ? same_before(in.h, op.kh, op.stride) : 0, padx = op.same ? same_before(in.w, op.kw, op.stride) : 0;
             if (op.src == 0 && h->stem4) {
@@ -230,6 +245,28 @@ int run_cached(ctx_cnn* h, int n) {
     }
     if (hipGraphLaunch(g.exec, h->lane[0]) != hipSuccess) return cfail(h, CTX_E_DEVICE, "hipGraphLaunch failed");
     return CTX_OK;
+}
+
+void free_stats(ctx_cnn* h) {
+    for (ctx_cnn::StatSlot& sl : h->stats)
+        for (float* p : {sl.acc, sl.mean, sl.std}) if (p) (void)hipFree(p);
+    h->stats.clear();
+    h->stats_stage = -1;
+}
+
+void free_reward(ctx_cnn* h) {
+    for (float* p : {h->r_mean, h->r_std, h->r_cost}) if (p) (void)hipFree(p);
+    h->r_mean = h->r_std = h->r_cost = nullptr;
+    h->r_frames = h->r_c = 0;
+}
+
+// Uploads m frames and runs one pass (the staging buffer is reused by the next chunk: callers sync before it)
+int forward_chunk(ctx_cnn* h, const uint8_t* frames, int m) {
+    const ctx_cnn_buf& b0 = h->bufs.front();
+    const int64_t pix_in = (int64_t)b0.h * b0.w;
+    CNN_HIP(h, hipMemcpyAsync(h->u8, frames, (size_t)m * pix_in * 3, hipMemcpyHostToDevice, h->stream));
+    pad_channels_u8(h->stream, h->u8, h->dbuf[0], m * pix_in, h->stem4 ? 4 : b0.c);
+    return run_cached(h, m);
 }
 }  // namespace
 
@@ -302,6 +339,8 @@ void ctx_cnn_destroy(ctx_cnn* h) {
         if (h->wpack[l]) (void)hipFree(h->wpack[l]);
         if (l && h->lane[l]) { (void)hipStreamSynchronize(h->lane[l]); (void)hipStreamDestroy(h->lane[l]); }
     }
+    free_stats(h);
+    free_reward(h);
     for (auto& kv : h->graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
     for (hipEvent_t e : h->done) if (e) (void)hipEventDestroy(e);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -404,6 +443,129 @@ int ctx_cnn_profile(ctx_cnn* h, int n, int iters, float* ms, int max_ops) {
     for (size_t i = 0; i < h->ops.size(); ++i) ms[i] = (float)(acc[i] / iters);
     for (auto& e : ev) (void)hipEventDestroy(e);
     return rc;
+}
+
+// ---- Inception-feature baseline reward (include/ctxtrans.h: ctx_cnn_stats_* / ctx_cnn_reward_*)
+int ctx_cnn_stats_reset(ctx_cnn* h, const int32_t* buffers, const int32_t* channels, int nslots, int nframes) {
+    if (!h) return CTX_E_INVALID;
+    if (!buffers || !channels || nslots <= 0 || nframes <= 0 || nframes > h->max_images)
+        return cfail(h, CTX_E_INVALID, "stats_reset: need nslots >= 1 and 1 <= nframes <= max_images (%d)", h->max_images);
+    for (int i = 0; i < nslots; ++i) {
+        const int b = buffers[i];
+        if (b <= 0 || b >= (int)h->bufs.size()) return cfail(h, CTX_E_INVALID, "stats_reset: slot %d: buffer %d is not an activation buffer", i, b);
+        if (channels[i] <= h->bufs[b].c - 32 || channels[i] > h->bufs[b].c)
+            return cfail(h, CTX_E_INVALID, "stats_reset: slot %d: %d real channels in a %d-wide buffer", i, channels[i], h->bufs[b].c);
+    }
+    CNN_HIP(h, hipSetDevice(h->device));
+    CNN_HIP(h, hipStreamSynchronize(h->stream));
+    free_stats(h);
+    bool ok = true;
+    for (int i = 0; i < nslots && ok; ++i) {
+        ctx_cnn::StatSlot sl;
+        sl.buf = buffers[i]; sl.c = channels[i];
+        sl.n = (int64_t)nframes * h->bufs[sl.buf].h * h->bufs[sl.buf].w * sl.c;
+        for (float** p : {&sl.acc, &sl.mean, &sl.std})
+            ok = ok && hipMalloc((void**)p, (size_t)sl.n * sizeof(float)) == hipSuccess && hipMemset(*p, 0, (size_t)sl.n * sizeof(float)) == hipSuccess;
+        h->stats.push_back(sl);
+    }
+    if (!ok) { free_stats(h); return cfail(h, CTX_E_NOMEM, "stats_reset: device allocation failed"); }
+    h->stats_frames = nframes;
+    h->stats_stage = 0;
+    h->stats_count[0] = h->stats_count[1] = 0;
+    return CTX_OK;
+}
+
+int ctx_cnn_stats_add_u8(ctx_cnn* h, const uint8_t* frames, int nvideos, int pass) {
+    if (!h) return CTX_E_INVALID;
+    if (!frames || nvideos <= 0 || (pass != 0 && pass != 1)) return cfail(h, CTX_E_INVALID, "stats_add_u8: bad arguments");
+    if (h->stats_stage != pass) return cfail(h, CTX_E_STATE, "stats_add_u8: pass %d is not open (reset, then pass 0, finish(0), pass 1, finish(1))", pass);
+    CNN_HIP(h, hipSetDevice(h->device));
+    const int F = h->stats_frames, per = h->max_images / F;
+    const int64_t fbytes = (int64_t)F * h->bufs.front().h * h->bufs.front().w * 3;
+    for (int v0 = 0; v0 < nvideos; v0 += per) {
+        const int nv = nvideos - v0 < per ? nvideos - v0 : per;
+        int rc = forward_chunk(h, frames + v0 * fbytes, nv * F);
+        if (rc != CTX_OK) return rc;
+        for (ctx_cnn::StatSlot& sl : h->stats) {
+            const ctx_cnn_buf& b = h->bufs[sl.buf];
+            incep_stats_accum(h->stream, h->dbuf[sl.buf], F, (int64_t)b.h * b.w, sl.c, b.c, nv, pass, sl.mean, sl.acc);
+        }
+        if (hipGetLastError() != hipSuccess) return cfail(h, CTX_E_DEVICE, "stats kernel launch failed");
+        CNN_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    h->stats_count[pass] += nvideos;
+    return CTX_OK;
+}
+
+int ctx_cnn_stats_finish(ctx_cnn* h, int pass) {
+    if (!h) return CTX_E_INVALID;
+    if (pass != 0 && pass != 1) return cfail(h, CTX_E_INVALID, "stats_finish: pass must be 0 or 1");
+    if (h->stats_stage != pass || h->stats_count[pass] <= 0) return cfail(h, CTX_E_STATE, "stats_finish(%d): that pass is not open or saw no video", pass);
+    if (pass == 1 && h->stats_count[1] != h->stats_count[0])
+        return cfail(h, CTX_E_STATE, "stats_finish(1): pass 1 saw %d videos, pass 0 %d", h->stats_count[1], h->stats_count[0]);
+    CNN_HIP(h, hipSetDevice(h->device));
+    for (ctx_cnn::StatSlot& sl : h->stats) {
+        incep_stats_finish(h->stream, sl.acc, sl.n, h->stats_count[pass], pass, pass ? sl.std : sl.mean);
+        if (!pass) CNN_HIP(h, hipMemsetAsync(sl.acc, 0, (size_t)sl.n * sizeof(float), h->stream));
+    }
+    if (hipGetLastError() != hipSuccess) return cfail(h, CTX_E_DEVICE, "stats kernel launch failed");
+    CNN_HIP(h, hipStreamSynchronize(h->stream));
+    h->stats_stage = pass + 1;
+    return CTX_OK;
+}
+
+int ctx_cnn_stats_read(ctx_cnn* h, int slot, float* means, float* stds, int* count) {
+    if (!h) return CTX_E_INVALID;
+    if (slot < 0 || slot >= (int)h->stats.size()) return cfail(h, CTX_E_INVALID, "stats_read: slot %d of %zu", slot, h->stats.size());
+    if (h->stats_stage < 1 || (stds && h->stats_stage < 2)) return cfail(h, CTX_E_STATE, "stats_read: the %s not finished", stds ? "stds are" : "means are");
+    const ctx_cnn::StatSlot& sl = h->stats[slot];
+    CNN_HIP(h, hipSetDevice(h->device));
+    if (means) CNN_HIP(h, hipMemcpyAsync(means, sl.mean, (size_t)sl.n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (stds) CNN_HIP(h, hipMemcpyAsync(stds, sl.std, (size_t)sl.n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    CNN_HIP(h, hipStreamSynchronize(h->stream));
+    if (count) *count = h->stats_count[0];
+    return CTX_OK;
+}
+
+int ctx_cnn_reward_set_stats(ctx_cnn* h, int channels, const float* means, const float* stds, int nframes) {
+    if (!h) return CTX_E_INVALID;
+    const ctx_cnn_buf& b = h->bufs.back();
+    if (!means || !stds || nframes <= 0 || nframes > h->max_images || channels <= b.c - 32 || channels > b.c)
+        return cfail(h, CTX_E_INVALID, "reward_set_stats: need 1 <= nframes <= max_images (%d) and the output's real channel count (%d-wide buffer)",
+                     h->max_images, b.c);
+    CNN_HIP(h, hipSetDevice(h->device));
+    CNN_HIP(h, hipStreamSynchronize(h->stream));
+    free_reward(h);
+    const size_t n = (size_t)nframes * b.h * b.w * channels;
+    bool ok = hipMalloc((void**)&h->r_mean, n * sizeof(float)) == hipSuccess && hipMalloc((void**)&h->r_std, n * sizeof(float)) == hipSuccess &&
+              hipMalloc((void**)&h->r_cost, (size_t)h->max_images * sizeof(float)) == hipSuccess;
+    if (!ok) { free_reward(h); return cfail(h, CTX_E_NOMEM, "reward_set_stats: device allocation failed"); }
+    CNN_HIP(h, hipMemcpyAsync(h->r_mean, means, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    CNN_HIP(h, hipMemcpyAsync(h->r_std, stds, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    CNN_HIP(h, hipStreamSynchronize(h->stream));
+    h->r_frames = nframes;
+    h->r_c = channels;
+    return CTX_OK;
+}
+
+int ctx_cnn_reward_costs(ctx_cnn* h, const uint8_t* frames, int npaths, float* costs) {
+    if (!h) return CTX_E_INVALID;
+    if (!frames || !costs || npaths <= 0) return cfail(h, CTX_E_INVALID, "reward_costs: bad arguments");
+    if (!h->r_mean) return cfail(h, CTX_E_STATE, "reward_costs: no statistics (ctx_cnn_reward_set_stats first)");
+    CNN_HIP(h, hipSetDevice(h->device));
+    const ctx_cnn_buf& b = h->bufs.back();
+    const int F = h->r_frames, per = h->max_images / F;
+    const int64_t fbytes = (int64_t)F * h->bufs.front().h * h->bufs.front().w * 3;
+    for (int p0 = 0; p0 < npaths; p0 += per) {
+        const int np = npaths - p0 < per ? npaths - p0 : per;
+        int rc = forward_chunk(h, frames + p0 * fbytes, np * F);
+        if (rc != CTX_OK) return rc;
+        incep_costs(h->stream, h->dbuf.back(), np * F, F, (int64_t)b.h * b.w, h->r_c, b.c, h->r_mean, h->r_std, h->r_cost);
+        if (hipGetLastError() != hipSuccess) return cfail(h, CTX_E_DEVICE, "cost kernel launch failed");
+        CNN_HIP(h, hipMemcpyAsync(costs + (int64_t)p0 * F, h->r_cost, (size_t)np * F * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        CNN_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    return CTX_OK;
 }
 
 void* ctx_cnn_stream(ctx_cnn* h) { return h ? (void*)h->stream : nullptr; }

@@ -152,6 +152,15 @@ void pad_channels_f32(hipStream_t s, const float* in, float* out, int64_t npix, 
 void maxpool3x3s2(hipStream_t s, const float* in, float* out, int nimg, int hi, int wi, int c, int ldo);
 void avgpool3x3s1(hipStream_t s, const float* in, float* out, int nimg, int hi, int wi, int c, int ldo);
 
+// Inception head and feature reward (incep_reward.hip): kh x kw stride-s VALID average pool (PreLogits); per-timestep statistics over
+// videos of F frames read from a [nvid*F, hw, cpad] buffer (c real channels) into [F, hw, c] (pass 0: acc += x, pass 1:
+// acc += (x - mean)^2; finish: acc / count, pass 1 sqrt of it); per-frame cost mean((means - x)^2 / (std + 1e-5)) with std == 0 dropped
+void avgpool_valid(hipStream_t s, const float* in, float* out, int nimg, int hi, int wi, int c, int kh, int kw, int stride, int ldo);
+void incep_stats_accum(hipStream_t s, const float* feat, int F, int64_t hw, int c, int cpad, int nvid, int pass, const float* mean, float* acc);
+void incep_stats_finish(hipStream_t s, const float* acc, int64_t n, int count, int pass, float* out);
+void incep_costs(hipStream_t s, const float* feat, int nframes, int F, int64_t hw, int c, int cpad, const float* means, const float* stds,
+                 float* costs);
+
 // device batch sampler (scripts/train_script.py:153-159); lut[256] = f32(x / 127.5 - 1)
 void gather_triples(hipStream_t s, const uint8_t* vdata, int T, int N, int64_t npi, const int* csrc, const int* ctgt, int B, int b0,
                     const float* lut, float* img);

@@ -10,6 +10,11 @@ Layer table: nets/inception_v3.py:93-416 at depth_multiplier 1 (the only way the
 follow the reference's scopes, including the three irregular ones (Mixed_5c/Branch_1 'Conv2d_0b_1x1' and
 'Conv_1_0c_5x5', :170-173; the 3x3 stride-2 convs named '..._1a_1x1' in Mixed_6a, :218-227), so a TF checkpoint
 converted to .npz loads by name.
+
+`final` cuts the op list at any end point (the last buffer is then that end point's); 'PreLogits' and 'Logits' append the
+classifier head of nets/inception_v3.py:510-523 -- avg_pool2d over min(map, 8) per axis, VALID, slim's default stride 2, then
+the linear 1x1 Conv2d_1c_1x1 (bias, no batch norm, no ReLU) to 1001 classes, spatially squeezed -- which the reference's
+sampler prints ImageNet classes with (rllab/sampler/base.py:87-89) and the Inception-feature baseline reads 'PreLogits' of.
 """
 from __future__ import annotations
 
@@ -74,6 +79,10 @@ BLOCKS = OrderedDict([
                   [("max",)]]),
     ("Mixed_7b", _block8("Conv2d_0b_3x1")), ("Mixed_7c", _block8("Conv2d_0c_3x1")),
 ])
+HEAD = ("PreLogits", "Logits")
+ENDPOINTS = [n for n, _ in STEM] + list(BLOCKS) + list(HEAD)
+NUM_CLASSES = 1001                  # inception_v3(images, num_classes=1001): ImageNet + background
+LOGITS_SCOPE = "InceptionV3/Logits/Conv2d_1c_1x1"
 
 
 def _pad32(c):
@@ -89,19 +98,48 @@ class _Layout:
     buffer, the others in channel slots of one temporary buffer that the branches' next convolutions read as slices.  The
     variables keep their names, shapes and creation order; only their place in the weight blob changes (conv['ld'], ['col0'])."""
 
-    def __init__(self, H, W, merge_heads=True):
+    def __init__(self, H, W, merge_heads=True, final="Mixed_7c"):
+        if final not in ENDPOINTS:
+            raise ValueError(f"final must be one of {ENDPOINTS}, got {final!r}")
         self.merge_heads = merge_heads
         self.bufs, self.ops, self.convs, self.endpoints = [], [], [], OrderedDict()
         self.woff = 0
         self.lane = 0                   # branch index inside a block: independent branches may overlap on the device
-        x = self.new_buf(H, W, 3)
+        self.out = x = self.new_buf(H, W, 3)
         for name, step in STEM:
             x = self.apply(x, step, "InceptionV3/")
-            self.endpoints[name] = x
+            self.endpoints[name] = self.out = x
+            if name == final:
+                return
         for name, branches in BLOCKS.items():
             x = self.block(x, branches, f"InceptionV3/{name}/")
-            self.endpoints[name] = x
-        self.out = x
+            self.endpoints[name] = self.out = x
+            if name == final:
+                return
+        self.head(x, final)
+
+    def head(self, x, final):
+        """nets/inception_v3.py:510-523.  PreLogits = avg_pool2d(net, k, padding='VALID') with k = min(map, 8) per axis and slim's
+        default stride 2 (the head is outside the stride-1 arg_scope of the aux head); Logits = a linear 1x1 conv, 1001 columns padded
+        to 1024 (zero filter columns and bias), squeezed -- defined only where PreLogits is 1x1 (TF's squeeze would fail otherwise)."""
+        k = (min(x[1], 8), min(x[2], 8))
+        h, w = self.out_grid(x, k, 2, V)
+        pre = self.new_buf(h, w, x[3])
+        self.ops.append(dict(kind=_lib.CTX_CNN_AVGPOOL_VALID, src=x[0], dst=pre[0], dst_ch0=0, kh=k[0], kw=k[1], stride=2, same=0, cout=0,
+                             w_off=0, b_off=0, lane=0))
+        self.endpoints["PreLogits"] = self.out = pre
+        if final == "PreLogits":
+            return
+        if (h, w) != (1, 1):
+            raise ValueError(f"Logits needs a 1x1 PreLogits (TF squeezes it); this input size gives {h}x{w}")
+        cout = _pad32(NUM_CLASSES)
+        nw = x[3] * cout
+        self.ops.append(dict(kind=_lib.CTX_CNN_CONV_LINEAR, src=pre[0], dst=self.new_buf(1, 1, NUM_CLASSES)[0], dst_ch0=0, kh=1, kw=1, stride=1,
+                             same=1, cout=cout, w_off=self.woff, b_off=self.woff + nw, lane=0))
+        self.convs.append(dict(scope=LOGITS_SCOPE, k=(1, 1), cin=x[3], cin_pad=x[3], cout=NUM_CLASSES, cout_pad=cout, w_off=self.woff,
+                               b_off=self.woff + nw, grid=(1, 1), linear=True))
+        self.woff += nw + cout
+        self.endpoints["Logits"] = self.out = (self.ops[-1]["dst"], 1, 1, NUM_CLASSES)
 
     def new_buf(self, h, w, c):
         self.bufs.append((h, w, _pad32(c)))
@@ -221,15 +259,17 @@ class _Layout:
 
 
 class InceptionFrontend:
-    """frames -> Mixed_7c feature maps on one MI355X.  `max_images` bounds one device pass (larger batches are chunked)."""
+    """frames -> Mixed_7c feature maps on one MI355X.  `max_images` bounds one device pass (larger batches are chunked).
+    final: the last end point computed (ENDPOINTS; 'PreLogits' / 'Logits' append the classifier head)."""
 
-    def __init__(self, H=125, W=125, max_images=75, device=0, precision="f32", stream=None, merge_heads=None):
+    def __init__(self, H=125, W=125, max_images=75, device=0, precision="f32", stream=None, merge_heads=None, final="Mixed_7c"):
         self._lib = _lib.load()
         self.H, self.W = H, W
         if merge_heads is None:
             import os
             merge_heads = os.environ.get("CTX_CNN_MERGE", "1") != "0"
-        lay = _Layout(H, W, merge_heads)
+        lay = _Layout(H, W, merge_heads, final)
+        self.final = final
         # the output buffer must be the last one for the C side: re-number so that it is
         order = [i for i in range(len(lay.bufs)) if i != lay.out[0]] + [lay.out[0]]
         remap = {old: new for new, old in enumerate(order)}
@@ -237,7 +277,7 @@ class InceptionFrontend:
         self._ops = [dict(op, src=remap[op["src"]], dst=remap[op["dst"]], dst2=remap[op["dst2"]] if op.get("nsplit") else 0) for op in lay.ops]
         self.convs, self.weight_floats = lay.convs, lay.woff
         self.endpoints = OrderedDict((k, (remap[v[0]],) + v[1:]) for k, v in lay.endpoints.items())
-        self.out_shape = lay.out[1:]                       # (h, w, 2048)
+        self.out_shape = lay.out[1:]                       # (h, w, 2048) at the default `final`; real channels
         self.max_images = max_images
         bufs = (CnnBuf * len(self._bufs))(*[CnnBuf(*b) for b in self._bufs])
         ops = (CnnOp * len(self._ops))(*[CnnOp(o["kind"], o["src"], o["dst"], o["dst_ch0"], o["kh"], o["kw"], o["stride"], o["same"], o["cout"], o["lane"],
@@ -251,6 +291,12 @@ class InceptionFrontend:
             msg = self._lib.ctx_cnn_last_error(None)
             self._h = ctypes.c_void_p()
             raise CtxError(rc, msg.decode() if msg else "")
+
+    @staticmethod
+    def max_images_limit(H, W, final="Mixed_7c"):
+        """The largest max_images ctx_cnn_create accepts at this input size: every activation buffer stays under 2 GiB
+        (187 at 299 x 299, whose 32-wide frame buffer is the largest)."""
+        return min(((1 << 31) - 1) // (h * w * c * 4) for h, w, c in _Layout(H, W, final=final).bufs)
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
@@ -281,14 +327,27 @@ class InceptionFrontend:
         out = []
         for c in self.convs:
             out += [(c["scope"] + "/weights", c["k"] + (c["cin"], c["cout"]))]
+            if c.get("linear"):                               # the head's Conv2d_1c_1x1: biases, no batch norm
+                out += [(c["scope"] + "/biases", (c["cout"],))]
+                continue
             out += [(c["scope"] + "/BatchNorm/" + n, (c["cout"],)) for n in ("beta", "moving_mean", "moving_variance")]
         return out
 
     def set_variables(self, tree):
-        """tree: {tf_variable_name: array}.  Folds the batch norm (inference form) into filter and bias and uploads."""
+        """tree: {tf_variable_name: array}.  Folds the batch norm (inference form) into filter and bias and uploads.  Keys of parts
+        not built (AuxLogits/*, and Logits/* below `final` = 'Logits') are ignored."""
         blob = np.zeros(self.weight_floats, np.float32)
         for c in self.convs:
             w = np.asarray(tree[c["scope"] + "/weights"], np.float64)
+            if c.get("linear"):
+                b = np.asarray(tree[c["scope"] + "/biases"], np.float64)
+                if w.shape != c["k"] + (c["cin"], c["cout"]) or b.shape != (c["cout"],):
+                    raise ValueError(f"{c['scope']}: expected weights {c['k'] + (c['cin'], c['cout'])} and biases {(c['cout'],)}, got {w.shape}, {b.shape}")
+                wp = np.zeros((c["cin_pad"], c["cout_pad"]))
+                wp[:c["cin"], :c["cout"]] = w[0, 0]
+                blob[c["w_off"]:c["w_off"] + wp.size] = wp.reshape(-1)
+                blob[c["b_off"]:c["b_off"] + c["cout"]] = b
+                continue
             beta, mean, var = (np.asarray(tree[c["scope"] + "/BatchNorm/" + n], np.float64) for n in ("beta", "moving_mean", "moving_variance"))
             if w.shape != c["k"] + (c["cin"], c["cout"]):
                 raise ValueError(f"{c['scope']}/weights: expected {c['k'] + (c['cin'], c['cout'])}, got {w.shape}")
@@ -324,15 +383,36 @@ class InceptionFrontend:
         return tree
 
     # ------------------------------------------------------------------ the fetch
-    def features(self, frames_u8):
-        """uint8 frames [n,H,W,3] -> Mixed_7c [n,h,w,2048] (host arrays; PCIe both ways)."""
+    def _check_frames(self, frames_u8):
         fr = np.ascontiguousarray(frames_u8)
         if fr.dtype != np.uint8 or fr.ndim != 4 or fr.shape[1:] != (self.H, self.W, 3):
             raise ValueError(f"frames must be uint8 [n,{self.H},{self.W},3], got {fr.dtype} {fr.shape}")
-        out = np.empty((fr.shape[0],) + tuple(self.out_shape), np.float32)
+        return fr
+
+    def _real(self, out):
+        """The output buffer is channel-padded where the end point's width is not a multiple of 32 (Conv2d_3b_1x1, Logits)."""
+        c = self.out_shape[2]
+        return out if out.shape[-1] == c else np.ascontiguousarray(out[..., :c])
+
+    def features(self, frames_u8):
+        """uint8 frames [n,H,W,3] -> the `final` end point, Mixed_7c [n,h,w,2048] by default (host arrays; PCIe both ways)."""
+        fr = self._check_frames(frames_u8)
+        out = np.empty((fr.shape[0],) + tuple(self._bufs[-1]), np.float32)
         self._ck(self._lib.ctx_cnn_forward_u8(self._h, fr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), fr.shape[0],
                                               out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
-        return out
+        return self._real(out)
+
+    def logits(self, frames_u8):
+        """uint8 frames [n,H,W,3] -> Logits [n,1001] (final='Logits'; the reference's check that a checkpoint loaded, base.py:87-89)."""
+        if self.final != "Logits":
+            raise ValueError("logits() needs a front end built with final='Logits'")
+        return self.features(frames_u8).reshape(-1, NUM_CLASSES)
+
+    def predictions(self, frames_u8):
+        """softmax(Logits) [n,1001] on the host (end_points['Predictions'], nets/inception_v3.py:523)."""
+        z = self.logits(frames_u8).astype(np.float64)
+        z = np.exp(z - z.max(axis=1, keepdims=True))
+        return (z / z.sum(axis=1, keepdims=True)).astype(np.float32)
 
     def flops_per_image(self):
         """Algorithmic FLOPs of one image's pass (2 per multiply-add, real channel counts)."""
@@ -341,9 +421,7 @@ class InceptionFrontend:
     def features_u8_dev(self, frames_u8):
         """uint8 frames [n,H,W,3] (n <= max_images) -> integer DEVICE address of Mixed_7c [n,h,w,2048].  Asynchronous on the handle's
         stream; the frames array is kept alive by this object until the next call / sync."""
-        fr = np.ascontiguousarray(frames_u8)
-        if fr.dtype != np.uint8 or fr.ndim != 4 or fr.shape[1:] != (self.H, self.W, 3):
-            raise ValueError(f"frames must be uint8 [n,{self.H},{self.W},3], got {fr.dtype} {fr.shape}")
+        fr = self._check_frames(frames_u8)
         self._pending = fr                                    # the upload reads it in stream order
         d_out = ctypes.c_void_p()
         self._ck(self._lib.ctx_cnn_forward_u8_dev(self._h, fr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), fr.shape[0], ctypes.byref(d_out)))
@@ -351,9 +429,9 @@ class InceptionFrontend:
 
     def output(self, n):
         """Host copy of the last forward's Mixed_7c maps [n,h,w,2048] (synchronises)."""
-        out = np.empty((n,) + tuple(self.out_shape), np.float32)
+        out = np.empty((n,) + tuple(self._bufs[-1]), np.float32)
         self._ck(self._lib.ctx_cnn_read_buffer(self._h, len(self._bufs) - 1, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
-        return out
+        return self._real(out)
 
     def features_dev(self, d_frames_f32, n):
         """Device f32 frames [n,H,W,3] in [-1,1] (integer address) -> integer device address of [n,h,w,2048].  Asynchronous."""
@@ -378,7 +456,12 @@ class InceptionFrontend:
         out = []
         for o, t in zip(self._ops, ms):
             h, w, _ = self._bufs[o["dst"]]
-            if o["kind"] == _lib.CTX_CNN_CONV and o.get("nconvs", 1) > 1:                     # merged 1x1 heads of a block
+            if o["kind"] == _lib.CTX_CNN_CONV_LINEAR:
+                c = next(convs)
+                out.append((c["scope"], f"1x1 linear {c['cin']}->{c['cout']}", (h, w), float(t), 2.0 * n * c["cin"] * c["cout"]))
+            elif o["kind"] == _lib.CTX_CNN_AVGPOOL_VALID:
+                out.append(("avgpool", f"{o['kh']}x{o['kw']} s{o['stride']} VALID", (h, w), float(t), 0.0))
+            elif o["kind"] == _lib.CTX_CNN_CONV and o.get("nconvs", 1) > 1:                     # merged 1x1 heads of a block
                 cs = [by_scope[sc] for sc in o["scopes"]]
                 flops = sum(2.0 * n * h * w * c["cin"] * c["cout"] for c in cs)
                 out.append((cs[0]["scope"].rsplit("/", 2)[0] + "/{1x1 heads}", f"1x1 s1 SAME {cs[0]['cin']}->" + "+".join(str(c["cout"]) for c in cs),
@@ -390,6 +473,63 @@ class InceptionFrontend:
             else:
                 out.append(("maxpool" if o["kind"] == _lib.CTX_CNN_MAXPOOL else "avgpool", "3x3", (h, w), float(t), 0.0))
         return out
+
+    # ------------------------------------------------------------------ Inception-feature reward (ctx_cnn_stats_* / ctx_cnn_reward_*)
+    def stats(self, videos, layers, nframes=None):
+        """Per-timestep means and stds of end points over videos, computed on the device: {layer: (means, stds)}, each
+        [nframes, h, w, c] f32, equal to numpy's float32  np.mean / np.std(axis=0)  over the videos' features bit for bit.
+        videos: iterable of uint8 [nframes, H, W, 3] (lists of frames are stacked); two passes over it, one forward per video each,
+        max_images // nframes videos per device pass.  layers: end points at or before `final`."""
+        videos = [self._check_frames(np.stack(v) if isinstance(v, (list, tuple)) else v) for v in videos]
+        if not videos:
+            raise ValueError("no videos")
+        F = videos[0].shape[0] if nframes is None else int(nframes)
+        if any(v.shape[0] != F for v in videos):
+            raise ValueError(f"every video must hold {F} frames")
+        layers = list(layers)
+        for name in layers:
+            if name not in self.endpoints:
+                raise ValueError(f"end point {name!r} is not computed by this front end (final={self.final!r})")
+        bufs = (ctypes.c_int32 * len(layers))(*[self.endpoints[n][0] for n in layers])
+        chans = (ctypes.c_int32 * len(layers))(*[self.endpoints[n][3] for n in layers])
+        self._ck(self._lib.ctx_cnn_stats_reset(self._h, bufs, chans, len(layers), F))
+        per = max(1, self.max_images // F)
+        for pas in (0, 1):
+            for i0 in range(0, len(videos), per):
+                fr = np.ascontiguousarray(np.concatenate(videos[i0:i0 + per]))
+                self._ck(self._lib.ctx_cnn_stats_add_u8(self._h, fr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), len(videos[i0:i0 + per]), pas))
+            self._ck(self._lib.ctx_cnn_stats_finish(self._h, pas))
+        out = OrderedDict()
+        for i, name in enumerate(layers):
+            _, h, w, c = self.endpoints[name]
+            m, sd = np.empty((F, h, w, c), np.float32), np.empty((F, h, w, c), np.float32)
+            self._ck(self._lib.ctx_cnn_stats_read(self._h, i, m.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                                  sd.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), None))
+            out[name] = (m, sd)
+        return out
+
+    def reward_set_stats(self, means, stds):
+        """Demo statistics [nframes, h, w, c] of the `final` end point for reward_costs (uploaded once)."""
+        shape = tuple(self.out_shape)
+        means, stds = (np.ascontiguousarray(a, np.float32) for a in (means, stds))
+        if means.ndim != 4 or means.shape[1:] != shape or stds.shape != means.shape:
+            raise ValueError(f"means / stds must be [nframes, {', '.join(map(str, shape))}], got {means.shape}, {stds.shape}")
+        self._ck(self._lib.ctx_cnn_reward_set_stats(self._h, shape[2], means.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                                    stds.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), means.shape[0]))
+        self._reward_frames = means.shape[0]
+
+    def reward_costs(self, frames_u8, npaths):
+        """uint8 frames [npaths * nframes, H, W, 3] -> costs [npaths, nframes] (forward + cost on the device; only the costs come back)."""
+        fr = self._check_frames(frames_u8)
+        F = getattr(self, "_reward_frames", 0)
+        if not F:
+            raise CtxError(_lib.CTX_E_STATE, "reward_costs: reward_set_stats first")
+        if fr.shape[0] != npaths * F:
+            raise ValueError(f"{fr.shape[0]} frames for {npaths} paths of {F}")
+        costs = np.empty((npaths, F), np.float32)
+        self._ck(self._lib.ctx_cnn_reward_costs(self._h, fr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), npaths,
+                                                costs.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        return costs
 
     @property
     def stream(self):

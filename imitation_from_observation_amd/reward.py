@@ -9,6 +9,8 @@ Restates the `mode == 'ours'` branch of BaseSampler.process_samples (rllab/sampl
 The arithmetic on the frames runs in the HIP translator; several paths are encoded per launch (the
 encoder is per-frame independent, so results do not depend on the grouping).  The reference's internal
 inconsistencies on this path (SURVEY.md 3.4 e-g) are resolved to the intended behaviour and noted inline.
+
+`InceptionFeatureReward` (end of file) is the comparison reward of modes 'inception' / 'inceptionsame' (base.py:69-111, 178-189).
 """
 from __future__ import annotations
 
@@ -206,6 +208,109 @@ class TranslatorReward:
             frames0 = self._frames_of(paths[0])
             self.build_demo_cache(self.validdata, [frames0[0][vp] for vp in range(self.nvp)], distributed=True)
         costs = self.paths_costs(paths, distributed=distributed)
+        for p, c in zip(paths, costs):
+            for j in range(self.batch_size):
+                p["rewards"][j * 2 + 1] -= c[j] * (j ** 2)
+        return costs
+
+
+class InceptionFeatureReward:
+    """The Inception-feature baseline of the reference's sampler (modes 'inception' / 'inceptionsame'; rllab/sampler/base.py:69-111
+    to set up, :178-189 per path).  Per path: the 25 rendered frames of viewpoint 0 go through the frozen Inception-v3 up to `layer`,
+      diff = means - feat;  diff[std == 0] = 0;  cost_j = mean over (h, w, c) of diff^2 / (std + 1e-5);  rewards[2j+1] -= cost_j * j^2.
+    means / std [25, h, w, c] come from a meanfile ('inception': npz[layer], npz[layer + 'std']) or from expert rollouts
+    ('inceptionsame': np.mean / np.std over axis 0 of their features).  Forward, statistics and cost run on the device
+    (InceptionFrontend.stats / reward_costs); only the [paths, 25] costs cross PCIe.  `front` must be built with final=layer."""
+
+    def __init__(self, front, layer, batch_size=25, paths_per_launch=None):
+        if layer == "Logits":
+            raise ValueError("Logits is 2-D after TF's squeeze: the reference's mean over axes (1, 2, 3) is not defined on it")
+        if getattr(front, "final", None) != layer:
+            raise ValueError(f"the cost reads the front end's last end point: build it with final={layer!r} (got {getattr(front, 'final', None)!r})")
+        self.front, self.layer, self.batch_size = front, layer, int(batch_size)
+        self.paths_per_launch = int(paths_per_launch or max(1, front.max_images // self.batch_size))
+        if self.batch_size > front.max_images:
+            raise ValueError(f"a path's {self.batch_size} frames exceed the front end's max_images {front.max_images}")
+        self.means, self.std = None, None
+
+    @classmethod
+    def for_sampler(cls, mode, layer, imsize, meanfile=None, expert_rollouts=None, inception_ckpt=None, batch_size=25,
+                    paths_per_launch=10, device=0):
+        """What BaseSampler.initialize() sets up for mode.startswith('inception') (base.py:69-111): the front end on the sampler's
+        imsize up to `layer` (variables from `inception_ckpt`, an .npz keyed by the TF names), and the statistics from `meanfile`
+        (mode 'inception') or from the frames of expert rollouts (mode 'inceptionsame'; the reference rolls out 20)."""
+        from .inception_frontend import InceptionFrontend
+        if mode not in ("inception", "inceptionsame"):
+            raise ValueError(f"mode must be 'inception' or 'inceptionsame', got {mode!r}")
+        # one forward holds as many whole paths as the front end's buffers allow (7 at 299 x 299); a launch of more is chunked
+        per_forward = max(1, min(paths_per_launch, InceptionFrontend.max_images_limit(imsize[0], imsize[1], layer) // batch_size))
+        front = InceptionFrontend(imsize[0], imsize[1], max_images=batch_size * per_forward, device=device, final=layer)
+        if inception_ckpt is not None:
+            front.load(inception_ckpt)
+        r = cls(front, layer, batch_size=batch_size, paths_per_launch=paths_per_launch)
+        if mode == "inception":
+            if meanfile is None:
+                raise ValueError("mode 'inception' reads its statistics from a meanfile")
+            r.load_meanfile(meanfile)
+        else:
+            if expert_rollouts is None:
+                raise ValueError("mode 'inceptionsame' builds its statistics from expert rollouts' frames")
+            r.build_stats(expert_rollouts)
+        return r
+
+    # ------------------------------------------------------------------ statistics
+    def set_stats(self, means, std):
+        self.front.reward_set_stats(means, std)
+        self.means, self.std = np.asarray(means, np.float32), np.asarray(std, np.float32)
+        return self
+
+    def load_meanfile(self, path):
+        """data = np.load(meanfile); means = data[layer]; std = data[layer + 'std'] (base.py:107-109)."""
+        with np.load(path) as z:
+            return self.set_stats(z[self.layer], z[self.layer + "std"])
+
+    def build_stats(self, rollouts):
+        """rollouts: per expert rollout, its batch_size uint8 frames [H, W, 3] (viewpoint 0; base.py:94-105).  means / std are
+        float32 np.mean / np.std over axis 0 of their features, bit for bit."""
+        (m, sd), = self.front.stats(rollouts, [self.layer], self.batch_size).values()
+        return self.set_stats(m, sd)
+
+    def build_meanfile(self, videos, layers, path=None):
+        """The two-pass meanfile builder of the notebooks (per layer: sum over videos / count, then sum of (v - mean)^2 / count, sqrt;
+        float32): one forward per video per pass through the front end for every end point in `layers` (at or before its `final`).  Writes
+        {layer: means, layer + 'std': std} to `path` (np.savez) when given; returns the dict."""
+        out = {}
+        for name, (m, sd) in self.front.stats(videos, layers, self.batch_size).items():
+            out[name], out[name + "std"] = m, sd
+        if path is not None:
+            np.savez(path, **out)
+        return out
+
+    # ------------------------------------------------------------------ base.py:178-189
+    @staticmethod
+    def _frames_of(path):
+        """imgs = [img[0] for img in env_infos['imgs'] if img is not None]: viewpoint 0 of every rendered step (base.py:182)."""
+        return [img[0] for img in path["env_infos"]["imgs"] if img is not None]
+
+    def paths_costs(self, paths):
+        """costs[p][j] for every path, paths_per_launch paths per device call."""
+        if self.means is None:
+            raise RuntimeError("no statistics: load_meanfile(path), build_stats(rollouts) or set_stats(means, std) first")
+        bs = self.batch_size
+        frames = [self._frames_of(p) for p in paths]
+        for f in frames:
+            if len(f) != bs:
+                raise ValueError(f"a path has {len(f)} rendered frames, the sampler's placeholder holds {bs} (base.py:72)")
+        costs = np.zeros((len(paths), bs), np.float32)
+        for p0 in range(0, len(paths), self.paths_per_launch):
+            grp = frames[p0:p0 + self.paths_per_launch]
+            u8 = np.stack([fr for f in grp for fr in f]).astype(np.uint8, copy=False)
+            costs[p0:p0 + len(grp)] = self.front.reward_costs(u8, len(grp))
+        return costs
+
+    def process_paths(self, paths):
+        """In place: path['rewards'][2j+1] -= cost_j * j**2 (base.py:188-189).  Returns the costs."""
+        costs = self.paths_costs(paths)
         for p, c in zip(paths, costs):
             for j in range(self.batch_size):
                 p["rewards"][j * 2 + 1] -= c[j] * (j ** 2)

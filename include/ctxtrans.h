@@ -45,7 +45,8 @@ extern "C" {
 
 #define CTX_ABI_VERSION 4   /* 2: ctx_config carries strides / kernels / filters / keep_prob / loss_mode; 3: per-handle options,
                                ctx_dp_train_step_sampled / ctx_dp_eval_sampled, ctx_prof_entry.useful_frac; 4: ctx_dev_frames;
-                               still 4 (additions only): ctx_vjp_args, ctx_dev_forward_vjp, ctx_dev_backward_vjp, ctx_params_written */
+                               still 4 (additions only): ctx_vjp_args, ctx_dev_forward_vjp, ctx_dev_backward_vjp, ctx_params_written;
+                               CTX_CNN_AVGPOOL_VALID / CTX_CNN_CONV_LINEAR, ctx_cnn_stats_*, ctx_cnn_reward_* */
 
 enum {
     CTX_OK = 0,
@@ -402,13 +403,18 @@ int ctx_debug_read(ctx_handle* h, const char* name, float* host, size_t n);
  *            filter [kh][kw][src channels (padded)][cout] at w_off, bias [cout] at b_off (floats into the blob);
  *            output written to channels [dst_ch0, dst_ch0 + cout) of buffer dst (tf.concat = adjacent slices).
  *   MAXPOOL  3x3 stride 2 VALID.     AVGPOOL  3x3 stride 1 SAME, mean over the taps inside the image.
+ *   AVGPOOL_VALID  kh x kw stride `stride` VALID, mean over the kh*kw taps: the classifier head's
+ *            slim.avg_pool2d(Mixed_7c, [min(h,8), min(w,8)], padding='VALID') = PreLogits (nets/inception_v3.py:510-515).
+ *   CONV_LINEAR    a CONV with bias and NO ReLU (slim.conv2d(..., activation_fn=None, normalizer_fn=None)): Logits = the 1x1
+ *            Conv2d_1c_1x1 on PreLogits (:518-519), 1001 classes padded to cout 1024 with zero filter columns and bias.
+ *            (ABI 4, additions only: kinds 3 and 4.)
  * Buffer 0 is the frame buffer (h, w, 32: channels 0..2 hold the frame); the LAST buffer is the output.
  * Every buffer is written once per pass (by one op, or by several ops into disjoint channel slices). */
-enum { CTX_CNN_CONV = 0, CTX_CNN_MAXPOOL = 1, CTX_CNN_AVGPOOL = 2 };
+enum { CTX_CNN_CONV = 0, CTX_CNN_MAXPOOL = 1, CTX_CNN_AVGPOOL = 2, CTX_CNN_AVGPOOL_VALID = 3, CTX_CNN_CONV_LINEAR = 4 };
 typedef struct ctx_cnn_buf { int32_t h, w, c; } ctx_cnn_buf;
 typedef struct ctx_cnn_op {
     int32_t kind, src, dst, dst_ch0;
-    int32_t kh, kw, stride, same;     /* CONV only; same: 1 = 'SAME', 0 = 'VALID' */
+    int32_t kh, kw, stride, same;     /* CONV / CONV_LINEAR (same: 1 = 'SAME', 0 = 'VALID') and AVGPOOL_VALID (kh, kw, stride) */
     int32_t cout;
     int32_t lane;                     /* 0..3: ops of different lanes may run concurrently (the branches of an Inception block);
                                          the library orders every op after the writers of its src buffer */
@@ -442,6 +448,32 @@ int ctx_cnn_read_buffer(ctx_cnn* h, int index, int n, float* out);   /* end-poin
 int ctx_cnn_profile(ctx_cnn* h, int n, int iters, float* ms, int max_ops);
 void* ctx_cnn_stream(ctx_cnn* h);
 int ctx_cnn_sync(ctx_cnn* h);
+
+/* ---- Inception-feature baseline reward (modes 'inception' / 'inceptionsame', rllab/sampler/base.py:69-111, 178-189) ----
+ * Per-timestep demo statistics, accumulated on the device from the activation buffers in place (their padded channel stride):
+ *   ctx_cnn_stats_reset   slots = the buffers (index as in ctx_cnn_create; not buffer 0) with their REAL channel counts
+ *                         channels[i] (> buffer width - 32) to accumulate, over videos of nframes frames (1 <= nframes <= max_images).
+ *                         Every slot's statistics are [nframes, h, w, channels[i]].  Clears the accumulators.
+ *   ctx_cnn_stats_add_u8  frames: host uint8 [nvideos * nframes, H, W, 3]; runs the forward (whole videos per pass, max_images /
+ *                         nframes of them) and adds  x  (pass 0) or  (x - mean)^2  (pass 1) per element, videos in order.
+ *   ctx_cnn_stats_finish  pass 0: mean = sum / count; pass 1: std = sqrt(sum / count).  Pass 1 must see as many videos as pass 0.
+ *   ctx_cnn_stats_read    slot's means (after finish(0)) and stds (after finish(1); nullable) into host [nframes, h, w, c]; *count
+ *                         (nullable) = videos of pass 0.
+ * Every sum is a sequential f32 loop in video order without contraction, division and sqrt correctly rounded: the results equal
+ * numpy's float32  np.mean(v, 0) / np.std(v, 0)  over the videos' features bit for bit.  Calls out of order: CTX_E_STATE.
+ *
+ * The per-path cost on the LAST buffer (the front end's `final` end point):
+ *   ctx_cnn_reward_set_stats  means / stds: host f32 [nframes, h, w, channels] (channels = the last buffer's real count).
+ *   ctx_cnn_reward_costs      frames: host uint8 [npaths * nframes, H, W, 3] -> costs [npaths * nframes]:
+ *                             costs[f] = mean over (h, w, c) of d^2 / (std + 1e-5),  d = means[f % nframes] - x[f], d = 0 where std == 0
+ *                             (terms in f32, summed in f64 in a fixed order).  Whole paths per forward; only the costs cross PCIe.
+ *                             CTX_E_STATE before ctx_cnn_reward_set_stats. */
+int ctx_cnn_stats_reset(ctx_cnn* h, const int32_t* buffers, const int32_t* channels, int nslots, int nframes);
+int ctx_cnn_stats_add_u8(ctx_cnn* h, const uint8_t* frames, int nvideos, int pass);
+int ctx_cnn_stats_finish(ctx_cnn* h, int pass);
+int ctx_cnn_stats_read(ctx_cnn* h, int slot, float* means, float* stds, int* count);
+int ctx_cnn_reward_set_stats(ctx_cnn* h, int channels, const float* means, const float* stds, int nframes);
+int ctx_cnn_reward_costs(ctx_cnn* h, const uint8_t* frames, int npaths, float* costs);
 
 #ifdef __cplusplus
 }
