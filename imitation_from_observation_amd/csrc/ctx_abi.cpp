@@ -78,7 +78,10 @@ int ctx_create_ex(const ctx_config* cfg, int device, void* stream, void* arena, 
             h->own_arena = true;
         }
     }
-    if (rc == CTX_OK) rc = h->gen ? gen_alloc(h) : alloc_buffers(h);
+    if (rc == CTX_OK) {
+        set_routing(h);
+        rc = h->gen ? gen_alloc(h) : alloc_buffers(h);
+    }
     // packed-filter cache (dconv.h: DcPackCache): only where the library owns the parameters -- a caller-owned arena (ctx_create_ex) may be
     // written behind the handle's back, there every launch packs as before
     if (rc == CTX_OK && h->own_arena) {

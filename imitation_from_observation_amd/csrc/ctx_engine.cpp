@@ -1,6 +1,9 @@
 // ctx_engine.cpp -- the launch sequences of libctxtrans.so: buffers, forward / backward / Adam of ContextSkipNew
 // (gym/envs/mujoco/arm_shaping.py:1272-1354), the table-driven engine of ContextAEReal / ContextAEInception2 (ctxtrans_gen.inc), the
 // captured inference forwards.  No CPU code path: every contraction runs in the HIP kernels of igemm.h / kernels.hip / the direct kernels.
+// Both engines launch their layers through the helpers under "layer launch helpers": fc_layer / fc_dx / fc_dw, and conv / convt / wgrad
+// / convt3, which alone choose the kernel of a conv-type layer; the rules in which the variants differ are the handle's routing record
+// (ctx_handle::rt, set_routing).
 #include "ctx_internal.h"
 
 namespace ctxi {
@@ -24,7 +27,7 @@ int fail(ctx_handle* h, int code, const char* fmt, ...) {
 struct ProfScope {
     ctx_handle* h;
     int idx = -1;
-    // useful: share of `flops` whose product meets two data operands (tap_frac for SAME-padded convolutions; 1 elsewhere)
+    // useful: share of `flops` whose product meets two data operands (tap_frac_p for SAME-padded convolutions; 1 elsewhere)
     ProfScope(ctx_handle* h_, const std::string& name, const char* kernel, double flops, double useful = 1.0) : h(h_) {
         if (!h->prof_on) return;
         idx = h->prof_cursor++;
@@ -51,21 +54,8 @@ struct ProfScope {
 
 // Share of a SAME-padded K x K stride-s layer's (position, tap) pairs whose tap lies INSIDE the image: the products of the conv, of
 // its transposed conv and of its filter gradient that multiply data and not padding zeros.  n_big = the layer's large grid (conv
-// input = transposed-conv output); TF's rule: out = ceil(n / s), pad_total = max((out - 1) s + K - n, 0), before = total / 2.
+// input = transposed-conv output), n_small = its small grid, pad = pad_before.
 // 5x5 stride 2 on an even grid: (5 n_small - 3) / (5 n_small) per axis -- 92.6 / 85.6 / 72.3 % in 2-D on 16x16 / 8x8 / 4x4 grids.
-double tap_frac1(int n_big, int K, int s) {
-    const int n_small = (n_big + s - 1) / s;
-    const int total = std::max((n_small - 1) * s + K - n_big, 0), before = total / 2;
-    int64_t valid = 0;
-    for (int i = 0; i < n_small; ++i)
-        for (int k = 0; k < K; ++k) {
-            const int y = s * i + k - before;
-            valid += y >= 0 && y < n_big;
-        }
-    return (double)valid / ((double)K * n_small);
-}
-double tap_frac(int hb, int wb, int K, int s) { return tap_frac1(hb, K, s) * tap_frac1(wb, K, s); }
-// the same count for a layer given by its own (stride, pad_before) -- the table-driven models' parameterisation
 double tap_frac_p1(int n_big, int n_small, int K, int s, int pad) {
     int64_t valid = 0;
     for (int i = 0; i < n_small; ++i)
@@ -177,7 +167,24 @@ void build_params(const ctx_config& c, std::vector<ParamInfo>& out, int64_t& tot
 
 int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
-
+// what both engines' buffers end with: reduction scratch for up to `maxc` columns, the split-K slab, the direct kernels' filter
+// packs (one of each per stream lane), the loss scalars and 256 B of zeros
+int alloc_tail(ctx_handle* h, int64_t slab_floats, int64_t maxc) {
+    const int64_t scratch = std::max<int64_t>(4 * LOSS_BLOCKS, (int64_t)COLSUM_SPLITS * maxc);
+    TRY(dev_alloc(h, &h->scratch, scratch));
+    h->slab_floats = slab_floats;
+    TRY(dev_alloc(h, &h->slab, h->slab_floats));
+    TRY(dev_alloc(h, &h->wpack, DC_WPACK_FLOATS));
+    for (int l = 0; l < ctx_handle::NLANE; ++l) {
+        TRY(dev_alloc(h, &h->slabL[l], h->slab_floats));
+        TRY(dev_alloc(h, &h->scratchL[l], scratch));
+        TRY(dev_alloc(h, &h->wpackL[l], DC_WPACK_FLOATS));
+    }
+    TRY(dev_alloc(h, &h->scalars, 4));
+    TRY(dev_alloc(h, &h->zeros, 64));
+    if (hipMemset(h->zeros, 0, 64 * sizeof(float)) != hipSuccess) return fail(h, CTX_E_DEVICE, "hipMemset(zeros)");
+    return CTX_OK;
+}
 
 int alloc_buffers(ctx_handle* h) {
     const int64_t B = h->Bm, d = h->d, F = h->F;
@@ -222,21 +229,7 @@ int alloc_buffers(ctx_handle* h) {
     }
     TRY(dev_alloc(h, &h->dout, 2 * B * h->npi));
     TRY(dev_alloc(h, &h->dout4, 2 * B * h->npi / 3 * 4));
-    int64_t maxc = std::max<int64_t>(h->D0, F);
-    maxc = std::max<int64_t>(maxc, 16 * d);
-    TRY(dev_alloc(h, &h->scratch, std::max<int64_t>(4 * LOSS_BLOCKS, (int64_t)COLSUM_SPLITS * maxc)));
-    h->slab_floats = 32ll << 20;
-    TRY(dev_alloc(h, &h->slab, h->slab_floats));
-    TRY(dev_alloc(h, &h->wpack, DC_WPACK_FLOATS));
-    for (int l = 0; l < ctx_handle::NLANE; ++l) {
-        TRY(dev_alloc(h, &h->slabL[l], h->slab_floats));
-        TRY(dev_alloc(h, &h->scratchL[l], std::max<int64_t>(4 * LOSS_BLOCKS, (int64_t)COLSUM_SPLITS * maxc)));
-        TRY(dev_alloc(h, &h->wpackL[l], DC_WPACK_FLOATS));
-    }
-    TRY(dev_alloc(h, &h->scalars, 4));
-    TRY(dev_alloc(h, &h->zeros, 64));
-    if (hipMemset(h->zeros, 0, 64 * sizeof(float)) != hipSuccess) return fail(h, CTX_E_DEVICE, "hipMemset(zeros)");
-    return CTX_OK;
+    return alloc_tail(h, 32ll << 20, std::max<int64_t>(std::max<int64_t>(h->D0, F), 16 * d));
 }
 
 // the 4-channel copy of a pointer into img / dout (cin = 3 loaders); pack_c4 refreshes `npix` pixels of it
@@ -250,7 +243,7 @@ void pack_c4(ctx_handle* h, const float* p3, int64_t npix) { pack3to4(h->stream,
 // terms of `loss` (ctx_config.loss_terms; 0 = all)
 int loss_terms_of(const ctx_handle* h) { return h->cfg.loss_terms ? h->cfg.loss_terms : 7; }
 
-SplitWs ws_of(ctx_handle* h) { return SplitWs{h->slab, h->slab_floats, h->cfg.precision, h->gen ? 0 : 7}; }
+SplitWs ws_of(ctx_handle* h) { return SplitWs{h->slab, h->slab_floats, h->cfg.precision, h->rt.swz}; }
 
 // Everything below enqueues on h->stream with h->slab / h->scratch; LaneSwap points those at the second lane
 // for the lifetime of a scope.  fork(): the second lane starts after everything enqueued so far on the
@@ -430,44 +423,42 @@ bool use_dc3(const ctx_handle* h) {
     return on && dconv_ok(3, h->d) && dconv_ok(3, 2 * h->d);
 }
 
+// The conv-layer routing rules of this handle's variant.  Every rule that ContextSkipNew and the table-driven models do not share is
+// here, with the reason; the options read (direct3, dconv) are create-only, precision and variant are fixed by the config.
+void set_routing(ctx_handle* h) {
+    Routing& rt = h->rt;
+    const bool skipnew = !h->gen, f32 = h->cfg.precision == CTX_PREC_F32;
+    rt.swz = skipnew ? 7 : 0;          // the XCD swizzle was measured to pay on ContextSkipNew's launches only (launch.h: SplitWs)
+    rt.wconvt = skipnew;               // wconvt.hip's tiles were tuned and measured on ContextSkipNew's 5x5 stride-2 layers only
+    rt.patch = skipnew;                // measured on ContextSkipNew's grids only (the rectangle order covers nimg % 32 == 0 anyway)
+    rt.starved = skipnew;              // the reward hook's 25-frame launches; only alloc_buffers sizes the product buffer PP
+    // smallest grid whose stride-2 transposed conv runs position-major: in f32 ContextSkipNew's 4x4 grids keep the class-major launch
+    // (64 problems of 1 .. 9 taps leave a tail)
+    rt.q_minpos = skipnew && f32 ? 64 : 0;
+    rt.h4_direct_bf16 = skipnew;       // exact f32 arithmetic either way; measured faster in ContextSkipNew's split-bf16 step only
+    rt.direct3 = skipnew ? use_dc3(h) : h->gen->narrow;   // ContextAEReal's narrow f32 path runs every layer on the direct kernels
+}
+
 // d_h4 (conv2d_transpose to the 3 image channels) in one pass on the vector ALUs (convt3.hip) instead of scatter product + gather.
-// ContextSkipNew: both precisions (exact f32 arithmetic either way); the table-driven models: exact-f32 mode only.
 // CTX_CONVT3_DIRECT=0 restores the two-step route (and its P3 buffer).
 bool d_h4_direct(const ctx_handle* h, int c1, int c2, int hs, int ws, int stride) {
     const bool on = (h->opt.v[OPT_DIRECT3] & 8) != 0;
-    return on && (h->cfg.precision == CTX_PREC_F32 || !h->gen) && convt3_direct_ok(c1, c2, hs, ws, stride);
+    return on && (h->cfg.precision == CTX_PREC_F32 || h->rt.h4_direct_bf16) && convt3_direct_ok(c1, c2, hs, ws, stride);
 }
 bool use_q(int nimg) { return opt(OPT_POSMAJOR) && nimg >= 64; }
 
-// smallest grid (positions) whose transposed conv runs position-major: in f32 the 4x4 grids keep the class-major launch (64 problems of
-// 1 .. 9 taps leave a tail)
-int q_minpos(const ctx_handle* h) { return h->cfg.precision ? 0 : 64; }
-
-// y = lrelu(conv2d(x) + b): x [nimg, hb, wb, ca] -> y [nimg, hb/2, wb/2, cb]
-void conv_layer(ctx_handle* h, const std::string& name, const float* x, int nimg, int hb, int wb, int ca, const float* w,
-                const float* b, float* y, int cb) {
-    const int hs = hb / 2, ws = wb / 2, R = nimg * hs * ws;
+// bias + activation into y (row stride ld)
+Epi epi_act(float* y, int64_t ld, const float* b, int lrelu) {
     Epi ep;
-    ep.out1 = y; ep.ld1 = cb; ep.bias = b; ep.lrelu = 1;
-    const bool c3 = ca == 3 && use_dc3(h) && c3conv_ok(hb, wb, 2, cb, ep);
-    ProfScope ps(h, name + " fwd", ca == 3 ? (c3 ? K_C3CONV : use_dc3(h) ? K_DCFWD : K_C3FWD) : K_CONV, 2.0 * R * 25 * ca * cb, tap_frac(hb, wb, 5, 2));
-    if (c3) c3conv(h->stream, x, nimg, hb, wb, 2, w, cb, ep);
-    else if (ca == 3 && use_dc3(h)) {
-        DcFwd P{};
-        P.x1 = x; P.ld1 = 3; P.c1 = 3; P.CI = 3; P.hin = hb; P.win = wb; P.nimg = nimg; P.w = w; P.wmode = 0; P.N = cb; P.ep = ep; P.wp = h->wpack; P.pc = &h->pack;
-        dconv_conv(h->stream, P, 2, 1);
-    } else if (ca == 3) conv3_fwd(h->stream, KmC3Gather{c4of(h, x), hb, wb, hs, ws, R, g_zeros}, NmC3Weights{w, cb, g_zeros}, ep, R, cb, ws_of(h));
-    else if (use_q(nimg)) conv_fwd_q(h->stream, KmConvGatherQ{x, ca, make_posgeo(hs, ws, hb, wb, 2, 1, 5, ca / KC), nimg, g_zeros}, NmConvWeightsQ{w, ca, cb, 5, g_zeros}, ep, cb, ws_of(h));
-    else conv_fwd(h->stream, KmConvGather{x, ca, hb, wb, hs, ws, ca / KC, R, g_zeros}, nm(w, cb, cb, 25 * ca), ep, R, cb, ws_of(h));
+    ep.out1 = y; ep.ld1 = ld; ep.bias = b; ep.lrelu = lrelu;
+    return ep;
 }
 
 // y = act(x W + b), x possibly [x0 | x1] along K
 void fc_layer(ctx_handle* h, const std::string& name, const KmPlain& a, int M, int K, const float* w, const float* b, int N,
               int lrelu, float* y) {
     ProfScope ps(h, name + " fwd", K_FCFWD, 2.0 * M * K * N);
-    Epi ep;
-    ep.out1 = y; ep.ld1 = N; ep.bias = b; ep.lrelu = lrelu;
-    gemm_fc_fwd(h->stream, a, nm(w, N, N, K), ep, M, N, K / KC, ws_of(h));
+    gemm_fc_fwd(h->stream, a, nm(w, N, N, K), epi_act(y, N, b, lrelu), M, N, K / KC, ws_of(h));
 }
 
 // dx = dy W^T (+ epilogue): dy [M, N], W [K, N] -> dx [M, K]
@@ -496,6 +487,169 @@ void fc_dw(ctx_handle* h, const std::string& name, const XL& x, int K, const flo
     bias_grad(h, name, dy, M, N, db);
 }
 
+// The conv-type layers of both engines: which kernel runs a launch is decided here and nowhere else, from the layer's geometry, the
+// handle's routing record (h->rt) and two facts of the call: `direct` (this layer runs on the direct kernels of dconv.h) and `infer`
+// (an inference forward: translate / encode).  The engines decide which buffers a layer reads and writes and on which lane it runs.
+
+// a SAME-padded K x K stride-s layer: big grid hb x wb (conv input = transposed-conv output), small grid hs x ws, pad = pad_before
+struct Geo { int hb, wb, hs, ws, s, pad, K; };
+double useful_frac(const Geo& g) { return tap_frac_p(g.hb, g.wb, g.hs, g.ws, g.K, g.s, g.pad); }
+// small-grid operand [x1 | x2] of c1 + c2 channels, x2 (a decoder layer's ctx skip) read at image index img % nmod2; c2 = 0: x1 alone
+struct Cat { const float* x1; int c1; const float* x2 = nullptr; int c2 = 0; int nmod2 = 1; };
+
+// y = conv2d(x, w) into ep: x [nimg, hb, wb, ca] -> [nimg, hs, ws, cb], w read as [K, K, ca, cb].  The encoders' layers and the input
+// gradient of every decoder layer.
+void conv(ctx_handle* h, const std::string& label, const Geo& g, const float* x, int ca, int nimg, const float* w, int cb, const Epi& ep,
+          bool direct) {
+    const int R = nimg * g.hs * g.ws, K2 = g.K * g.K;
+    const bool c3 = direct && ca == 3 && g.K == 5 && g.pad == (5 - g.s) / 2 && c3conv_ok(g.hb, g.wb, g.s, cb, ep);
+    ProfScope ps(h, label, c3 ? K_C3CONV : direct ? K_DCFWD : ca == 3 ? K_C3FWD : K_CONV, 2.0 * R * K2 * ca * cb, useful_frac(g));
+    if (c3) c3conv(h->stream, x, nimg, g.hb, g.wb, g.s, w, cb, ep);
+    else if (direct) {
+        DcFwd P{};
+        P.x1 = x; P.ld1 = ca; P.c1 = ca; P.CI = ca; P.hin = g.hb; P.win = g.wb; P.nimg = nimg;
+        P.w = w; P.wmode = 0; P.N = cb; P.ep = ep; P.wp = h->wpack; P.pc = &h->pack;
+        dconv_conv(h->stream, P, g.s, g.pad);
+    } else if (ca == 3) {
+        KmC3Gather a{c4of(h, x), g.hb, g.wb, g.hs, g.ws, R, g_zeros};
+        a.s = g.s; a.pad = g.pad;
+        conv3_fwd(h->stream, a, NmC3Weights{w, cb, g_zeros}, ep, R, cb, ws_of(h));
+    } else if (use_q(nimg)) {                      // position-major: only the taps inside the grid (on a 1x1 grid: 1 of K*K)
+        conv_fwd_q(h->stream, KmConvGatherQ{x, ca, make_posgeo(g.hs, g.ws, g.hb, g.wb, g.s, g.pad, g.K, ca / KC), nimg, g_zeros},
+                   NmConvWeightsQ{w, ca, cb, g.K, g_zeros}, ep, cb, ws_of(h));
+    } else {
+        KmConvGather a{x, ca, g.hb, g.wb, g.hs, g.ws, ca / KC, R, g_zeros};
+        a.s = g.s; a.pad = g.pad; a.K = g.K;
+        conv_fwd(h->stream, a, nm(w, cb, cb, K2 * ca), ep, R, cb, ws_of(h));
+    }
+}
+
+// y = conv2d_transpose(in, w) into ep: in [nimg, hs, ws, c1 + c2] -> [nimg, hb, wb, ca], w [K, K, ca, c1 + c2].  The decoders'
+// d_h1 .. d_h3, the input gradient of encoder layers >= 1, the feature-map gradients of a VJP.
+void convt(ctx_handle* h, const std::string& label, const Geo& g, const Cat& in, int nimg, const float* w, int ca, const Epi& ep,
+           bool direct, bool infer) {
+    const int hs = g.hs, ws = g.ws, R = nimg * hs * ws, cb = in.c1 + in.c2, K2 = g.K * g.K;
+    const bool k5s2 = g.K == 5 && g.s == 2;
+    // starved inference launches (the reward hook's 25 frames): one plain product + a gather of bias + lrelu (launch.h: convt_product)
+    // (measured at 25 frames: 4x4 grid 130 -> 87 us; the 8x8 / 16x16 grids 75 / 73 -> 87 / 85 us, so those stay on the tiles)
+    const bool prod = !direct && h->rt.starved && infer && k5s2 && nimg <= PP_IMG && hs * ws <= 16 && h->PP && (h->opt.v[OPT_WCONVT] & 16) &&
+                      ca % 4 == 0 && cb % KC == 0 && in.c1 % KC == 0;
+    // (split-bf16 mode: the exact-f32 kernel only where it is the faster one -- the 16x16 grids' few-channel input gradients)
+    const bool wide = !direct && !prod && h->rt.wconvt && k5s2 && (h->cfg.precision == CTX_PREC_F32 || (in.c2 == 0 && hs == 16)) &&
+                      wconvt_ok(hs, ws, in.c1, in.c2, ca, nimg);
+    ProfScope ps(h, label, direct ? K_DCFWD : prod ? K_CONVT3P : wide ? K_WCONVT : g.s == 2 ? K_CONVT : K_CONVT1,
+                 2.0 * R * K2 * cb * ca, useful_frac(g));
+    if (direct) {
+        DcFwd P{};
+        P.x1 = in.x1; P.ld1 = in.c1; P.c1 = in.c1; P.CI = cb;
+        if (in.x2) { P.x2 = in.x2; P.ld2 = in.c2; P.nmod2 = in.nmod2; }
+        P.hin = hs; P.win = ws; P.nimg = nimg; P.w = w; P.wmode = 1; P.N = ca; P.ep = ep; P.wp = h->wpack; P.pc = &h->pack;
+        if (g.s == 2) dconv_convt2(h->stream, P); else dconv_convt1(h->stream, P);
+    } else if (prod) {
+        convt_product(h->stream, KmCat2{in.x1, in.c1, in.c1, in.x2, in.c2, in.nmod2, hs * ws, R, cb / KC, g_zeros}, w, cb, ca, h->PP, R, ws_of(h));
+        convt_gather(h->stream, h->PP, ep.bias, ep.out1, nimg, hs, ws, ca, ep.lrelu);
+    } else if (wide) {
+        wconvt_fwd(h->stream, in.x1, in.c1, in.x2, in.c2, in.nmod2, nimg, hs, ws, w, ca, ep, ws_of(h));
+    } else if (g.s == 2 && use_q(nimg) && hs * ws >= h->rt.q_minpos) {
+        convt_fwd_q(h->stream, KmConvTGatherQ{in.x1, in.c1, in.c1, in.x2, in.c2, in.nmod2, make_tposgeo(hs, ws, g.K, g.pad, cb / KC), nimg, g_zeros},
+                    KmConvTWeightsQ{w, ca, cb, g.K, g_zeros}, ep, ca, ws_of(h));
+    } else if (g.s == 2) {
+        KmConvTGather a{in.x1, in.c1, in.c1, in.x2, in.c2, in.nmod2, hs, ws, cb / KC, R, g_zeros};
+        a.K = g.K; a.pb = g.pad;
+        KmConvTWeights b{w, ca, cb, cb / KC, g_zeros};
+        b.K = g.K; b.pb = g.pad;
+        convt_fwd(h->stream, a, b, ep, R, ca, ws_of(h));
+    } else if (use_q(nimg) && hs * ws <= 64) {     // stride 1, position-major: only the taps inside the (small) grid
+        convt1_fwd_q(h->stream, KmConvT1GatherQ{in.x1, in.c1, in.c1, in.x2, in.c2, in.nmod2, make_posgeo(hs, ws, hs, ws, 1, g.K - 1 - g.pad, g.K, cb / KC), nimg, g_zeros},
+                     KmConvT1WeightsQ{w, ca, cb, g.K, g_zeros}, ep, ca, ws_of(h));
+    } else {                                       // stride 1: a correlation with the mirrored offsets
+        KmConvGather a{in.x1, in.c1, hs, ws, hs, ws, cb / KC, R, g_zeros};
+        a.s = 1; a.pad = g.pad; a.flip = 1; a.K = g.K;
+        if (in.x2) { a.x2 = in.x2; a.ldx2 = in.c2; a.c1 = in.c1; a.nmod2 = in.nmod2; }
+        KmConvTWeights b{w, ca, cb, cb / KC, g_zeros};
+        b.flip25 = 1; b.K = g.K;
+        convt1_fwd(h->stream, a, b, ep, R, ca, ws_of(h));
+    }
+}
+
+// dw [K, K, ca, c1 + c2] of a layer with big-grid side `big` [nimg, hb, wb, ca] and small-grid side `in` [nimg, hs, ws, c1 + c2], and
+// db = the column sums of the layer's output gradient: `big` for a two-operand launch (a decoder's transposed conv), `in` otherwise
+void wgrad(ctx_handle* h, const std::string& name, const Geo& g, const float* big, int ca, const Cat& in, int nimg, float* dw, float* db,
+           bool direct) {
+    const int cb = in.c1 + in.c2, R = nimg * g.hs * g.ws, K2 = g.K * g.K;
+    const bool two = in.x2 != nullptr;
+    if (two) bias_grad(h, name, big, (int64_t)nimg * g.hb * g.wb, ca, db);
+    else if (!direct) bias_grad(h, name, in.x1, R, cb, db);     // (direct: dconv_wgrad returns the column sums of its small operand too)
+    const double fl = 2.0 * R * K2 * ca * cb, uf = useful_frac(g);
+    if (direct) {
+        DcWgrad W{};
+        W.big = big; W.ldb = ca; W.CA = ca; W.s1 = in.x1; W.ld1 = in.c1; W.c1 = in.c1; W.CB = cb;
+        if (two) { W.s2 = in.x2; W.ld2 = in.c2; W.nmod2 = in.nmod2; }
+        else W.db = db;
+        W.hb = g.hb; W.wb = g.wb; W.hs = g.hs; W.ws = g.ws; W.nimg = nimg; W.S = g.s; W.pad = g.pad; W.out = dw;
+        ProfScope ps(h, name + " dw", dw_label(W), fl, uf);
+        dconv_wgrad(h->stream, W, h->slab, h->slab_floats);
+        return;
+    }
+    Epi eg;
+    eg.out1 = dw; eg.ld1 = cb;
+    const int hsws = g.hs * g.ws, sh = make_pixdiv(1, hsws).ws_sh;
+    const NmWgradSmall s1{in.x1, in.c1, in.c1, nullptr, 0, 1, cb, hsws, sh, R, g_zeros};
+    const NmWgradSmall2 s2{in.x1, in.c1, in.c1, in.x2, in.c2, in.nmod2, cb, hsws, sh, R, g_zeros};
+    if (ca == 3) {
+        NmC3WgradBig b{c4of(h, big), g.hb, g.wb, make_pixdiv(g.hs, g.ws), R, g_zeros};
+        b.s = g.s; b.pad = g.pad;
+        ProfScope ps(h, name + " dw", K_C3WGRAD, fl, uf);
+        if (two) conv3_wgrad2(h->stream, b, s2, eg, cb, ws_of(h));
+        else conv3_wgrad(h->stream, b, s1, eg, cb, ws_of(h));
+        return;
+    }
+    ProfScope ps(h, name + " dw", K_WGRAD, fl, uf);
+    if (rect_ok(nimg) && (!two || rect_ok(in.nmod2))) {
+        const RectGeo rg = make_rect(nimg, g.hs, g.ws, g.hb, g.wb, g.s, g.pad, g.K);
+        const NmWgradBigR b{big, ca, ca, rg, g_zeros};
+        if (two) conv_wgrad2_r(h->stream, b, NmWgradSmall2R{in.x1, in.c1, in.c1, in.x2, in.c2, in.nmod2, cb, rg, g_zeros}, eg, ca, cb, ws_of(h));
+        else conv_wgrad_r(h->stream, b, NmWgradSmallR{in.x1, in.c1, in.c1, rg, g_zeros}, eg, ca, cb, ws_of(h));
+    } else if (h->rt.patch && g.K == 5 && g.s == 2 && g.pad == 1 && patch_ok(g.hs, g.ws)) {   // (the patch loaders know hb = 2 hs only)
+        const PatchGeo pg = make_patch(nimg, g.hs, g.ws);
+        const NmWgradBigP b{big, ca, ca, g.wb, pg, g_zeros};
+        if (two) conv_wgrad2_p(h->stream, b, NmWgradSmall2P{in.x1, in.c1, in.c1, in.x2, in.c2, in.nmod2, cb, pg, g_zeros}, eg, ca, cb, ws_of(h));
+        else conv_wgrad_p(h->stream, b, NmWgradSmallP{in.x1, in.c1, in.c1, pg, g_zeros}, eg, ca, cb, ws_of(h));
+    } else {
+        NmWgradBig b{big, ca, ca, g.hb, g.wb, make_pixdiv(g.hs, g.ws), R, g_zeros};
+        b.s = g.s; b.pad = g.pad; b.K = g.K;
+        if (two) conv_wgrad2(h->stream, b, s2, eg, ca, cb, ws_of(h));
+        else conv_wgrad(h->stream, b, s1, eg, ca, cb, ws_of(h));
+    }
+}
+
+// out = conv2d_transpose(in, w) + b to the 3 image channels (d_h4): in [nimg, hs, ws, c1 + c2] -> out [nimg, hb, wb, 3]
+void convt3(ctx_handle* h, const std::string& name, const Geo& g, const Cat& in, int nimg, const float* w, const float* b, float* out,
+            bool infer) {
+    const int hs = g.hs, ws = g.ws, R = nimg * hs * ws, cb = in.c1 + in.c2, K2 = g.K * g.K;
+    const double fl = 2.0 * R * K2 * cb * 3, uf = useful_frac(g);
+    // (starved inference launches take the product + gather route here too: the direct kernel offers 200 two-wave tiles to 256 CUs
+    // at 25 frames, 54 us)
+    const bool prod = h->rt.starved && infer && nimg <= PP_IMG && (h->opt.v[OPT_WCONVT] & 16) && cb % KC == 0 && in.c1 % KC == 0;
+    if (d_h4_direct(h, in.c1, in.c2, hs, ws, g.s) && !prod) {
+        ProfScope ps(h, name + " fwd", K_CONVT3D, fl, uf);
+        convt3_direct(h->stream, in.x1, in.c1, in.x2, in.c2, in.nmod2, nimg, hs, ws, g.s, w, b, out);
+        return;
+    }
+    const KmCat2 a{in.x1, in.c1, in.c1, in.x2, in.c2, in.nmod2, hs * ws, R, cb / KC, g_zeros};
+    {
+        ProfScope ps(h, name + " fwd product", K_CONVT3P, fl, uf);
+        if (g.s == 2) convt3_product(h->stream, a, w, cb, h->P3, R, ws_of(h));
+        else convt3_product_t(h->stream, a, w, cb, h->P3, R, ws_of(h));
+    }
+    ProfScope ps(h, name + " fwd gather", K_CONVT3, 0.0);
+    if (g.s == 2) convt3_gather(h->stream, h->P3, b, out, nimg, hs, ws);
+    else convt3_gather_s1_t(h->stream, h->P3, b, out, nimg, hs, ws);
+}
+
+// ContextSkipNew's layer k (encoder h_k; decoder d_h(4-k) mirrors it): 5x5 stride 2 from the grid H >> k
+Geo skip_geo(const ctx_handle* h, int k) { return Geo{h->hh[k], h->ww[k], h->hh[k + 1], h->ww[k + 1], 2, 1, 5}; }
+
 struct Scope {
     float *w[4], *b[4], *w4, *b4, *wz, *bz;
     float *gw[4], *gb[4], *gw4, *gb4, *gwz, *gbz;
@@ -520,11 +674,11 @@ void encoder_fwd(ctx_handle* h, const std::string& scn, const Scope& sc, const f
                  int z_lrelu) {
     const int d = h->d, F = h->F;
     const float* in = x;
-    int ca = 3;
     for (int k = 0; k < 4; ++k) {
-        conv_layer(h, scn + "/h" + std::to_string(k) + "_conv", in, nimg, h->hh[k], h->ww[k], ca, sc.w[k], sc.b[k], act[k], d << k);
+        const int ca = k ? d << (k - 1) : 3;
+        conv(h, scn + "/h" + std::to_string(k) + "_conv fwd", skip_geo(h, k), in, ca, nimg, sc.w[k], d << k, epi_act(act[k], d << k, sc.b[k], 1),
+             ca == 3 && h->rt.direct3);
         in = act[k];
-        ca = d << k;
     }
     const int K3 = h->hh[4] * h->ww[4] * 8 * d;   // NHWC flatten, arm_shaping.py:1287
     fc_layer(h, scn + "/h4_lin", km(act[3], K3, nimg, K3), nimg, K3, sc.w4, sc.b4, F, 1, act[4]);
@@ -573,7 +727,7 @@ void frame_grads3(ctx_handle* h, const float* dA0, int c, int slot0, int nimg, i
     for (int j = 0; j < nimg / B; ++j) {
         float* o = vjp_frame_out(h, slot0 + j);
         if (!o) continue;
-        ProfScope ps(h, "frames dx", K_CONVT3D, 2.0 * B * hs * ws * 25 * c * 3, tap_frac(hs * stride, ws * stride, 5, stride));
+        ProfScope ps(h, "frames dx", K_CONVT3D, 2.0 * B * hs * ws * 25 * c * 3, useful_frac(Geo{hs * stride, ws * stride, hs, ws, stride, (5 - stride) / 2, 5}));
         convt3_direct(h->stream, dA0 + (int64_t)j * B * hs * ws * c, c, dA0, 0, 1, B, hs, ws, stride, w, h->zeros, o);
         if (slot0 + j == 0) recon_tgt_term(h, o);
     }
@@ -600,7 +754,7 @@ void forward(ctx_handle* h, int B, Mode mode) {
     // / image index n % 1 by their consumers -- same values as B copies, 1 / B of the work)
     const int nc = mode == MODE_TRANSLATE && h->ctx_single ? 1 : B;
     // refresh the 4-channel copy of the frames in use (what the cin = 3 loaders read)
-    if (use_dc3(h)) {}
+    if (h->rt.direct3) {}
     else if (mode == MODE_TRAIN) pack_c4(h, h->img, 3ll * B * h->H * h->W);
     else pack_c4(h, h->img + B * npi, (mode == MODE_ENCODE ? 1ll : 2ll) * B * h->H * h->W);
     // (inside a captured translate the second branch starts ~70 us behind the first whichever chain is issued first, or layer by layer --
@@ -624,46 +778,15 @@ void forward(ctx_handle* h, int B, Mode mode) {
     fc_layer(h, "deconv/d_h0_lin", km(h->Z, F, nd, F), nd, F, h->Wp("deconv/d_h0_lin/Matrix"), h->Wp("deconv/d_h0_lin/bias"), (int)h->D0, 1, h->dz);
     const float* dec = h->dz;
     for (int k = 1; k <= 4; ++k) {
-        const int hs = h->hh[5 - k], ws = h->ww[5 - k];      // input grid of d_hk
-        const int c1 = (16 * d) >> k, c2 = c1;                // decoder stream | ctx skip h_{4-k}
-        const int ca = k < 4 ? (8 * d) >> k : 3;
+        const int c1 = (16 * d) >> k;                         // decoder stream | ctx skip h_{4-k}, c1 channels each
         const std::string nm_ = "deconv/d_h" + std::to_string(k);
         const float* w = h->Wp((nm_ + "/w").c_str());
         const float* b = h->Wp((nm_ + "/biases").c_str());
-        const float* skip = h->c[4 - k];
-        const double fl = 2.0 * nd * hs * ws * 25 * (c1 + c2) * ca, uf = tap_frac(2 * hs, 2 * ws, 5, 2);
-        if (k < 4) {
-            const int R = nd * hs * ws;
-            const bool wide = h->cfg.precision == CTX_PREC_F32 && wconvt_ok(hs, ws, c1, c2, ca, nd);
-            // starved inference launches (the reward hook's 25 frames): one plain product + a gather (launch.h: convt_product)
-            // (measured at 25 frames: 4x4 grid 130 -> 87 us; the 8x8 / 16x16 grids 75 / 73 -> 87 / 85 us, so those stay on the tiles)
-            const bool prod = mode != MODE_TRAIN && nd <= PP_IMG && hs * ws <= 16 && h->PP && (h->opt.v[OPT_WCONVT] & 16) && ca % 4 == 0 && (c1 + c2) % KC == 0 && c1 % KC == 0;
-            ProfScope ps(h, nm_ + " fwd", prod ? K_CONVT3P : wide ? K_WCONVT : K_CONVT, fl, uf);
-            Epi ep;
-            ep.out1 = h->e[k]; ep.ld1 = ca; ep.bias = b; ep.lrelu = 1;
-            if (prod) {
-                convt_product(h->stream, KmCat2{dec, c1, c1, skip, c2, nc, hs * ws, R, (c1 + c2) / KC, g_zeros}, w, c1 + c2, ca, h->PP, R, ws_of(h));
-                convt_gather(h->stream, h->PP, b, h->e[k], nd, hs, ws, ca, 1);
-            } else if (wide) wconvt_fwd(h->stream, dec, c1, skip, c2, nc, nd, hs, ws, w, ca, ep, ws_of(h));
-            else if (use_q(nd) && hs * ws >= q_minpos(h)) convt_fwd_q(h->stream, KmConvTGatherQ{dec, c1, c1, skip, c2, nc, make_tposgeo(hs, ws, 5, 1, (c1 + c2) / KC), nd, g_zeros},
-                                       KmConvTWeightsQ{w, ca, c1 + c2, 5, g_zeros}, ep, ca, ws_of(h));
-            else convt_fwd(h->stream, KmConvTGather{dec, c1, c1, skip, c2, nc, hs, ws, (c1 + c2) / KC, R, g_zeros},
-                           KmConvTWeights{w, ca, c1 + c2, (c1 + c2) / KC, g_zeros}, ep, R, ca, ws_of(h));
-            dec = h->e[k];
-        } else {
-            const int R = nd * hs * ws;
-            // (the same for d_h4 at <= PP_IMG images: the direct kernel offers 200 two-wave tiles to 256 CUs there, 54 us at 25 frames)
-            const bool prod3 = mode != MODE_TRAIN && nd <= PP_IMG && (h->opt.v[OPT_WCONVT] & 16) && (c1 + c2) % KC == 0 && c1 % KC == 0;
-            if (d_h4_direct(h, c1, c2, hs, ws, 2) && !prod3) {
-                ProfScope ps(h, nm_ + " fwd", K_CONVT3D, fl, uf);
-                convt3_direct(h->stream, dec, c1, skip, c2, nc, nd, hs, ws, 2, w, b, h->out);
-            } else {
-                { ProfScope ps(h, nm_ + " fwd product", K_CONVT3P, fl, uf);
-                  convt3_product(h->stream, KmCat2{dec, c1, c1, skip, c2, nc, hs * ws, R, (c1 + c2) / KC, g_zeros}, w, c1 + c2, h->P3, R, ws_of(h)); }
-                { ProfScope ps(h, nm_ + " fwd gather", K_CONVT3, 0.0);
-                  convt3_gather(h->stream, h->P3, b, h->out, nd, hs, ws); }
-            }
-        }
+        const Cat in{dec, c1, h->c[4 - k], c1, nc};
+        if (k == 4) { convt3(h, nm_, skip_geo(h, 0), in, nd, w, b, h->out, mode != MODE_TRAIN); break; }
+        const int ca = (8 * d) >> k;
+        convt(h, nm_ + " fwd", skip_geo(h, 4 - k), in, nd, w, ca, epi_act(h->e[k], ca, b, 1), false, mode != MODE_TRAIN);
+        dec = h->e[k];
     }
 }
 
@@ -679,64 +802,26 @@ void backward(ctx_handle* h, int B, int sim_batch) {
     float* tgt_z = h->Z + (int64_t)B * F;
     float* src_z = h->Z + 2ll * B * F;
     seed_grads(h, B, sim_batch, h->dsim2, F, 0);
-    if (!use_dc3(h)) pack_c4(h, h->dout, 2ll * B * h->H * h->W);
+    if (!h->rt.direct3) pack_c4(h, h->dout, 2ll * B * h->H * h->W);
 
     // ---- decoder, both passes at once (batch 2B)
     const float* dy = h->dout;
     for (int k = 4; k >= 1; --k) {
-        const int hs = h->hh[5 - k], wsm = h->ww[5 - k], hb = 2 * hs, wb = 2 * wsm;
-        const int c1 = (16 * d) >> k, c2 = c1, cb = c1 + c2;
+        const int c1 = (16 * d) >> k;
         const int ca = k < 4 ? (8 * d) >> k : 3;
-        const int R = 2 * B * hs * wsm;
+        const Geo g = skip_geo(h, 4 - k);
         const std::string nm_ = "deconv/d_h" + std::to_string(k);
-        const float* w = h->Wp((nm_ + "/w").c_str());
         const float* dec_in = k > 1 ? h->e[k - 1] : h->dz;      // decoder half of the concat input
         float* d_dec = k > 1 ? h->dE[k - 1] : h->dDz;
-        const double fl = 2.0 * R * 25 * cb * ca, uf = tap_frac(hb, wb, 5, 2);
-        NmWgradSmall2 small{dec_in, c1, c1, h->c[4 - k], c2, B, cb, hs * wsm, make_pixdiv(1, hs * wsm).ws_sh, R, g_zeros};
-        Epi eg;
-        eg.out1 = h->Gp((nm_ + "/w").c_str()); eg.ld1 = cb;
+        const bool direct = ca == 3 && h->rt.direct3;
+        { Side sd(h, LANE_DW);
+          wgrad(h, nm_, g, dy, ca, Cat{dec_in, c1, h->c[4 - k], c1, B}, 2 * B, h->Gp((nm_ + "/w").c_str()), h->Gp((nm_ + "/biases").c_str()), direct); }
         // input gradient = SAME stride-2 conv of dy with the same filter read as [5,5,ca,cb]; cols < c1
         // are the decoder stream (masked by its lrelu), cols >= c1 the ctx skip of this pass
         Epi ed;
         ed.out1 = d_dec; ed.ld1 = c1; ed.nsplit = c1; ed.mask = dec_in; ed.ldm = c1;
-        ed.out2 = h->dSk[4 - k]; ed.ld2 = c2;
-        if (ca == 3 && use_dc3(h)) {
-            { Side sd(h, LANE_DW);
-              bias_grad(h, nm_, dy, (int64_t)2 * B * hb * wb, ca, h->Gp((nm_ + "/biases").c_str()));
-              DcWgrad Wg{};
-              Wg.big = dy; Wg.ldb = 3; Wg.CA = 3; Wg.s1 = dec_in; Wg.ld1 = c1; Wg.c1 = c1; Wg.s2 = h->c[4 - k]; Wg.ld2 = c2; Wg.nmod2 = B; Wg.CB = cb;
-              Wg.hb = hb; Wg.wb = wb; Wg.hs = hs; Wg.ws = wsm; Wg.nimg = 2 * B; Wg.S = 2; Wg.pad = 1; Wg.out = eg.out1;
-              ProfScope ps(h, nm_ + " dw", dw_label(Wg), fl, uf);
-              dconv_wgrad(h->stream, Wg, h->slab, h->slab_floats); }
-            if (c3conv_ok(hb, wb, 2, cb, ed)) {
-                ProfScope ps(h, nm_ + " dx", K_C3CONV, fl, uf);
-                c3conv(h->stream, dy, 2 * B, hb, wb, 2, w, cb, ed);
-            } else {
-              ProfScope ps(h, nm_ + " dx", K_DCFWD, fl, uf);
-              DcFwd D{};
-              D.x1 = dy; D.ld1 = 3; D.c1 = 3; D.CI = 3; D.hin = hb; D.win = wb; D.nimg = 2 * B; D.w = w; D.wmode = 0; D.N = cb; D.ep = ed; D.wp = h->wpack; D.pc = &h->pack;
-              dconv_conv(h->stream, D, 2, 1); }
-        } else if (ca == 3) {
-            { Side sd(h, LANE_DW);
-              bias_grad(h, nm_, dy, (int64_t)2 * B * hb * wb, ca, h->Gp((nm_ + "/biases").c_str()));
-              ProfScope ps(h, nm_ + " dw", K_C3WGRAD, fl, uf); conv3_wgrad2(h->stream, NmC3WgradBig{c4of(h, dy), hb, wb, make_pixdiv(hs, wsm), R, g_zeros}, small, eg, cb, ws_of(h)); }
-            { ProfScope ps(h, nm_ + " dx", K_C3FWD, fl, uf); conv3_fwd(h->stream, KmC3Gather{c4of(h, dy), hb, wb, hs, wsm, R, g_zeros}, NmC3Weights{w, cb, g_zeros}, ed, R, cb, ws_of(h)); }
-        } else {
-            { Side sd(h, LANE_DW);
-              bias_grad(h, nm_, dy, (int64_t)2 * B * hb * wb, ca, h->Gp((nm_ + "/biases").c_str()));
-              ProfScope ps(h, nm_ + " dw", K_WGRAD, fl, uf);
-              if (rect_ok(2 * B) && rect_ok(B)) {
-                  const RectGeo rg = make_rect(2 * B, hs, wsm, hb, wb, 2, 1, 5);
-                  conv_wgrad2_r(h->stream, NmWgradBigR{dy, ca, ca, rg, g_zeros}, NmWgradSmall2R{dec_in, c1, c1, h->c[4 - k], c2, B, cb, rg, g_zeros}, eg, ca, cb, ws_of(h));
-              } else if (patch_ok(hs, wsm)) {
-                  const PatchGeo pg = make_patch(2 * B, hs, wsm);
-                  conv_wgrad2_p(h->stream, NmWgradBigP{dy, ca, ca, wb, pg, g_zeros}, NmWgradSmall2P{dec_in, c1, c1, h->c[4 - k], c2, B, cb, pg, g_zeros}, eg, ca, cb, ws_of(h));
-              } else conv_wgrad2(h->stream, NmWgradBig{dy, ca, ca, hb, wb, make_pixdiv(hs, wsm), R, g_zeros}, small, eg, ca, cb, ws_of(h)); }
-            { ProfScope ps(h, nm_ + " dx", K_CONV, fl, uf);
-              if (use_q(2 * B)) conv_fwd_q(h->stream, KmConvGatherQ{dy, ca, make_posgeo(hs, wsm, hb, wb, 2, 1, 5, ca / KC), 2 * B, g_zeros}, NmConvWeightsQ{w, ca, cb, 5, g_zeros}, ed, cb, ws_of(h));
-              else conv_fwd(h->stream, KmConvGather{dy, ca, hb, wb, hs, wsm, ca / KC, R, g_zeros}, nm(w, cb, cb, 25 * ca), ed, R, cb, ws_of(h)); }
-        }
+        ed.out2 = h->dSk[4 - k]; ed.ld2 = c1;
+        conv(h, nm_ + " dx", g, dy, ca, 2 * B, h->Wp((nm_ + "/w").c_str()), 2 * c1, ed, direct);
         dy = d_dec;
     }
     // d_h0_lin: input Z[0:2B] = [trans_z | tgt_z]; simloss adds +-c(trans_z - tgt_z) to its gradient
@@ -783,59 +868,23 @@ void backward(ctx_handle* h, int B, int sim_batch) {
             else if (!h->bucket_fn) adam_early(h, lin0, lin1, dw_lane);
         }
         for (int k = 3; k >= 0; --k) {
-            const int hb = h->hh[k], wb = h->ww[k], hs = hb / 2, wsm = wb / 2;
+            const Geo g = skip_geo(h, k);
             const int ca = k ? d << (k - 1) : 3, cb = d << k;
-            const int R = nimg * hs * wsm;
-            const float* xin = k ? act[k - 1] : x;
             const std::string ln = scn + "/h" + std::to_string(k) + "_conv";
-            const double fl = 2.0 * R * 25 * ca * cb, uf = tap_frac(hb, wb, 5, 2);
-            NmWgradSmall small{dA[k], cb, cb, nullptr, 0, 1, cb, hs * wsm, make_pixdiv(1, hs * wsm).ws_sh, R, g_zeros};
-            Epi eg;
-            eg.out1 = sc.gw[k]; eg.ld1 = cb;
+            { Side sd(h, dw_lane);
+              wgrad(h, ln, g, k ? act[k - 1] : x, ca, Cat{dA[k], cb}, nimg, sc.gw[k], sc.gb[k], ca == 3 && h->rt.direct3); }
             if (k == 0) {
-                {
-                Side sd(h, dw_lane);
-                if (!use_dc3(h)) bias_grad(h, ln, dA[k], R, cb, sc.gb[k]);       // (dconv_wgrad returns the column sums of its small operand too)
-                if (use_dc3(h)) {
-                    DcWgrad Wg{};
-                    Wg.big = xin; Wg.ldb = 3; Wg.CA = 3; Wg.s1 = dA[k]; Wg.ld1 = cb; Wg.c1 = cb; Wg.CB = cb;
-                    Wg.hb = hb; Wg.wb = wb; Wg.hs = hs; Wg.ws = wsm; Wg.nimg = nimg; Wg.S = 2; Wg.pad = 1; Wg.out = eg.out1;
-                    Wg.db = sc.gb[k];
-                    ProfScope ps(h, ln + " dw", dw_label(Wg), fl, uf);
-                    dconv_wgrad(h->stream, Wg, h->slab, h->slab_floats);
-                } else {
-                    ProfScope ps(h, ln + " dw", K_C3WGRAD, fl, uf);
-                    conv3_wgrad(h->stream, NmC3WgradBig{c4of(h, xin), hb, wb, make_pixdiv(hs, wsm), R, g_zeros}, small, eg, cb, ws_of(h));
-                }
-                }
-                if (h->vjp) frame_grads3(h, dA[0], cb, slot0, nimg, hs, wsm, 2, sc.w[0]);   // (the training step has no frame gradient)
+                if (h->vjp) frame_grads3(h, dA[0], cb, slot0, nimg, g.hs, g.ws, 2, sc.w[0]);   // (the training step has no frame gradient)
                 break;
             }
-            { Side sd(h, dw_lane);
-              bias_grad(h, ln, dA[k], R, cb, sc.gb[k]);
-              ProfScope ps(h, ln + " dw", K_WGRAD, fl, uf);
-              if (rect_ok(nimg)) {
-                  const RectGeo rg = make_rect(nimg, hs, wsm, hb, wb, 2, 1, 5);
-                  conv_wgrad_r(h->stream, NmWgradBigR{xin, ca, ca, rg, g_zeros}, NmWgradSmallR{dA[k], cb, cb, rg, g_zeros}, eg, ca, cb, ws_of(h));
-              } else if (patch_ok(hs, wsm)) {
-                  const PatchGeo pg = make_patch(nimg, hs, wsm);
-                  conv_wgrad_p(h->stream, NmWgradBigP{xin, ca, ca, wb, pg, g_zeros}, NmWgradSmallP{dA[k], cb, cb, pg, g_zeros}, eg, ca, cb, ws_of(h));
-              } else conv_wgrad(h->stream, NmWgradBig{xin, ca, ca, hb, wb, make_pixdiv(hs, wsm), R, g_zeros}, small, eg, ca, cb, ws_of(h)); }
             // input gradient = conv2d_transpose of dA[k] with the same filter read as [5,5,ca,cb]
             Epi ed;
             ed.out1 = dA[k - 1]; ed.ld1 = ca; ed.mask = act[k - 1]; ed.ldm = ca;
             if (with_skips) {
                 ed.add1 = h->dSk[k - 1]; ed.lda1 = ca;
-                ed.add2 = h->dSk[k - 1] + (int64_t)B * hb * wb * ca; ed.lda2 = ca;
+                ed.add2 = h->dSk[k - 1] + (int64_t)B * g.hb * g.wb * ca; ed.lda2 = ca;
             }
-            // (split-bf16 mode: the exact-f32 kernel only where it is the faster one -- the 16x16 grids' few-channel input gradients)
-            const bool wide = (h->cfg.precision == CTX_PREC_F32 || hs == 16) && wconvt_ok(hs, wsm, cb, 0, ca, nimg);
-            ProfScope ps(h, ln + " dx", wide ? K_WCONVT : K_CONVT, fl, uf);
-            if (wide) wconvt_fwd(h->stream, dA[k], cb, nullptr, 0, 1, nimg, hs, wsm, sc.w[k], ca, ed, ws_of(h));
-            else if (use_q(nimg) && hs * wsm >= q_minpos(h)) convt_fwd_q(h->stream, KmConvTGatherQ{dA[k], cb, cb, nullptr, 0, 1, make_tposgeo(hs, wsm, 5, 1, cb / KC), nimg, g_zeros},
-                                         KmConvTWeightsQ{sc.w[k], ca, cb, 5, g_zeros}, ed, ca, ws_of(h));
-            else convt_fwd(h->stream, KmConvTGather{dA[k], cb, cb, nullptr, 0, 1, hs, wsm, cb / KC, R, g_zeros}, KmConvTWeights{sc.w[k], ca, cb, cb / KC, g_zeros},
-                           ed, R, ca, ws_of(h));
+            convt(h, ln + " dx", g, Cat{dA[k], cb}, nimg, sc.w[k], ca, ed, false, false);
         }
     };
     // `conv` on [tgt | src]: code gradients are rows [B, 3B) of dZ; hz_lin has an lrelu

@@ -86,14 +86,28 @@ struct GenState {
     int in_ch(int k) const { return k ? cp[k - 1] : C0; }
 };
 
+// How a handle routes its conv-type layers (ctx_engine.cpp: conv / convt / wgrad / convt3): every rule in which ContextSkipNew and the
+// table-driven models differ, fixed at create (set_routing, which gives the reason for each value).
+struct Routing {
+    int swz = 0;                 // XCD-swizzle bits of the implicit-GEMM launches (SplitWs::swz)
+    bool wconvt = false;         // wconvt.hip on 5x5 stride-2 transposed convs
+    bool patch = false;          // patch-ordered filter gradients (5x5 stride 2 on power-of-two grids)
+    bool starved = false;        // inference launches of <= PP_IMG images as one product + a gather (convt_product; d_h4's product)
+    int q_minpos = 0;            // smallest grid (positions) of a stride-2 position-major transposed conv
+    bool h4_direct_bf16 = false; // d_h4 on its direct kernel (convt3.hip) in split-bf16 mode too
+    bool direct3 = false;        // 3-channel layers on the direct kernels of dconv.h (the frames / d out read as [pixel][3], no 4-channel copies)
+};
+
 }  // namespace ctxi
 using ctxi::GenState;
 using ctxi::ParamInfo;
+using ctxi::Routing;
 
 struct ctx_handle {
     ctx_config cfg{};
     Options opt{};               // this handle's switches (options.h; ctx_set_option): the process defaults (environment) at ctx_create
     GenState* gen = nullptr;     // CTX_VARIANT_REAL / CTX_VARIANT_INCEPTION2 state (ctxtrans_gen.inc)
+    Routing rt{};                // conv-layer routing rules of this variant (set_routing, at create)
     int Fp = 0;                  // row stride of the code buffers Z / dZ (featsize, or featsize padded to 32 for REAL)
     int device = 0;
     hipStream_t stream = nullptr;
@@ -237,6 +251,7 @@ void backward(ctx_handle* h, int B, int sim_batch);
 int adam_step(ctx_handle* h, float lr);
 int gen_alloc(ctx_handle* h);
 int alloc_buffers(ctx_handle* h);
+void set_routing(ctx_handle* h);
 bool use_lanes(const ctx_handle* h);
 void adam_begin(ctx_handle* h, float lr);
 void adam_end(ctx_handle* h);

@@ -22,6 +22,8 @@
 // The C ABI keeps the reference's shapes: ctx_set_params / get_* scatter and gather through `real2pad`.
 // tf.nn.dropout(., keep_prob) in ContextAEReal with the module-level keep_prob = 1.0 (arm_shaping.py:1476) is the identity.
 // Filter / bias gradients run on the LANE_DW side stream beside the input-gradient chain (Side scopes below).
+// Every layer launches through the layer helpers of ctx_engine.cpp (fc_* and conv / convt / wgrad / convt3, with this model's routing
+// record ctx_handle::rt); this file says which buffers each layer reads and writes, not which kernel runs it.
 
 namespace ctxi {
 
@@ -180,51 +182,11 @@ int gen_alloc(ctx_handle* h) {
     if (r.C0 == 3) TRY(dev_alloc(h, &h->dout4, 2 * B * h->npi / 3 * 4));
     if (r.C0 == 3 && !d_h4_direct(h, r.cp[0], r.cp[0], r.gh[0], r.gw[0], r.se[0]))
         TRY(dev_alloc(h, &h->P3, 2 * B * HW * P3_LD, false));   // written by an epilogue, read by the gather: 64-bit indexing
-    TRY(dev_alloc(h, &h->scratch, std::max<int64_t>(4 * LOSS_BLOCKS, (int64_t)COLSUM_SPLITS * maxc)));
-    h->slab_floats = r.C0 == 3 ? 8ll << 20 : 48ll << 20;   // wide layers on tiny grids live on split-K
-    TRY(dev_alloc(h, &h->slab, h->slab_floats));
-    TRY(dev_alloc(h, &h->wpack, DC_WPACK_FLOATS));
-    for (int l = 0; l < ctx_handle::NLANE; ++l) {             // side lanes (filter / bias gradients run beside the dx chain)
-        TRY(dev_alloc(h, &h->slabL[l], h->slab_floats));
-        TRY(dev_alloc(h, &h->scratchL[l], std::max<int64_t>(4 * LOSS_BLOCKS, (int64_t)COLSUM_SPLITS * maxc)));
-        TRY(dev_alloc(h, &h->wpackL[l], DC_WPACK_FLOATS));
-    }
-    TRY(dev_alloc(h, &h->scalars, 4));
-    TRY(dev_alloc(h, &h->zeros, 64));
-    if (hipMemset(h->zeros, 0, 64 * sizeof(float)) != hipSuccess) return fail(h, CTX_E_DEVICE, "hipMemset(zeros)");
-    return CTX_OK;
+    return alloc_tail(h, r.C0 == 3 ? 8ll << 20 : 48ll << 20, maxc);   // (wide layers on tiny grids live on split-K: the larger slab)
 }
 
-// conv2d + bias + lrelu over `nimg` images: x [nimg, hb, wb, ca] -> y [nimg, hb/s, wb/s, cb]
-void gen_conv(ctx_handle* h, const std::string& name, const float* x, int nimg, int hb, int wb, int ca, int s, int pad, int K, const float* w,
-              const float* b, float* y, int cb) {
-    const GenState& r = *h->gen;
-    const int hs = hb / s, ws = wb / s, R = nimg * hs * ws, K2 = K * K;
-    Epi ep;
-    ep.out1 = y; ep.ld1 = cb; ep.bias = b; ep.lrelu = 1;
-    const bool c3 = r.narrow && ca == 3 && K == 5 && pad == (s == 2 ? 1 : 2) && c3conv_ok(hb, wb, s, cb, ep);
-    ProfScope ps(h, name + " fwd", c3 ? K_C3CONV : r.narrow ? K_DCFWD : ca == 3 ? K_C3FWD : K_CONV, 2.0 * R * K2 * ca * cb, tap_frac_p(hb, wb, hs, ws, K, s, pad));
-    if (c3) c3conv(h->stream, x, nimg, hb, wb, s, w, cb, ep);
-    else if (r.narrow) {
-        DcFwd P{};
-        P.x1 = x; P.ld1 = ca; P.c1 = ca; P.CI = ca; P.hin = hb; P.win = wb; P.nimg = nimg;
-        P.w = w; P.wmode = 0; P.N = cb; P.ep = ep; P.wp = h->wpack; P.pc = &h->pack;
-        dconv_conv(h->stream, P, s, pad);
-    } else if (ca == 3) {
-        KmC3Gather a{c4of(h, x), hb, wb, hs, ws, R, g_zeros};
-        a.s = s; a.pad = pad;
-        conv3_fwd(h->stream, a, NmC3Weights{w, cb, g_zeros}, ep, R, cb, ws_of(h));
-    } else {
-        if (use_q(nimg)) {                                   // position-major: only the taps inside the grid (on a 1x1 grid: 1 of K*K)
-            conv_fwd_q(h->stream, KmConvGatherQ{x, ca, make_posgeo(hs, ws, hb, wb, s, pad, K, ca / KC), nimg, g_zeros},
-                       NmConvWeightsQ{w, ca, cb, K, g_zeros}, ep, cb, ws_of(h));
-            return;
-        }
-        KmConvGather a{x, ca, hb, wb, hs, ws, ca / KC, R, g_zeros};
-        a.s = s; a.pad = pad; a.K = K;
-        conv_fwd(h->stream, a, nm(w, cb, cb, K2 * ca), ep, R, cb, ws_of(h));
-    }
-}
+// encoder layer k (decoder d_h(4-k) mirrors it): grid in = grid out * effective stride
+Geo gen_geo(const GenState& r, int k) { return Geo{r.gh[k] * r.se[k], r.gw[k] * r.se[k], r.gh[k], r.gw[k], r.se[k], r.pd[k], r.Kk[k]}; }
 
 // encoder `set` over images [img0, img0 + nimg) of the stacked batch [tgt | src | ctx]
 // dropout is part of the TRAINING graph only (keep_prob is fed as 1.0 by the sampler and by validation: ablations.py:556)
@@ -249,11 +211,11 @@ void gen_encoder_fwd(ctx_handle* h, int B, int set, int img0, int nimg, bool dro
     const float* P = h->arena;
     const std::string sc = set == 1 ? "conv_context" : "conv";
     const float* in = h->img + (int64_t)img0 * h->npi;
-    int hb = h->H, wb = h->W;
     for (int k = 0; k < 4; ++k) {
         float* y = r.a[k] + (int64_t)img0 * r.gh[k] * r.gw[k] * r.cp[k];
-        gen_conv(h, sc + "/h" + std::to_string(k) + "_conv", in, nimg, hb, wb, r.in_ch(k), r.se[k], r.pd[k], r.Kk[k], P + r.w[set][k], P + r.b[set][k], y, r.cp[k]);
-        in = y; hb = r.gh[k]; wb = r.gw[k];
+        conv(h, sc + "/h" + std::to_string(k) + "_conv fwd", gen_geo(r, k), in, r.in_ch(k), nimg, P + r.w[set][k], r.cp[k],
+             epi_act(y, r.cp[k], P + r.b[set][k], 1), r.narrow);
+        in = y;
     }
     if (!fc) return;                                              // (the caller runs the FC layers: rchain_fwd)
     const int Fp = r.Fp, D0p = (int)r.D0p;
@@ -279,7 +241,7 @@ void gen_forward(ctx_handle* h, int B, Mode mode) {
     GenState& r = *h->gen;
     const float* P = h->arena;
     const int Fp = r.Fp, D0p = (int)r.D0p;
-    if (r.C0 == 3 && !r.narrow) {                                             // refresh the 4-channel copy of the frames in use
+    if (r.C0 == 3 && !h->rt.direct3) {                                        // refresh the 4-channel copy of the frames in use
         if (mode == MODE_ENCODE) pack_c4(h, h->img + (int64_t)B * h->npi, (int64_t)B * h->H * h->W);
         else pack_c4(h, h->img, 3ll * B * h->H * h->W);
     }
@@ -332,79 +294,41 @@ void gen_forward(ctx_handle* h, int B, Mode mode) {
     const float* dec = r.dz;
     if (drop) { ew_mul(h->stream, r.dzd, D0p, r.dz, D0p, r.dM[6], D0p, nd, D0p); dec = r.dzd; }    // site 6: reshape(z_) * M6 feeds d_h1 (:1661)
     for (int k = 1; k <= 4; ++k) {
-        const int gi = 4 - k;                                   // encoder layer whose output is the skip
-        const int hs = r.gh[gi], ws = r.gw[gi], s = r.se[gi], R = nd * hs * ws, ch = r.cp[gi], co = r.in_ch(gi);
-        const int Kd = r.Kk[gi], K2 = Kd * Kd;                    // d_hk mirrors encoder layer 4 - k (arm_shaping.py:1841-1857)
-        const float* skip = r.a[gi] + 2ll * B * hs * ws * ch;     // ctx third of the encoder batch
+        const int gi = 4 - k;                                   // d_hk mirrors encoder layer 4 - k (arm_shaping.py:1841-1857), whose output is the skip
+        const Geo g = gen_geo(r, gi);
+        const int ch = r.cp[gi], co = r.in_ch(gi);
+        const Cat in{dec, ch, r.a[gi] + 2ll * B * g.hs * g.ws * ch, ch, nc};     // [decoder | ctx third of the encoder batch]
         const std::string nm_ = "deconv/d_h" + std::to_string(k);
-        const float* w = P + r.dw[k];
-        const float* b = P + r.db[k];
-        const double fl = 2.0 * R * K2 * (2 * ch) * co, uf = tap_frac_p(hs * s, ws * s, hs, ws, Kd, s, r.pd[gi]);
-        if (k == 4 && co == 3 && d_h4_direct(h, ch, ch, hs, ws, s)) {  // 3 output channels: one pass on the vector ALUs (convt3.hip)
-            ProfScope ps(h, nm_ + " fwd", K_CONVT3D, fl, uf);
-            convt3_direct(h->stream, dec, ch, skip, ch, nc, nd, hs, ws, s, w, b, h->out);
-            break;
-        }
-        if (k == 4 && co == 3) {                                 // ... or scatter product + gather (split-bf16 mode)
-            { ProfScope ps(h, nm_ + " fwd product", K_CONVT3P, fl, uf);
-              convt3_product_t(h->stream, KmCat2{dec, ch, ch, skip, ch, nc, hs * ws, R, 2 * ch / KC, g_zeros}, w, 2 * ch, h->P3, R, ws_of(h)); }
-            ProfScope ps(h, nm_ + " fwd gather", K_CONVT3, 0.0);
-            convt3_gather_s1_t(h->stream, h->P3, b, h->out, nd, hs, ws);
-            break;
-        }
-        Epi ep;
-        ep.out1 = k < 4 ? r.e[k] : h->out; ep.ld1 = co; ep.bias = b; ep.lrelu = k < 4;
+        if (k == 4 && co == 3) { convt3(h, nm_, g, in, nd, P + r.dw[k], P + r.db[k], h->out, tr); break; }
+        Epi ep = epi_act(k < 4 ? r.e[k] : h->out, co, P + r.db[k], k < 4);
         if (k == 4 && r.residual) {                              // out = h4 + tgtctx: the ctx frames serve both decoder passes
             ep.add1 = h->img + 2ll * B * h->npi; ep.lda1 = co; ep.add1_mod = (int64_t)B * h->H * h->W;     // (translate with one context frame: the entry points still lay out B copies for this add)
         }
-        ProfScope ps(h, nm_ + " fwd", r.narrow ? K_DCFWD : s == 2 ? K_CONVT : K_CONVT1, fl, uf);
-        if (r.narrow) {
-            DcFwd P{};
-            P.x1 = dec; P.ld1 = ch; P.c1 = ch; P.x2 = skip; P.ld2 = ch; P.nmod2 = nc; P.CI = 2 * ch;
-            P.hin = hs; P.win = ws; P.nimg = nd; P.w = w; P.wmode = 1; P.N = co; P.ep = ep; P.wp = h->wpack; P.pc = &h->pack;
-            if (s == 2) dconv_convt2(h->stream, P); else dconv_convt1(h->stream, P);
-        } else if (s == 2 && use_q(nd)) {
-            convt_fwd_q(h->stream, KmConvTGatherQ{dec, ch, ch, skip, ch, nc, make_tposgeo(hs, ws, Kd, r.pd[gi], 2 * ch / KC), nd, g_zeros},
-                        KmConvTWeightsQ{w, co, 2 * ch, Kd, g_zeros}, ep, co, ws_of(h));
-        } else if (s == 2) {
-            KmConvTGather a{dec, ch, ch, skip, ch, nc, hs, ws, 2 * ch / KC, R, g_zeros};
-            a.K = Kd; a.pb = r.pd[gi];
-            KmConvTWeights bw{w, co, 2 * ch, 2 * ch / KC, g_zeros};
-            bw.K = Kd; bw.pb = r.pd[gi];
-            convt_fwd(h->stream, a, bw, ep, R, co, ws_of(h));
-        } else if (use_q(nd) && hs * ws <= 64) {                 // stride 1, position-major: only the taps inside the (small) grid
-            convt1_fwd_q(h->stream, KmConvT1GatherQ{dec, ch, ch, skip, ch, nc, make_posgeo(hs, ws, hs, ws, 1, Kd - 1 - r.pd[gi], Kd, 2 * ch / KC), nd, g_zeros},
-                         KmConvT1WeightsQ{w, co, 2 * ch, Kd, g_zeros}, ep, co, ws_of(h));
-        } else {
-            KmConvGather a{dec, ch, hs, ws, hs, ws, 2 * ch / KC, R, g_zeros};
-            a.s = 1; a.pad = r.pd[gi]; a.flip = 1; a.x2 = skip; a.ldx2 = ch; a.c1 = ch; a.nmod2 = nc; a.K = Kd;
-            KmConvTWeights bw{w, co, 2 * ch, 2 * ch / KC, g_zeros};
-            bw.flip25 = 1; bw.K = Kd;
-            convt1_fwd(h->stream, a, bw, ep, R, co, ws_of(h));
-        }
+        convt(h, nm_ + " fwd", g, in, nd, P + r.dw[k], co, ep, r.narrow, tr);
         dec = r.e[k];
     }
 }
 
 // VJP frame / feature-map gradients, one launch per image slot [tgt | src | ctx] the caller asked for.  3-channel frames
 // (ContextAEReal): the direct transposed conv of frame_grads3.  Feature maps (ContextAEInception2, C a multiple of 32): the
-// implicit-GEMM dx path of the deeper layers (`dx`), no lrelu'; out = decode + tgtctx adds d out + d out2 to the ctx maps.  The tgt
-// slot adds the recon terms' direct gradient w.r.t. their target (recon_tgt_term) in either case.
-struct GenPart { int img0, nimg, set; bool skips; };   // images [img0, img0 + nimg) of [tgt | src | ctx] through encoder `set`
-template <class DX>
-void gen_frame_grads(ctx_handle* h, int B, const DX& dx) {
+// transposed conv of the deeper layers' input gradients, no lrelu'; out = decode + tgtctx adds d out + d out2 to the ctx maps.  The
+// tgt slot adds the recon terms' direct gradient w.r.t. their target (recon_tgt_term) in either case.
+void gen_frame_grads(ctx_handle* h, int B) {
     const GenState& r = *h->gen;
     if (r.C0 == 3) {
         frame_grads3(h, r.dA[0], r.cp[0], 0, 3 * B, r.gh[0], r.gw[0], r.se[0], h->arena + r.w[0][0]);
         return;
     }
+    const Geo g = gen_geo(r, 0);
     for (int j = 0; j < 3; ++j) {
         float* o = vjp_frame_out(h, j);
         if (!o) continue;
         Epi ed;
         ed.out1 = o; ed.ld1 = r.C0;
         if (j == 2 && r.residual) { ed.add1 = h->dout; ed.lda1 = r.C0; ed.add2 = h->dout + (int64_t)B * h->npi; ed.lda2 = r.C0; }
-        dx(GenPart{j * B, B, j == 2 ? r.nset - 1 : 0, false}, ed, std::string(j == 0 ? "tgt" : j == 1 ? "src" : "ctx") + " frames dx");
+        const float* w = h->arena + r.w[j == 2 ? r.nset - 1 : 0][0];
+        convt(h, std::string(j == 0 ? "tgt" : j == 1 ? "src" : "ctx") + " frames dx", g, Cat{r.dA[0] + (int64_t)j * B * g.hs * g.ws * r.cp[0], r.cp[0]},
+              B, w, r.C0, ed, r.narrow, false);
         if (j == 0) recon_tgt_term(h, o);
     }
 }
@@ -417,84 +341,31 @@ void gen_backward(ctx_handle* h, int B, int sim_batch) {
     const int Fp = r.Fp, D0p = (int)r.D0p, F = h->F;
     const bool drop = gen_drop(h);
     seed_grads(h, B, sim_batch, r.dsim2, Fp, F);
-    if (r.C0 == 3 && !r.narrow) pack_c4(h, h->dout, 2ll * B * h->H * h->W);
+    if (r.C0 == 3 && !h->rt.direct3) pack_c4(h, h->dout, 2ll * B * h->H * h->W);
     // ---- decoder, both passes (2B)
     const float* dy = h->dout;
     for (int k = 4; k >= 1; --k) {
         const int gi = 4 - k;
-        const int hs = r.gh[gi], wsm = r.gw[gi], s = r.se[gi], pad = r.pd[gi], hb = hs * s, wb = wsm * s;
-        const int ch = r.cp[gi], ca = r.in_ch(gi), cb = 2 * ch, R = 2 * B * hs * wsm;
-        const int Kd = r.Kk[gi], K2 = Kd * Kd;
+        const Geo g = gen_geo(r, gi);
+        const int ch = r.cp[gi], ca = r.in_ch(gi);
         const std::string nm_ = "deconv/d_h" + std::to_string(k);
         // (with dropout d_h1 was fed dz * M6: the same sign as dz wherever M6 > 0, so it also serves as the lrelu' reference; the
         // gradient is multiplied by M6 after the launch -- the two factors commute)
         const float* dec_in = k > 1 ? r.e[k - 1] : (drop ? r.dzd : r.dz);
         float* d_dec = k > 1 ? r.dE[k - 1] : r.dDz;
-        const float* skip = r.a[gi] + 2ll * B * hs * wsm * ch;
-        const double fl = 2.0 * R * K2 * cb * ca, uf = tap_frac_p(hb, wb, hs, wsm, Kd, s, pad);
-        { Side sd(h, LANE_DW); bias_grad(h, nm_, dy, (int64_t)2 * B * hb * wb, ca, G + r.db[k]); }
-        NmWgradSmall2 small{dec_in, ch, ch, skip, ch, B, cb, hs * wsm, make_pixdiv(1, hs * wsm).ws_sh, R, g_zeros};
-        Epi eg;
-        eg.out1 = G + r.dw[k]; eg.ld1 = cb;
+        // filter gradient dw[tap][a = deconv output channel][b = channel of [decoder | skip]]
+        { Side sd(h, LANE_DW);
+          wgrad(h, nm_, g, dy, ca, Cat{dec_in, ch, r.a[gi] + 2ll * B * g.hs * g.ws * ch, ch, B}, 2 * B, G + r.dw[k], G + r.db[k], r.narrow); }
+        // input gradient of a conv2d_transpose (any stride) = the SAME conv2d of dy with the filter read [K,K,ca,cb]
         Epi ed;
         ed.out1 = d_dec; ed.ld1 = ch; ed.nsplit = ch; ed.mask = dec_in; ed.ldm = ch; ed.out2 = r.dSk[gi]; ed.ld2 = ch;
-        if (r.narrow) {
-            {   // filter gradient dw[tap][a = deconv output channel][b = channel of [decoder | skip]]
-                Side sd(h, LANE_DW);
-                DcWgrad W{};
-                W.big = dy; W.ldb = ca; W.CA = ca; W.s1 = dec_in; W.ld1 = ch; W.c1 = ch; W.s2 = skip; W.ld2 = ch; W.nmod2 = B; W.CB = cb;
-                W.hb = hb; W.wb = wb; W.hs = hs; W.ws = wsm; W.nimg = 2 * B; W.S = s; W.pad = pad; W.out = eg.out1;
-                ProfScope ps(h, nm_ + " dw", dw_label(W), fl, uf);
-                dconv_wgrad(h->stream, W, h->slab, h->slab_floats);
-            }
-            // input gradient of a conv2d_transpose (any stride) = the SAME conv2d of dy with the filter read [5,5,ca,cb]
-            const bool c3 = ca == 3 && Kd == 5 && pad == (s == 2 ? 1 : 2) && c3conv_ok(hb, wb, s, cb, ed);
-            ProfScope ps(h, nm_ + " dx", c3 ? K_C3CONV : K_DCFWD, fl, uf);
-            if (c3) c3conv(h->stream, dy, 2 * B, hb, wb, s, P + r.dw[k], cb, ed);
-            else {
-                DcFwd D{};
-                D.x1 = dy; D.ld1 = ca; D.c1 = ca; D.CI = ca; D.hin = hb; D.win = wb; D.nimg = 2 * B;
-                D.w = P + r.dw[k]; D.wmode = 0; D.N = cb; D.ep = ed; D.wp = h->wpack; D.pc = &h->pack;
-                dconv_conv(h->stream, D, s, pad);
-            }
-        } else if (ca == 3) {
-            NmC3WgradBig big{c4of(h, dy), hb, wb, make_pixdiv(hs, wsm), R, g_zeros};
-            big.s = s; big.pad = pad;
-            { Side sd(h, LANE_DW); ProfScope ps(h, nm_ + " dw", K_C3WGRAD, fl, uf); conv3_wgrad2(h->stream, big, small, eg, cb, ws_of(h)); }
-            KmC3Gather ga{c4of(h, dy), hb, wb, hs, wsm, R, g_zeros};
-            ga.s = s; ga.pad = pad;
-            ProfScope ps(h, nm_ + " dx", K_C3FWD, fl, uf);
-            conv3_fwd(h->stream, ga, NmC3Weights{P + r.dw[k], cb, g_zeros}, ed, R, cb, ws_of(h));
-        } else {
-            {
-                Side sd(h, LANE_DW);
-                ProfScope ps(h, nm_ + " dw", K_WGRAD, fl, uf);
-                if (rect_ok(2 * B) && rect_ok(B)) {
-                    const RectGeo rg = make_rect(2 * B, hs, wsm, hb, wb, s, pad, Kd);
-                    conv_wgrad2_r(h->stream, NmWgradBigR{dy, ca, ca, rg, g_zeros}, NmWgradSmall2R{dec_in, ch, ch, skip, ch, B, cb, rg, g_zeros}, eg, ca, cb, ws_of(h));
-                } else {
-                    NmWgradBig big{dy, ca, ca, hb, wb, make_pixdiv(hs, wsm), R, g_zeros};
-                    big.s = s; big.pad = pad; big.K = Kd;
-                    conv_wgrad2(h->stream, big, small, eg, ca, cb, ws_of(h));
-                }
-            }
-            // input gradient of a conv2d_transpose (any stride) = the SAME conv2d of dy with the filter read [K,K,ca,cb]
-            ProfScope ps(h, nm_ + " dx", K_CONV, fl, uf);
-            if (use_q(2 * B)) {
-                conv_fwd_q(h->stream, KmConvGatherQ{dy, ca, make_posgeo(hs, wsm, hb, wb, s, pad, Kd, ca / KC), 2 * B, g_zeros},
-                           NmConvWeightsQ{P + r.dw[k], ca, cb, Kd, g_zeros}, ed, cb, ws_of(h));
-            } else {
-                KmConvGather ga{dy, ca, hb, wb, hs, wsm, ca / KC, R, g_zeros};
-                ga.s = s; ga.pad = pad; ga.K = Kd;
-                conv_fwd(h->stream, ga, nm(P + r.dw[k], cb, cb, K2 * ca), ed, R, cb, ws_of(h));
-            }
-        }
+        conv(h, nm_ + " dx", g, dy, ca, 2 * B, P + r.dw[k], 2 * ch, ed, r.narrow);
         dy = d_dec;
     }
     if (drop) ew_mul(h->stream, r.dDz, D0p, r.dDz, D0p, r.dM[6], D0p, 2 * B, D0p);       // site 6
     // image ranges.  Weights (and filter gradients): one encoder -> all 3B rows at once; two -> `conv` on [0,2B), `conv_context`
     // on [2B,3B).  Input gradients: rows of tgt/src images have no skip term, ctx rows add both decoder passes' skip gradients.
-    using Part = GenPart;
+    struct Part { int img0, nimg, set; bool skips; };   // images [img0, img0 + nimg) of [tgt | src | ctx] through encoder `set`
     const Part wparts2[2] = {{0, 2 * B, 0, false}, {2 * B, B, 1, true}};
     const Part wparts1[1] = {{0, 3 * B, 0, false}};
     const Part* wparts = r.nset == 2 ? wparts2 : wparts1;
@@ -585,87 +456,27 @@ void gen_backward(ctx_handle* h, int B, int sim_batch) {
     }
     }   // (!chain)
     for (int k = 3; k >= 0; --k) {
-        const int hs = r.gh[k], wsm = r.gw[k], s = r.se[k], pad = r.pd[k], hb = hs * s, wb = wsm * s;
+        const Geo g = gen_geo(r, k);
         const int ca = r.in_ch(k), cb = r.cp[k];
-        const int Ke = r.Kk[k], K2 = Ke * Ke;
         const float* xin = k ? r.a[k - 1] : h->img;
+        auto dyk = [&](const Part& q) { return Cat{r.dA[k] + (int64_t)q.img0 * g.hs * g.ws * cb, cb}; };
         for (int i = 0; i < r.nset; ++i) {
             const Part& q = wparts[i];
-            const int R = q.nimg * hs * wsm;
-            const std::string ln = scn(q.set) + "/h" + std::to_string(k) + "_conv";
-            const float* dyk = r.dA[k] + (int64_t)q.img0 * hs * wsm * cb;
-            const float* xk = xin + (int64_t)q.img0 * hb * wb * ca;
-            const double fl = 2.0 * R * K2 * ca * cb, uf = tap_frac_p(hb, wb, hs, wsm, Ke, s, pad);
             Side sd(h, LANE_DW);                              // this part's bias and filter gradient: off the dx chain
-            if (!r.narrow) bias_grad(h, ln, dyk, R, cb, G + r.b[q.set][k]);      // (narrow: column sums of dy come out of dconv_wgrad, whose small operand dy is)
-            NmWgradSmall small{dyk, cb, cb, nullptr, 0, 1, cb, hs * wsm, make_pixdiv(1, hs * wsm).ws_sh, R, g_zeros};
-            Epi eg;
-            eg.out1 = G + r.w[q.set][k]; eg.ld1 = cb;
-            if (r.narrow) {
-                DcWgrad W{};
-                W.big = xk; W.ldb = ca; W.CA = ca; W.s1 = dyk; W.ld1 = cb; W.c1 = cb; W.CB = cb;
-                W.hb = hb; W.wb = wb; W.hs = hs; W.ws = wsm; W.nimg = q.nimg; W.S = s; W.pad = pad; W.out = eg.out1;
-                W.db = G + r.b[q.set][k];
-                ProfScope ps(h, ln + " dw", dw_label(W), fl, uf);
-                dconv_wgrad(h->stream, W, h->slab, h->slab_floats);
-            } else if (ca == 3) {
-                NmC3WgradBig big{c4of(h, xk), hb, wb, make_pixdiv(hs, wsm), R, g_zeros};
-                big.s = s; big.pad = pad;
-                ProfScope ps(h, ln + " dw", K_C3WGRAD, fl, uf);
-                conv3_wgrad(h->stream, big, small, eg, cb, ws_of(h));
-            } else {
-                ProfScope ps(h, ln + " dw", K_WGRAD, fl, uf);
-                if (rect_ok(q.nimg)) {
-                    const RectGeo rg = make_rect(q.nimg, hs, wsm, hb, wb, s, pad, Ke);
-                    conv_wgrad_r(h->stream, NmWgradBigR{xk, ca, ca, rg, g_zeros}, NmWgradSmallR{dyk, cb, cb, rg, g_zeros}, eg, ca, cb, ws_of(h));
-                } else {
-                    NmWgradBig big{xk, ca, ca, hb, wb, make_pixdiv(hs, wsm), R, g_zeros};
-                    big.s = s; big.pad = pad; big.K = Ke;
-                    conv_wgrad(h->stream, big, small, eg, ca, cb, ws_of(h));
-                }
-            }
+            wgrad(h, scn(q.set) + "/h" + std::to_string(k) + "_conv", g, xin + (int64_t)q.img0 * g.hb * g.wb * ca, ca, dyk(q), q.nimg,
+                  G + r.w[q.set][k], G + r.b[q.set][k], r.narrow);
         }
-        // input gradient = conv2d_transpose of dA[k] with the filter read [K,K,ca,cb], images [q.img0, q.img0 + q.nimg) into ed
-        auto dx = [&](const Part& q, const Epi& ed, const std::string& label) {
-            const int64_t so = (int64_t)q.img0 * hs * wsm * cb;
-            const int Rp = q.nimg * hs * wsm;
-            const float* w = P + r.w[q.set][k];
-            ProfScope ps(h, label, r.narrow ? K_DCFWD : s == 2 ? K_CONVT : K_CONVT1, 2.0 * Rp * K2 * ca * cb, tap_frac_p(hb, wb, hs, wsm, Ke, s, pad));
-            if (r.narrow) {                                      // conv2d_transpose of dA[k] with the filter read [5,5,ca,cb]: n = ca, k = cb
-                DcFwd D{};
-                D.x1 = r.dA[k] + so; D.ld1 = cb; D.c1 = cb; D.CI = cb; D.hin = hs; D.win = wsm; D.nimg = q.nimg;
-                D.w = w; D.wmode = 1; D.N = ca; D.ep = ed; D.wp = h->wpack; D.pc = &h->pack;
-                if (s == 2) dconv_convt2(h->stream, D); else dconv_convt1(h->stream, D);
-            } else if (s == 2 && use_q(q.nimg)) {
-                convt_fwd_q(h->stream, KmConvTGatherQ{r.dA[k] + so, cb, cb, nullptr, 0, 1, make_tposgeo(hs, wsm, Ke, pad, cb / KC), q.nimg, g_zeros},
-                            KmConvTWeightsQ{w, ca, cb, Ke, g_zeros}, ed, ca, ws_of(h));
-            } else if (s == 2) {
-                KmConvTGather ga{r.dA[k] + so, cb, cb, nullptr, 0, 1, hs, wsm, cb / KC, Rp, g_zeros};
-                ga.K = Ke; ga.pb = pad;
-                KmConvTWeights bw{w, ca, cb, cb / KC, g_zeros};
-                bw.K = Ke; bw.pb = pad;
-                convt_fwd(h->stream, ga, bw, ed, Rp, ca, ws_of(h));
-            } else if (use_q(q.nimg) && hs * wsm <= 64) {
-                convt1_fwd_q(h->stream, KmConvT1GatherQ{r.dA[k] + so, cb, cb, nullptr, 0, 1, make_posgeo(hs, wsm, hs, wsm, 1, Ke - 1 - pad, Ke, cb / KC), q.nimg, g_zeros},
-                             KmConvT1WeightsQ{w, ca, cb, Ke, g_zeros}, ed, ca, ws_of(h));
-            } else {
-                KmConvGather ga{r.dA[k] + so, cb, hs, wsm, hs, wsm, cb / KC, Rp, g_zeros};
-                ga.s = 1; ga.pad = pad; ga.flip = 1; ga.K = Ke;
-                KmConvTWeights bw{w, ca, cb, cb / KC, g_zeros};
-                bw.flip25 = 1; bw.K = Ke;
-                convt1_fwd(h->stream, ga, bw, ed, Rp, ca, ws_of(h));
-            }
-        };
         if (k == 0) {                                            // the training step has no gradient w.r.t. the frames / features
-            if (h->vjp) gen_frame_grads(h, B, dx);
+            if (h->vjp) gen_frame_grads(h, B);
             break;
         }
+        // input gradient = conv2d_transpose of dA[k] with the filter read [K,K,ca,cb]
         for (const Part& q : xparts) {
-            const int64_t bo = (int64_t)q.img0 * hb * wb * ca;
+            const int64_t bo = (int64_t)q.img0 * g.hb * g.wb * ca;
             Epi ed;
             ed.out1 = r.dA[k - 1] + bo; ed.ld1 = ca; ed.mask = r.a[k - 1] + bo; ed.ldm = ca;
-            if (q.skips) { ed.add1 = r.dSk[k - 1]; ed.lda1 = ca; ed.add2 = r.dSk[k - 1] + (int64_t)B * hb * wb * ca; ed.lda2 = ca; }
-            dx(q, ed, scn(q.set) + "/h" + std::to_string(k) + "_conv dx");
+            if (q.skips) { ed.add1 = r.dSk[k - 1]; ed.lda1 = ca; ed.add2 = r.dSk[k - 1] + (int64_t)B * g.hb * g.wb * ca; ed.lda2 = ca; }
+            convt(h, scn(q.set) + "/h" + std::to_string(k) + "_conv dx", g, dyk(q), q.nimg, P + r.w[q.set][k], ca, ed, r.narrow, false);
         }
     }
     if (use_lanes(h)) join(h, LANE_DW);
