@@ -98,6 +98,7 @@ SIGNATURES = {
     "ctx_train_step_sampled": (_c.c_int, [_P, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32), _c.c_int, _c.c_float, _F]),
     "ctx_eval_sampled": (_c.c_int, [_P, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32), _c.c_int, _F, _F, _F]),
     "ctx_last_outputs": (_c.c_int, [_P, _F, _F, _F]),
+    "ctx_nn_err": (_c.c_int, [_P, _c.c_int, _c.c_int, _c.POINTER(_c.c_int64)]),
     "ctx_eval": (_c.c_int, [_P, _F, _F, _F, _c.c_int, _F, _F, _F]),
     "ctx_dev_forward_backward": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_int]),
     "ctx_dev_frames": (_c.c_int, [_P, _c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p)]),
@@ -129,6 +130,7 @@ SIGNATURES = {
     "ctx_dp_train_step_sampled": (_c.c_int, [_P, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32), _c.c_int, _c.c_float, _F]),
     "ctx_dp_eval_sampled": (_c.c_int, [_P, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32), _c.c_int, _F, _F, _F]),
     "ctx_dp_allreduce_host_f64": (_c.c_int, [_P, _c.POINTER(_c.c_double), _c.c_size_t]),
+    "ctx_dp_nn_err": (_c.c_int, [_P, _c.c_int, _c.POINTER(_c.c_int64)]),
     "ctx_profile_step": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_float, _c.c_int, _c.POINTER(CtxProfEntry), _c.c_int,
                                     _c.POINTER(_c.c_int)]),
     "ctx_debug_read": (_c.c_int, [_P, _c.c_char_p, _F, _c.c_size_t]),
@@ -140,6 +142,9 @@ SIGNATURES = {
     "ctx_cnn_forward_u8": (_c.c_int, [_P, _U8, _c.c_int, _F]),
     "ctx_cnn_forward_u8_dev": (_c.c_int, [_P, _U8, _c.c_int, _c.POINTER(_P)]),
     "ctx_cnn_forward_dev": (_c.c_int, [_P, _P, _c.c_int, _c.POINTER(_P)]),
+    "ctx_cnn_demos_upload": (_c.c_int, [_P, _U8, _c.c_int, _c.c_int]),
+    "ctx_cnn_forward_sampled_dev": (_c.c_int, [_P, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32), _c.c_int, _c.c_int, _c.c_int,
+                                               _c.POINTER(_P)]),
     "ctx_cnn_read_buffer": (_c.c_int, [_P, _c.c_int, _c.c_int, _F]),
     "ctx_cnn_profile": (_c.c_int, [_P, _c.c_int, _c.c_int, _F, _c.c_int]),
     "ctx_cnn_stream": (_P, [_P]),

@@ -59,6 +59,14 @@ struct ctx_cnn {
     int stats_frames = 0, stats_stage = -1, stats_count[2] = {0, 0};   // stage: 0 pass 0 open, 1 mean done / pass 1 open, 2 std done
     float *r_mean = nullptr, *r_std = nullptr, *r_cost = nullptr;
     int r_frames = 0, r_c = 0;
+    // the trainer's demo tensor, resident (ctx_cnn_demos_upload / ctx_cnn_forward_sampled_dev): uint8 vdata[T][N][H][W][3] + 16 bytes
+    // of slack, the shard's index arrays on the device [choicesrc | choicetgt] and their pinned staging
+    uint8_t* vdata = nullptr;
+    int vT = 0, vN = 0;
+    int* choice = nullptr;
+    int* choice_host = nullptr;
+    hipEvent_t ev_choice = nullptr;                   // recorded after the last upload from choice_host
+    bool choice_pending = false;
     std::string err;
 };
 
@@ -341,6 +349,10 @@ void ctx_cnn_destroy(ctx_cnn* h) {
     }
     free_stats(h);
     free_reward(h);
+    if (h->vdata) (void)hipFree(h->vdata);
+    if (h->choice) (void)hipFree(h->choice);
+    if (h->choice_host) (void)hipHostFree(h->choice_host);
+    if (h->ev_choice) (void)hipEventDestroy(h->ev_choice);
     for (auto& kv : h->graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
     for (hipEvent_t e : h->done) if (e) (void)hipEventDestroy(e);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -388,6 +400,65 @@ int ctx_cnn_forward_u8_dev(ctx_cnn* h, const uint8_t* frames, int n, const float
     CNN_HIP(h, hipMemcpyAsync(h->u8, frames, (size_t)n * pix_in * 3, hipMemcpyHostToDevice, h->stream));
     pad_channels_u8(h->stream, h->u8, h->dbuf[0], n * pix_in, h->stem4 ? 4 : b0.c);
     const int rc = run_cached(h, n);
+    if (rc != CTX_OK) return rc;
+    if (d_out) *d_out = h->dbuf.back();
+    return CTX_OK;
+}
+
+// vdata: host uint8 [T, N, H, W, 3] at the front end's input size -> resident in HBM (replaces an earlier upload).  The trainer's
+// demo tensor: ctx_cnn_forward_sampled_dev gathers its batches on the device.
+int ctx_cnn_demos_upload(ctx_cnn* h, const uint8_t* vdata, int T, int N) {
+    if (!h) return CTX_E_INVALID;
+    if (!vdata || T <= 0 || N <= 0) return cfail(h, CTX_E_INVALID, "bad demo tensor (T %d, N %d)", T, N);
+    CNN_HIP(h, hipSetDevice(h->device));
+    CNN_HIP(h, hipStreamSynchronize(h->stream));              // a queued pass may still read the old tensor
+    if (h->vdata) { (void)hipFree(h->vdata); h->vdata = nullptr; h->vT = h->vN = 0; }
+    const ctx_cnn_buf& b0 = h->bufs.front();
+    const size_t bytes = (size_t)T * N * b0.h * b0.w * 3;
+    // + 16: the sampler reads the aligned 16-byte words that hold a frame's bytes, the last of which may reach past the last frame
+    if (hipMalloc((void**)&h->vdata, bytes + 16) != hipSuccess) {
+        (void)hipGetLastError();
+        h->vdata = nullptr;
+        return cfail(h, CTX_E_NOMEM, "hipMalloc(%zu bytes) for the demo tensor", bytes + 16);
+    }
+    if (!h->choice) {
+        bool ok = hipMalloc((void**)&h->choice, 2 * (size_t)h->max_images * sizeof(int)) == hipSuccess &&
+                  hipHostMalloc((void**)&h->choice_host, 2 * (size_t)h->max_images * sizeof(int), hipHostMallocDefault) == hipSuccess &&
+                  hipEventCreateWithFlags(&h->ev_choice, hipEventDisableTiming) == hipSuccess;
+        if (!ok) return cfail(h, CTX_E_NOMEM, "index buffers of the sampler");
+    }
+    CNN_HIP(h, hipMemsetAsync(h->vdata + bytes, 0, 16, h->stream));
+    CNN_HIP(h, hipMemcpyAsync(h->vdata, vdata, bytes, hipMemcpyHostToDevice, h->stream));
+    CNN_HIP(h, hipStreamSynchronize(h->stream));
+    h->vT = T; h->vN = N;
+    return CTX_OK;
+}
+
+// This rank's 3 B_local images [src | ctx | tgt] of the trainer's global batch, gathered from the resident demo tensor straight into
+// buffer 0, then one pass.  Asynchronous on the handle's stream (the index arrays are staged before the call returns).
+int ctx_cnn_forward_sampled_dev(ctx_cnn* h, const int32_t* choicesrc, const int32_t* choicetgt, int B_global, int rank, int world,
+                                const float** d_out) {
+    if (!h) return CTX_E_INVALID;
+    if (!h->vdata) return cfail(h, CTX_E_STATE, "ctx_cnn_demos_upload first");
+    if (!choicesrc || !choicetgt) return cfail(h, CTX_E_INVALID, "NULL index array");
+    if (world < 1 || rank < 0 || rank >= world) return cfail(h, CTX_E_INVALID, "bad rank %d / world %d", rank, world);
+    if (B_global <= 0 || B_global % world) return cfail(h, CTX_E_INVALID, "global batch %d is not a positive multiple of the %d ranks", B_global, world);
+    const int B = B_global / world, row0 = rank * B;
+    if (3ll * B > h->max_images) return cfail(h, CTX_E_INVALID, "%d triples per rank need %d front-end images, the handle holds %d", B, 3 * B, h->max_images);
+    for (int b = 0; b < B_global; ++b)      // (the whole array: every rank refuses the same bad call, so no rank is left waiting in a collective)
+        if (choicesrc[b] < 0 || choicesrc[b] >= h->vN || choicetgt[b] < 0 || choicetgt[b] >= h->vN)
+            return cfail(h, CTX_E_INVALID, "video index out of range [0,%d)", h->vN);
+    CNN_HIP(h, hipSetDevice(h->device));
+    if (h->choice_pending) CNN_HIP(h, hipEventSynchronize(h->ev_choice));   // the previous upload has left the staging buffer
+    memcpy(h->choice_host, choicesrc + row0, (size_t)B * sizeof(int));
+    memcpy(h->choice_host + B, choicetgt + row0, (size_t)B * sizeof(int));
+    CNN_HIP(h, hipMemcpyAsync(h->choice, h->choice_host, 2 * (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    CNN_HIP(h, hipEventRecord(h->ev_choice, h->stream));
+    h->choice_pending = true;
+    const ctx_cnn_buf& b0 = h->bufs.front();
+    gather_frames_u8(h->stream, h->vdata, h->vT, h->vN, b0.h * b0.w, h->choice, h->choice + B, B, row0, h->dbuf[0], h->stem4 ? 4 : b0.c);
+    if (hipGetLastError() != hipSuccess) return cfail(h, CTX_E_DEVICE, "sampler launch failed");
+    const int rc = run_cached(h, 3 * B);
     if (rc != CTX_OK) return rc;
     if (d_out) *d_out = h->dbuf.back();
     return CTX_OK;

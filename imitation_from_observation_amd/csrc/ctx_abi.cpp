@@ -141,6 +141,8 @@ void ctx_destroy(ctx_handle* h) {
     for (hipEvent_t e : h->prof_ev) (void)hipEventDestroy(e);
     if (h->vdata) (void)hipFree(h->vdata);
     if (h->dp_host_buf) (void)hipFree(h->dp_host_buf);
+    if (h->nn_dist) (void)hipFree(h->nn_dist);
+    if (h->nn_tgt) (void)hipFree(h->nn_tgt);
     for (auto& kv : h->graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
     delete h->gen;
     dp_teardown(h);
@@ -416,8 +418,38 @@ int stage_frames(ctx_handle* h, const float* d_src, const float* d_ctx, const fl
     }
     return CTX_OK;
 }
+
+// nn_err of the last training-mode forward: its B output rows (model.out) against Bt tgt rows `tgt` [Bt, npi] (this handle's tgt slot,
+// or ctx_dp_nn_err's gathered global batch); the sum lands in h->nn_res[0] (a double) in stream order
+int nn_err_enqueue(ctx_handle* h, const float* tgt, int Bt, int nlen, int j0) {
+    if (h->npi % 4) return fail(h, CTX_E_INVALID, "nn_err: %lld elements per image is not a multiple of 4", (long long)h->npi);
+    const int B = h->last_B;
+    const size_t need = (size_t)Bt * B;
+    if (need > h->nn_dist_cap) {
+        if (h->nn_dist) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->nn_dist); h->nn_dist = nullptr; h->nn_dist_cap = 0; }
+        if (hipMalloc((void**)&h->nn_dist, need * sizeof(double)) != hipSuccess) return fail(h, CTX_E_NOMEM, "hipMalloc(%zu bytes) for nn_err", need * sizeof(double));
+        h->nn_dist_cap = need;
+    }
+    if (!h->nn_res) TRY(dev_alloc(h, &h->nn_res, 2));
+    nn_err(h->stream, tgt, Bt, h->out, B, h->npi, nlen, j0, h->nn_dist, h->nn_res);
+    HIP_TRY(h, hipGetLastError());
+    return CTX_OK;
+}
 }  // namespace ctxi
 extern "C" {
+
+int ctx_nn_err(ctx_handle* h, int nlen, int j0, int64_t* err) {
+    if (!h) return CTX_E_INVALID;
+    if (!err || nlen <= 0 || j0 < 0) return fail(h, CTX_E_INVALID, "nn_err: need err, nlen > 0 and j0 >= 0");
+    if (h->last_B <= 0) return fail(h, CTX_E_STATE, "no training-mode forward has run");
+    HIP_TRY(h, hipSetDevice(h->device));
+    TRY(nn_err_enqueue(h, h->img, h->last_B, nlen, j0));          // img = [tgt | src | ctx]
+    double r = 0.0;
+    HIP_TRY(h, hipMemcpyAsync(&r, h->nn_res, sizeof r, hipMemcpyDeviceToHost, h->stream));
+    TRY(finish(h));
+    *err = (int64_t)r;
+    return CTX_OK;
+}
 
 int ctx_dev_forward(ctx_handle* h, const float* d_src, const float* d_ctx, const float* d_tgt, int B) {
     TRY(check_B(h, B));

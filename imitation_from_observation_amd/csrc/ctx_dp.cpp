@@ -256,6 +256,40 @@ int ctx_dp_allreduce_host_f64(ctx_handle* h, double* buf, size_t n) {
     return rc;
 }
 
+// nn_err of the global batch: every rank's outputs against ALL tgt rows.  (1) all-gather of the tgt slots as a SUM all-reduce of a
+// zero-filled [B_global, npi] buffer in which each rank wrote its own rows -- exact: every element has one non-zero contributor;
+// (2) this rank's share with j0 = rank * B; (3) a SUM all-reduce of the shares (f64: exact for counts below 2^53).
+int ctx_dp_nn_err(ctx_handle* h, int nlen, int64_t* err) {
+    if (!h) return CTX_E_INVALID;
+    if (!h->dp_comm) return fail(h, CTX_E_STATE, "ctx_dp_init first");
+    if (!err || nlen <= 0) return fail(h, CTX_E_INVALID, "nn_err: need err and nlen > 0");
+    if (h->last_B <= 0) return fail(h, CTX_E_STATE, "no training-mode forward has run");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int B = h->last_B, Bg = B * h->dp_world;
+    const size_t n = (size_t)Bg * h->npi, mine = (size_t)B * h->npi;
+    if (n > h->nn_tgt_cap) {
+        if (h->nn_tgt) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->nn_tgt); h->nn_tgt = nullptr; h->nn_tgt_cap = 0; }
+        if (hipMalloc((void**)&h->nn_tgt, n * sizeof(float)) != hipSuccess) return fail(h, CTX_E_NOMEM, "hipMalloc(%zu bytes) for the gathered tgt rows", n * sizeof(float));
+        h->nn_tgt_cap = n;
+    }
+    HIP_TRY(h, hipMemsetAsync(h->nn_tgt, 0, n * sizeof(float), h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->nn_tgt + (size_t)h->dp_rank * mine, h->img, mine * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipEventRecord(h->dp_ev_ready, h->stream));
+    HIP_TRY(h, hipStreamWaitEvent(h->dp_stream, h->dp_ev_ready, 0));
+    RCCL_TRY(h, rccl().AllReduce(h->nn_tgt, h->nn_tgt, n, ncclFloat, ncclSum, h->dp_comm, h->dp_stream));
+    TRY(dp_wait(h));
+    TRY(nn_err_enqueue(h, h->nn_tgt, Bg, nlen, h->dp_rank * B));
+    HIP_TRY(h, hipEventRecord(h->dp_ev_ready, h->stream));
+    HIP_TRY(h, hipStreamWaitEvent(h->dp_stream, h->dp_ev_ready, 0));
+    RCCL_TRY(h, rccl().AllReduce(h->nn_res, h->nn_res + 1, 1, ncclDouble, ncclSum, h->dp_comm, h->dp_stream));
+    double r = 0.0;
+    HIP_TRY(h, hipMemcpyAsync(&r, h->nn_res + 1, sizeof r, hipMemcpyDeviceToHost, h->dp_stream));
+    HIP_TRY(h, hipStreamSynchronize(h->dp_stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *err = (int64_t)r;
+    return CTX_OK;
+}
+
 int ctx_dp_scalars(ctx_handle* h, float scalars[4]) {
     if (!h || !scalars) return CTX_E_INVALID;
     if (!h->dp_comm) return fail(h, CTX_E_STATE, "ctx_dp_init first");

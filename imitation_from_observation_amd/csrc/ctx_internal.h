@@ -185,6 +185,13 @@ struct ctx_handle {
     int64_t dp_split = -1;        // first float of the tail bucket once it has been started in this step
     int dp_rc = 0;                // result of the collectives started from inside backward
     std::vector<std::pair<int64_t, int64_t>> dp_done;   // [first, end) of the HEAD of the arena already sent in this step (the encoders' FC slices)
+    // the trainer's nn_err on the device (ctx_nn_err / ctx_dp_nn_err): distances [tgt rows x out rows] f64, the result pair
+    // {this rank's sum, the global sum} f64, and ctx_dp_nn_err's all-gathered tgt slots [B_global, npi]; grown on demand
+    double* nn_dist = nullptr;
+    size_t nn_dist_cap = 0;
+    double* nn_res = nullptr;
+    float* nn_tgt = nullptr;
+    size_t nn_tgt_cap = 0;
     // Adam beside the backward (fused training steps only: adam_begin / adam_early / adam_end): a slice of the arena is updated on
     // its own stream as soon as its gradients are final and its parameters have been read for the last time in this step
     hipStream_t adam_stream = nullptr;
@@ -262,6 +269,7 @@ void fire_bucket(ctx_handle* h, int64_t first);
 int dp_reduce_range(ctx_handle* h, int64_t first, int64_t count);    // ctx_dp.cpp
 void dp_teardown(ctx_handle* h);                                      // ctx_dp.cpp
 int stage_frames(ctx_handle* h, const float* d_src, const float* d_ctx, const float* d_tgt, int B);   // ctx_abi.cpp
+int nn_err_enqueue(ctx_handle* h, const float* tgt, int Bt, int nlen, int j0);                       // ctx_abi.cpp: h->nn_res[0]
 
 template <class T>
 int dev_alloc(ctx_handle* h, T** p, int64_t count, bool whole_tensor = true) {

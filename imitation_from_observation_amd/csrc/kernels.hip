@@ -509,6 +509,118 @@ void gather_triples(hipStream_t s, const uint8_t* vdata, int T, int N, int64_t n
 }
 
 // ------------------------------------------------------------------------------------------------
+// The same sampler in front of the Inception front end (ctx_cnn_forward_sampled_dev): the 3B frames [src | ctx | tgt] of rows
+// b0 .. b0 + B of the global batch, converted with prep_u8 (the front end's preprocessing, base.py:116-119) and written straight
+// into the channel-padded buffer 0 ([pixels][cpad]; channel 3 is written as the 0 it holds, channels 4.. are left alone) -- the
+// bits hipMemcpy + pad_channels_u8 make of the host-gathered frames.  A frame is H*W*3 bytes, an odd count at 125^2 and 299^2, so
+// a frame starts at any byte.  One block covers GF_PIX pixels of one image: the aligned 16-byte words that hold its 3 * GF_PIX
+// source bytes go to LDS (the demo tensor carries 16 bytes of slack past its last frame for the last word), then every thread
+// converts one pixel and stores it as one float4, lanes on consecutive pixels.
+// ------------------------------------------------------------------------------------------------
+constexpr int GF_PIX = NTHREADS;
+__global__ __launch_bounds__(NTHREADS) void gather_frames_u8_kernel(const uint8_t* __restrict__ vdata, int T, int N, int npix,
+                                                                    const int* __restrict__ csrc, const int* __restrict__ ctgt, int B,
+                                                                    int b0, float* __restrict__ out, int cpad) {
+    __shared__ uint4 words[(3 * GF_PIX + 15 + 15) / 16];
+    const int i = blockIdx.y, slot = i / B, b = i % B;               // slot 0 src, 1 ctx, 2 tgt (InceptionTranslator's order)
+    const int t = slot == 1 ? 0 : (b0 + b) % T;
+    const int v = slot == 0 ? csrc[b] : ctgt[b];
+    const int p0 = blockIdx.x * GF_PIX;
+    const int np = min(GF_PIX, npix - p0);
+    const uintptr_t first = reinterpret_cast<uintptr_t>(vdata + ((int64_t)t * N + v) * npix * 3 + (int64_t)p0 * 3);
+    const uintptr_t base = first & ~(uintptr_t)15;
+    const int nw = (int)((first + 3 * np - base + 15) >> 4);
+    for (int k = threadIdx.x; k < nw; k += NTHREADS) words[k] = reinterpret_cast<const uint4*>(base)[k];
+    __syncthreads();
+    if ((int)threadIdx.x < np) {
+        const uint8_t* px = reinterpret_cast<const uint8_t*>(words) + (first - base) + 3 * threadIdx.x;
+        *reinterpret_cast<float4*>(out + ((int64_t)i * npix + p0 + threadIdx.x) * cpad) =
+            make_float4(prep_u8(px[0]), prep_u8(px[1]), prep_u8(px[2]), 0.f);
+    }
+}
+
+void gather_frames_u8(hipStream_t s, const uint8_t* vdata, int T, int N, int npix, const int* csrc, const int* ctgt, int B, int b0,
+                      float* out, int cpad) {
+    hipLaunchKernelGGL(gather_frames_u8_kernel, dim3((npix + GF_PIX - 1) / GF_PIX, 3 * B), dim3(NTHREADS), 0, s, vdata, T, N, npix, csrc,
+                       ctgt, B, b0, out, cpad);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The trainer's nn_err (train_script.py:148) where the maps are: dist[i][b] = mean((tgt_i - out_b)^2) in f64 over npi elements for every
+// tgt row i < Bt and output row b < Bo; then, per b, the FIRST i of least distance (np.argmin) and |i - (j0 + b) % nlen| summed.  One
+// block per (b, NN_TI consecutive i): out_b is read once per tile.  Fixed per-thread order and a fixed tree: the same bits every run.
+// ------------------------------------------------------------------------------------------------
+constexpr int NN_TI = 8;
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(NTHREADS) void nn_dist_kernel(const float* __restrict__ tgt, int Bt, const float* __restrict__ out, int64_t npi,
+                                                           double* __restrict__ dist, int Bo) {
+    __shared__ double red[NN_TI][NTHREADS / 64];
+    const int b = blockIdx.x, i0 = blockIdx.y * NN_TI;
+    const int ni = min(NN_TI, Bt - i0);
+    double acc[NN_TI];
+#pragma unroll
+    for (int k = 0; k < NN_TI; ++k) acc[k] = 0.0;
+    const float* o = out + (int64_t)b * npi;
+    for (int64_t e = (int64_t)threadIdx.x * 4; e < npi; e += NTHREADS * 4) {
+        const float4 x = *reinterpret_cast<const float4*>(o + e);
+#pragma unroll
+        for (int k = 0; k < NN_TI; ++k) {
+            if (k < ni) {
+                const float4 y = *reinterpret_cast<const float4*>(tgt + (int64_t)(i0 + k) * npi + e);
+                const double d0 = (double)y.x - x.x, d1 = (double)y.y - x.y, d2 = (double)y.z - x.z, d3 = (double)y.w - x.w;
+                acc[k] += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
+            }
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NN_TI; ++k) {
+        const double s = wave_sum_f64(acc[k]);
+        if (lane == 0) red[k][wave] = s;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < ni) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < NTHREADS / 64; ++w) s += red[threadIdx.x][w];
+        dist[(int64_t)(i0 + threadIdx.x) * Bo + b] = s / (double)npi;
+    }
+}
+
+__global__ __launch_bounds__(NTHREADS) void nn_argmin_kernel(const double* __restrict__ dist, int Bt, int Bo, int nlen, int j0,
+                                                             double* __restrict__ res) {
+    __shared__ long long red[NTHREADS];
+    long long s = 0;
+    for (int b = threadIdx.x; b < Bo; b += NTHREADS) {
+        int best = 0;
+        double bd = dist[b];
+        for (int i = 1; i < Bt; ++i) {
+            const double d = dist[(int64_t)i * Bo + b];
+            if (d < bd) { bd = d; best = i; }
+        }
+        const int want = (int)(((int64_t)j0 + b) % nlen);
+        s += best > want ? best - want : want - best;
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = NTHREADS / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) res[0] = (double)red[0];
+}
+
+void nn_err(hipStream_t s, const float* tgt, int Bt, const float* out, int Bo, int64_t npi, int nlen, int j0, double* dist, double* res) {
+    hipLaunchKernelGGL(nn_dist_kernel, dim3(Bo, (Bt + NN_TI - 1) / NN_TI), dim3(NTHREADS), 0, s, tgt, Bt, out, npi, dist, Bo);
+    hipLaunchKernelGGL(nn_argmin_kernel, dim3(1), dim3(NTHREADS), 0, s, dist, Bt, Bo, nlen, j0, res);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Losses.  recon_k = tf.nn.l2_loss(tgt - out_k) = sum(d^2)/2 over the WHOLE batch
 // (arm_shaping.py:1352-1353); simloss = mean((trans_z - tgtimg_z)^2) * 1e3 (:1345).
 // Wavefront shuffle reduction -> one partial per block -> fixed-order final sum in f64.

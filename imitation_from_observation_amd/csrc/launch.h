@@ -164,6 +164,14 @@ void incep_costs(hipStream_t s, const float* feat, int nframes, int F, int64_t h
 // device batch sampler (scripts/train_script.py:153-159); lut[256] = f32(x / 127.5 - 1)
 void gather_triples(hipStream_t s, const uint8_t* vdata, int T, int N, int64_t npi, const int* csrc, const int* ctgt, int B, int b0,
                     const float* lut, float* img);
+// ... and in front of the Inception front end: 3B frames [src | ctx | tgt] of vdata[T][N][npix][3], prep_u8, into buffer 0 [3B * npix][cpad]
+// (vdata must carry 16 bytes of slack past its last frame: the loads are aligned 16-byte words)
+void gather_frames_u8(hipStream_t s, const uint8_t* vdata, int T, int N, int npix, const int* csrc, const int* ctgt, int B, int b0,
+                      float* out, int cpad);
+
+// the trainer's nn_err (train_script.py:148): dist [Bt, Bo] f64 scratch; res[0] = sum_b |argmin_i mean((tgt_i - out_b)^2) - (j0 + b) % nlen|
+// (first index on ties), as a double.  npi a multiple of 4, rows 16-byte aligned.
+void nn_err(hipStream_t s, const float* tgt, int Bt, const float* out, int Bo, int64_t npi, int nlen, int j0, double* dist, double* res);
 
 // Losses (arm_shaping.py:1345,1352-1354) and their seeds of the backward pass.
 //   out [2B, npi] (rows < B: translated pass, rows >= B: truth pass), tgt [B, npi]

@@ -427,6 +427,29 @@ class InceptionFrontend:
         self._ck(self._lib.ctx_cnn_forward_u8_dev(self._h, fr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), fr.shape[0], ctypes.byref(d_out)))
         return d_out.value
 
+    def load_demos(self, vdata_u8):
+        """Keep the trainer's demo tensor vdata[T,N,H,W,3] (uint8, at this front end's input size) resident on the device
+        (ctx_cnn_demos_upload; replaces an earlier one).  CtxError CTX_E_NOMEM when it does not fit."""
+        v = np.ascontiguousarray(vdata_u8)
+        if v.dtype != np.uint8 or v.ndim != 5 or v.shape[2:] != (self.H, self.W, 3):
+            raise ValueError(f"vdata must be uint8 [T,N,{self.H},{self.W},3], got {v.dtype} {v.shape}")
+        self._ck(self._lib.ctx_cnn_demos_upload(self._h, v.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), v.shape[0], v.shape[1]))
+        self.demo_shape = v.shape[:2]
+
+    def features_sampled_dev(self, choicesrc, choicetgt, B_global, rank=0, world=1):
+        """This rank's 3 B_local images [src | ctx | tgt] of the trainer's global batch (train_script.py:154-159; B_local = B_global /
+        world, rows rank * B_local ...) gathered on the device from the resident demo tensor, then the pass: integer DEVICE address of
+        the output [3 B_local, h, w, c].  Asynchronous on the handle's stream."""
+        cs = np.ascontiguousarray(choicesrc, dtype=np.int32)
+        ct = np.ascontiguousarray(choicetgt, dtype=np.int32)
+        if cs.shape != (B_global,) or ct.shape != (B_global,):
+            raise ValueError(f"choicesrc / choicetgt must both be [{B_global}], got {cs.shape} and {ct.shape}")
+        ip = ctypes.POINTER(ctypes.c_int32)
+        d_out = ctypes.c_void_p()
+        self._ck(self._lib.ctx_cnn_forward_sampled_dev(self._h, cs.ctypes.data_as(ip), ct.ctypes.data_as(ip), int(B_global), int(rank),
+                                                       int(world), ctypes.byref(d_out)))
+        return d_out.value
+
     def output(self, n):
         """Host copy of the last forward's Mixed_7c maps [n,h,w,2048] (synchronises)."""
         out = np.empty((n,) + tuple(self._bufs[-1]), np.float32)

@@ -5,7 +5,13 @@ compares is the feature tensor (base.py:132: self.image_trans = featreshape).
 
 Both handles share ONE stream and the feature maps stay in HBM: frames go up as uint8, the front end writes Mixed_7c into its
 output buffer, the translator reads that buffer through device pointers (ctx_cnn_forward_u8_dev -> ctx_translate_dev /
-ctx_encode_dev / ctx_dev_forward_backward), and only codes, predicted feature maps and scalars come back."""
+ctx_encode_dev / ctx_dev_forward_backward), and only codes, predicted feature maps and scalars come back.
+
+The trainer's surface (scripts/train_script.py:144-203, trainer.ModelTrainer): the host-fed steps train_step_u8 / evaluate_u8, and --
+with the demo tensor resident in the front end (load_demos) -- the sampled steps on one GPU (train_step_sampled / eval_sampled) and
+data parallel (dp_*): every rank holds the whole uint8 tensor, gathers its rows of the GLOBAL batch on the device and runs the front
+end on them per step, as the reference graph does; the translator's step is the bucketed RCCL step of ctx_dp_train_step on the maps.
+nn_err / dp_nn_err compare output maps with tgt maps where they are."""
 from __future__ import annotations
 
 import numpy as np
@@ -81,3 +87,96 @@ class InceptionTranslator:
         if outputs:
             res["out"], res["out2"], res["tgt"] = self.tr.last_outputs(out=True, out2=True, tgt=True)
         return res
+
+    # ------------------------------------------------------------------ the trainer's sampled steps (resident demo tensor)
+    def load_demos(self, vdata_u8):
+        """Keep the trainer's demo tensor vdata[T,N,H,W,3] (uint8 frames) resident in the front end (ctx_cnn_demos_upload)."""
+        self.front.load_demos(vdata_u8)
+        self.demo_shape = self.front.demo_shape
+
+    def _sampled_dev(self, choicesrc, choicetgt, rank=0, world=1):
+        cs = np.ascontiguousarray(choicesrc, dtype=np.int32)
+        ct = np.ascontiguousarray(choicetgt, dtype=np.int32)
+        if cs.shape != ct.shape or cs.ndim != 1:
+            raise ValueError("choicesrc / choicetgt must be 1-D and equally long")
+        B = cs.size // world
+        d = self.front.features_sampled_dev(cs, ct, cs.size, rank, world)
+        return d, d + B * self._per, d + 2 * B * self._per, B
+
+    def train_step_sampled(self, choicesrc, choicetgt, lr=1e-4):
+        """train_step_u8 on the batch the trainer samples (train_script.py:153-163), gathered from the resident tensor on the device:
+        the same calls on the same maps, so the same bits."""
+        ds, dc, dt, B = self._sampled_dev(choicesrc, choicetgt)
+        self.tr.dev_forward_backward(ds, dc, dt, B)
+        self.tr.dev_adam(lr)
+        return self.tr.dev_scalars()
+
+    def eval_sampled(self, choicesrc, choicetgt, outputs=True):
+        """evaluate_u8 on the sampled validation batch (train_script.py:169-176)."""
+        ds, dc, dt, B = self._sampled_dev(choicesrc, choicetgt)
+        self.tr.dev_forward(ds, dc, dt, B)
+        res = self.tr.dev_scalars()
+        if outputs:
+            res["out"], res["out2"], res["tgt"] = self.tr.last_outputs(out=True, out2=True, tgt=True)
+        return res
+
+    def nn_err(self, nlen, j0=0):
+        """trainer.nn_err of the last training-mode forward on the device: output maps against the tgt maps it was fed."""
+        return self.tr.nn_err(nlen, j0)
+
+    def last_outputs(self, out=True, out2=False, tgt=False):
+        return self.tr.last_outputs(out=out, out2=out2, tgt=tgt)
+
+    def save(self, path, with_adam=True, prefix=""):
+        return self.tr.save(path, with_adam=with_adam, prefix=prefix)
+
+    def load(self, path, prefix=""):
+        self.tr.load(path, prefix=prefix)
+
+    # ------------------------------------------------------------------ data parallel (one process per GPU)
+    @staticmethod
+    def dp_unique_id():
+        return Translator.dp_unique_id()
+
+    def dp_init(self, unique_id, rank, world):
+        """Collective: the translator joins the RCCL group (rank 0's parameters and Adam slots reach every replica); the front end is
+        frozen and needs no exchange."""
+        self.tr.dp_init(unique_id, rank, world)
+
+    def dp_world(self):
+        return self.tr.dp_world()
+
+    def dp_allreduce_host(self, arr):
+        return self.tr.dp_allreduce_host(arr)
+
+    def dp_scalars(self):
+        return self.tr.dp_scalars()
+
+    def _rank_world(self):
+        rank, world = self.tr.dp_world()
+        if world < 1:
+            raise ValueError("dp_init first")
+        return rank, world
+
+    def dp_train_step_sampled(self, choicesrc, choicetgt, lr=1e-4, scalars=True):
+        """One data-parallel step: this rank's rows of the GLOBAL batch through the front end (on the device, from the resident tensor),
+        then ctx_dp_train_step on the maps (simloss mean over the global batch, bucketed gradient all-reduce, Adam).  Returns the
+        GLOBAL dict(loss, simloss, recon1, recon2) when scalars."""
+        rank, world = self._rank_world()
+        ds, dc, dt, B = self._sampled_dev(choicesrc, choicetgt, rank, world)
+        return self.tr.dp_train_step(ds, dc, dt, B, lr=lr, scalars=scalars)
+
+    def dp_eval_sampled(self, choicesrc, choicetgt, outputs=True):
+        """The validation fetch sharded over the ranks (collective): GLOBAL scalars and -- outputs=True -- out / out2 / tgt maps of THIS
+        rank's rows."""
+        rank, world = self._rank_world()
+        ds, dc, dt, B = self._sampled_dev(choicesrc, choicetgt, rank, world)
+        self.tr.dev_forward(ds, dc, dt, B)
+        res = self.tr.dp_scalars()
+        if outputs:
+            res["out"], res["out2"], res["tgt"] = self.tr.last_outputs(out=True, out2=True, tgt=True)
+        return res
+
+    def dp_nn_err(self, nlen):
+        """nn_err of the GLOBAL batch (collective; ctx_dp_nn_err): the same integer on every rank."""
+        return self.tr.dp_nn_err(nlen)

@@ -40,6 +40,10 @@ device (t = b % nlen on the global row b) and runs the bucketed RCCL step; the v
 of the ranks' shares (each rank compares its outputs with ALL tgt frames of the batch), and only rank 0 writes checkpoints, clips,
 `validloss.npy`, `vdata_train.npy` and the CSV.  The parameters after k steps equal the single-GPU run's on the same draws up to f32
 summation order (tests/test_gpu_dp_two_ranks.py).
+The Inception variant (`inception=True`) does the same with its uint8 frames resident in the front end: each rank gathers its rows
+into the front end on the device (ctx_cnn_forward_sampled_dev), runs Inception on them per step as the reference graph does, and
+trains the translator with ctx_dp_train_step on the maps; `nn_err` is ctx_dp_nn_err (the tgt maps are all-gathered on the devices,
+never brought to the host).  On one GPU it keeps the host gather (train_step_u8 / evaluate_u8).
 """
 from __future__ import annotations
 
@@ -47,6 +51,8 @@ import csv
 import os
 
 import numpy as np
+
+from . import _lib
 
 LEARNING_RATE = 1e-4          # fed at every step, train_script.py:163,167
 
@@ -116,8 +122,6 @@ class ModelTrainer:
             raise ValueError(f"rank {rank} / world {world}")
         if self.world > 1 and batch_size % self.world:
             raise ValueError(f"batch_size {batch_size} (the GLOBAL batch) must be a multiple of world = {world}")
-        if self.world > 1 and inception:
-            raise ValueError("the Inception variant trains on one GPU here (its demo frames are not kept resident)")
         self.allloss, self.validloss = [], []
 
     # ------------------------------------------------------------------ the model behind the four sess.run sites
@@ -128,7 +132,7 @@ class ModelTrainer:
         H, W = self.idims
         if self.inception:
             from .oursinception import InceptionTranslator
-            tr = InceptionTranslator((H, W), max_batch=self.batch_size, device=self.device, precision=self.precision,
+            tr = InceptionTranslator((H, W), max_batch=self.batch_size // self.world, device=self.device, precision=self.precision,
                                      strides=self.strides, kernels=self.kernels, filters=self.filters)   # train_script.py:110
             tr.tr.init_params(self.seed)
             return tr
@@ -203,16 +207,32 @@ class ModelTrainer:
         log(str(validdata.shape) + str(traindata.shape))
         if rank == 0:
             np.save(basedir + "vdata_train", traindata[:, :200])
-        # device-resident demo tensor + device sampler where that is bit-identical to the host gather
-        u8, lattice = on_u8_lattice(vdata) if not self.inception else (None, False)
-        resident = lattice and hasattr(tr, "load_demos")
+        # device-resident demo tensor + device sampler where that is bit-identical to the host gather.  The Inception variant feeds
+        # uint8 frames to its front end: data parallel it samples them on the device (the front end's sampler), on one GPU it keeps
+        # the host gather
+        if self.inception:
+            u8 = vdata if vdata.dtype == np.uint8 else None
+            resident = dp and u8 is not None
+            if dp and not resident:
+                raise ValueError("data-parallel Inception training samples on the device: the demo tensor must be the uint8 frames "
+                                 f"(got {vdata.dtype})")
+        else:
+            u8, lattice = on_u8_lattice(vdata)
+            resident = lattice and hasattr(tr, "load_demos")
         if dp and not resident:
             raise ValueError("data-parallel training runs on the device-resident sampler: the demo tensor must lie on the uint8 lattice "
                              "(k / 127.5 - 1, what train_script.py:16-19 makes of video frames)")
         if resident:
             # only frames t < nlen are ever sampled (t = b % nlen, and frame 0 for the context); the device sampler takes
             # t = b % T with T = the uploaded tensor's length, so upload exactly nlen frames (vdata may hold more)
-            tr.load_demos(np.ascontiguousarray(u8[:nlen]))
+            try:
+                tr.load_demos(np.ascontiguousarray(u8[:nlen]))
+            except Exception as e:
+                if self.inception and getattr(e, "code", None) == _lib.CTX_E_NOMEM:
+                    raise ValueError(f"data-parallel Inception training keeps the demo tensor {u8[:nlen].shape} resident on every rank "
+                                     f"and it does not fit on the device ({e}): fewer videos, or one GPU (host gather)") from e
+                raise
+        dp_incep = dp and self.inception                           # nn_err of the global batch on the device (ctx_dp_nn_err)
 
         def train_step(cs, ct):
             if dp:
@@ -226,6 +246,8 @@ class ModelTrainer:
 
         def evaluate(cs, ct):
             """loss, sim, r1, r2, out, out2, tgt of a validation batch (indices into validdata)."""
+            if dp_incep:                                       # GLOBAL scalars; nn_err is taken on the device (dp_nn_err)
+                return tr.dp_eval_sampled(np.asarray(cs) + ntrain, np.asarray(ct) + ntrain, outputs=False), None
             src, ctx, tgt = self._batch(validdata, cs, ct)
             if dp:                                             # GLOBAL scalars; out / out2 = this rank's rows
                 ev = tr.dp_eval_sampled(np.asarray(cs) + ntrain, np.asarray(ct) + ntrain)
@@ -245,10 +267,13 @@ class ModelTrainer:
             choicetgt = np.random.choice(ntrain, B)
             sc = train_step(choicesrc, choicetgt)
             if itr % 4 == 0:
-                out, _, tgt = core.last_outputs(out=True, tgt=True)
-                if dp:                                         # this rank's outputs against ALL tgt frames of the batch (:148)
-                    tgt = self._batch(traindata, choicesrc, choicetgt)[2]
-                err = int(allsum([nn_err(tgt, out, nlen, j0)])[0])
+                if dp_incep:                                   # the tgt maps exist only on the device, one shard per rank
+                    err = int(tr.dp_nn_err(nlen))
+                else:
+                    out, _, tgt = core.last_outputs(out=True, tgt=True)
+                    if dp:                                     # this rank's outputs against ALL tgt frames of the batch (:148)
+                        tgt = self._batch(traindata, choicesrc, choicetgt)[2]
+                    err = int(allsum([nn_err(tgt, out, nlen, j0)])[0])
                 log("%s %s %s %s %s %s" % (itr, sc["loss"], sc["simloss"], sc["recon1"], sc["recon2"], err))
                 self.allloss.append(sc["loss"])
             if itr % 40 == 0 or itr % self.save_every == 0:
@@ -256,7 +281,7 @@ class ModelTrainer:
                 choicetgt = np.random.choice(nvalid, B)
                 ev, tgt = evaluate(choicesrc, choicetgt)
                 loss, sim, r1, r2 = ev["loss"], ev["simloss"], ev["recon1"], ev["recon2"]
-                err = int(allsum([nn_err(tgt, ev["out"], nlen, j0)])[0])
+                err = int(tr.dp_nn_err(nlen)) if dp_incep else int(allsum([nn_err(tgt, ev["out"], nlen, j0)])[0])
                 log("%s %s %s %s %s %s E" % (itr, loss, sim, r1, r2, err))
                 self.validloss.append(loss)
                 if itr % self.save_every == 0:

@@ -441,6 +441,13 @@ class Translator:
         self._ck(self._lib.ctx_last_outputs(self._h, *[_fp(a) if a is not None else None for a in arrs]))
         return tuple(arrs)
 
+    def nn_err(self, nlen, j0=0):
+        """The trainer's nn_err (train_script.py:148; trainer.nn_err) of the last training-mode forward on the device: its outputs against
+        the tgt frames (or maps) it was fed, distances in f64, first index on ties.  j0: global row of the first output."""
+        err = ctypes.c_int64()
+        self._ck(self._lib.ctx_nn_err(self._h, int(nlen), int(j0), ctypes.byref(err)))
+        return int(err.value)
+
     def evaluate(self, src, ctx, tgt, outputs=True):
         """Forward + losses (train_script.py:176,192-193)."""
         src, ctx, tgt, B = self._triple(src, ctx, tgt)
@@ -600,6 +607,13 @@ class Translator:
             raise ValueError("dp_allreduce_host wants a C-contiguous float64 array")
         self._ck(self._lib.ctx_dp_allreduce_host_f64(self._h, arr.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), arr.size))
         return arr
+
+    def dp_nn_err(self, nlen):
+        """nn_err of the GLOBAL batch after the same training-mode forward on every rank (ctx_dp_nn_err; collective): every rank's
+        outputs against the tgt rows of all ranks, the shares summed.  The same integer on every rank."""
+        err = ctypes.c_int64()
+        self._ck(self._lib.ctx_dp_nn_err(self._h, int(nlen), ctypes.byref(err)))
+        return int(err.value)
 
     def dp_scalars(self):
         sc = np.empty(4, np.float32)

@@ -46,7 +46,8 @@ extern "C" {
 #define CTX_ABI_VERSION 4   /* 2: ctx_config carries strides / kernels / filters / keep_prob / loss_mode; 3: per-handle options,
                                ctx_dp_train_step_sampled / ctx_dp_eval_sampled, ctx_prof_entry.useful_frac; 4: ctx_dev_frames;
                                still 4 (additions only): ctx_vjp_args, ctx_dev_forward_vjp, ctx_dev_backward_vjp, ctx_params_written;
-                               CTX_CNN_AVGPOOL_VALID / CTX_CNN_CONV_LINEAR, ctx_cnn_stats_*, ctx_cnn_reward_* */
+                               CTX_CNN_AVGPOOL_VALID / CTX_CNN_CONV_LINEAR, ctx_cnn_stats_*, ctx_cnn_reward_*; ctx_nn_err,
+                               ctx_dp_nn_err, ctx_cnn_demos_upload, ctx_cnn_forward_sampled_dev */
 
 enum {
     CTX_OK = 0,
@@ -238,6 +239,11 @@ int ctx_eval_sampled(ctx_handle* h, const int32_t* choicesrc, const int32_t* cho
 /* Host copies of model.out / model.out2 [B,H,W,3] of the last training-mode forward and of the tgt frames it was fed
  * (tfinput[2]) -- what the trainer's `nn_err` fetch reads next to the optimizer (train_script.py:148,163).  Any may be NULL. */
 int ctx_last_outputs(ctx_handle* h, float* out, float* out2, float* tgt);
+/* The trainer's nn_err (train_script.py:148) of the last training-mode forward, computed where the maps are: rows of model.out against
+ * the tgt slot it was fed,  *err = sum_b | argmin_i mean((tgt_i - out_b)^2) - ((j0 + b) % nlen) |  with the distances accumulated in
+ * f64 and the FIRST index of least distance on ties (np.argmin).  j0: the first global row of these outputs (a data-parallel shard's
+ * share).  Any variant (npi = H*W*C a multiple of 4).  Synchronous. */
+int ctx_nn_err(ctx_handle* h, int nlen, int j0, int64_t* err);
 /* Forward + losses only.  out / out2 (nullable) [B,H,W,3]. */
 int ctx_eval(ctx_handle* h, const float* src, const float* ctx, const float* tgt, int B,
              float scalars[4], float* out, float* out2);
@@ -341,7 +347,8 @@ int ctx_params_written(ctx_handle* h);
  *                         h4_lin / hz_lin slice, are reduced on a second stream while the encoders' backward still runs;
  *                         only the encoders' conv filters (18 % of the arena) go after it; then Adam.  scalars (nullable) =
  *                         GLOBAL {loss, simloss, recon1, recon2} (one more 16-byte all-reduce and a sync).  d_* are DEVICE
- *                         pointers [B,H,W,3] f32; every rank passes the same B.
+ *                         pointers [B,H,W,3] f32 -- for CTX_VARIANT_INCEPTION2 handles the Mixed_7c maps [B,h,w,C] f32, e.g.
+ *                         the three slices of ctx_cnn_forward_sampled_dev's output; every rank passes the same B.
  *   ctx_dp_scalars        global scalars of the last forward (collective) */
 #define CTX_DP_UNIQUE_ID_BYTES 128
 int ctx_dp_unique_id(uint8_t id[CTX_DP_UNIQUE_ID_BYTES]);
@@ -369,6 +376,11 @@ int ctx_dp_eval_sampled(ctx_handle* h, const int32_t* choicesrc, const int32_t* 
  * one device; reward.py shards the demo videos rank::world and adds the partial feature / frame sums): the group that
  * ctx_dp_init made serves it, no second communication library in the sampler process. */
 int ctx_dp_allreduce_host_f64(ctx_handle* h, double* buf, size_t n);
+/* ctx_nn_err of the GLOBAL batch (collective: every rank must call it, after the same training-mode forward on its shard): every rank's
+ * outputs against the tgt rows of ALL ranks.  The tgt slots are all-gathered as a SUM all-reduce of a zero-filled [B_global, npi] buffer
+ * in which each rank wrote its own rows (exact: one non-zero contributor per element), rank r's share is taken with j0 = r * B, and
+ * the shares are summed.  *err is the same on every rank. */
+int ctx_dp_nn_err(ctx_handle* h, int nlen, int64_t* err);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* One entry per launch group of a train step (a layer's forward, input gradient, filter gradient,
@@ -443,6 +455,19 @@ int ctx_cnn_forward_u8_dev(ctx_cnn* h, const uint8_t* frames, int n, const float
 /* d_frames: DEVICE f32 [n,H,W,3] in [-1,1], n <= max_images; *d_out: device pointer of the last buffer.
  * Asynchronous on the handle's stream (ctx_cnn_stream / ctx_cnn_sync). */
 int ctx_cnn_forward_dev(ctx_cnn* h, const float* d_frames, int n, const float** d_out);
+/* The trainer's input pipeline in front of the front end (mode 'oursinception', scripts/train_script.py:144-163; data parallel as
+ * ctx_dp_train_step_sampled).  ctx_cnn_demos_upload keeps vdata[T][N][H][W][3] (uint8 frames at the front end's input size) in HBM on
+ * the handle's device, replacing an earlier upload (CTX_E_NOMEM when it does not fit: 33 GB at 299x299, T = 25, N = 5000).
+ * ctx_cnn_forward_sampled_dev: every rank passes the SAME global index arrays choicesrc / choicetgt [B_global]
+ * (np.random.choice(ntrain, batch_size) twice, :154-155); rank r takes the global rows b in [r B/world, (r+1) B/world) and builds
+ * 3 B_local images [src | ctx | tgt]:  src[b] = vdata[b % T][choicesrc[b]],  ctx[b] = vdata[0][choicetgt[b]],
+ * tgt[b] = vdata[b % T][choicetgt[b]]  -- gathered, preprocessed and channel-padded into buffer 0 by one kernel, bit-identical to
+ * ctx_cnn_forward_u8_dev on the same frames gathered on the host -- then runs the pass; *d_out as ctx_cnn_forward_u8_dev.  Every index
+ * of the WHOLE arrays is checked before anything is launched (every rank refuses the same bad call); B_global % world != 0 and
+ * 3 B_local > max_images are refused too (CTX_E_INVALID).  Asynchronous on the handle's stream. */
+int ctx_cnn_demos_upload(ctx_cnn* h, const uint8_t* vdata, int T, int N);
+int ctx_cnn_forward_sampled_dev(ctx_cnn* h, const int32_t* choicesrc, const int32_t* choicetgt, int B_global, int rank, int world,
+                                const float** d_out);
 int ctx_cnn_read_buffer(ctx_cnn* h, int index, int n, float* out);   /* end-point tests */
 /* Per-op HIP-event times (ms, averaged over `iters` passes over the n images currently in buffer 0); measurement only. */
 int ctx_cnn_profile(ctx_cnn* h, int n, int iters, float* ms, int max_ops);
