@@ -13,6 +13,7 @@ CTX_VARIANT_INCEPTION2 = 2
 CTX_PREC_F32 = 0
 CTX_PREC_BF16X3 = 1
 CTX_DP_UNIQUE_ID_BYTES = 128
+CTX_DISC_TPIL, CTX_DISC_GAIL = 0, 1
 
 
 class CtxConfig(ctypes.Structure):
@@ -39,6 +40,11 @@ class CtxProfEntry(ctypes.Structure):
                 ("ms", ctypes.c_float), ("useful_frac", ctypes.c_float)]
 
 
+class CtxDiscConfig(ctypes.Structure):
+    """ctx_disc_config of include/ctxtrans.h."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("variant", "H", "W", "C", "max_batch")]
+
+
 class CtxError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libctxtrans error {code}: {msg}")
@@ -50,6 +56,7 @@ _P = _c.c_void_p
 _F = _c.POINTER(_c.c_float)
 _U8 = _c.POINTER(_c.c_uint8)
 _CFG = _c.POINTER(CtxConfig)
+_DCFG = _c.POINTER(CtxDiscConfig)
 
 # name -> (restype, argtypes): every symbol include/ctxtrans.h declares
 class CnnBuf(ctypes.Structure):
@@ -155,6 +162,30 @@ SIGNATURES = {
     "ctx_cnn_stats_read": (_c.c_int, [_P, _c.c_int, _F, _F, _c.POINTER(_c.c_int)]),
     "ctx_cnn_reward_set_stats": (_c.c_int, [_P, _c.c_int, _F, _F, _c.c_int]),
     "ctx_cnn_reward_costs": (_c.c_int, [_P, _U8, _c.c_int, _F]),
+    "ctx_disc_param_total_for": (_c.c_int64, [_DCFG]),
+    "ctx_disc_create": (_c.c_int, [_DCFG, _c.c_int, _c.POINTER(_P)]),
+    "ctx_disc_destroy": (None, [_P]),
+    "ctx_disc_last_error": (_c.c_char_p, [_P]),
+    "ctx_disc_param_count": (_c.c_int, [_P]),
+    "ctx_disc_param_info": (_c.c_int, [_P, _c.c_int, _c.POINTER(_c.c_char_p), _c.POINTER(_c.c_int),
+                                       _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
+    "ctx_disc_set_params": (_c.c_int, [_P, _F, _c.c_size_t]),
+    "ctx_disc_get_params": (_c.c_int, [_P, _F, _c.c_size_t]),
+    "ctx_disc_get_grads": (_c.c_int, [_P, _F, _c.c_size_t]),
+    "ctx_disc_set_adam_state": (_c.c_int, [_P, _F, _F, _c.c_size_t, _c.c_int64]),
+    "ctx_disc_get_adam_state": (_c.c_int, [_P, _F, _F, _c.c_size_t, _c.POINTER(_c.c_int64)]),
+    "ctx_disc_init_params": (_c.c_int, [_P, _c.c_uint64]),
+    "ctx_disc_sync": (_c.c_int, [_P]),
+    "ctx_disc_train": (_c.c_int, [_P, _F, _F, _F, _F, _c.c_int, _c.c_float, _F]),
+    "ctx_disc_train_u8": (_c.c_int, [_P, _U8, _P, _F, _F, _c.c_int, _c.c_float, _F]),
+    "ctx_disc_logits": (_c.c_int, [_P, _F, _F, _c.c_int, _c.c_int, _F]),
+    "ctx_disc_logits_u8": (_c.c_int, [_P, _U8, _P, _c.c_int, _c.c_int, _F]),
+    "ctx_disc_accuracy": (_c.c_int, [_P, _F, _F, _F, _c.c_int, _F]),
+    "ctx_disc_accuracy_u8": (_c.c_int, [_P, _U8, _P, _F, _c.c_int, _F]),
+    "ctx_disc_data_upload": (_c.c_int, [_P, _U8, _c.c_int, _c.c_int, _F, _F]),
+    "ctx_disc_train_epoch": (_c.c_int, [_P, _c.POINTER(_c.c_int32), _c.c_int64, _c.c_int, _c.c_int, _c.c_float, _c.c_int, _F, _F]),
+    "ctx_disc_reward_paths": (_c.c_int, [_P, _U8, _c.c_int, _c.c_int, _c.c_int, _F]),
+    "ctx_disc_debug_read": (_c.c_int, [_P, _c.c_char_p, _F, _c.c_size_t]),
 }
 
 _lib = None

@@ -315,3 +315,34 @@ class InceptionFeatureReward:
             for j in range(self.batch_size):
                 p["rewards"][j * 2 + 1] -= c[j] * (j ** 2)
         return costs
+
+
+class ThirdPersonReward:
+    """The two learned baselines of the comparison (launcher modes 'tpil' / 'gail'; sandbox/bradly/third_person/launchers/
+    cyberpunk_aws.py, cyberpunk_aws_gail.py): a discriminator retrained every iteration on expert / on-policy (/ expert-fail)
+    trajectories, whose P(expert) is the policy's reward.  Unlike the two classes above it is not frozen: every iteration calls
+    set_data(...), train_cost(n_epochs) and then process_paths(paths) (third_person.ThirdPersonCost does the work on the device)."""
+    N_EPOCHS = {"tpil": 10, "gail": 2}        # cyberpunk_trainer.py:113, cyberpunk_trainer_gail.py:83
+
+    def __init__(self, cost, mode):
+        self.cost, self.mode = cost, mode
+
+    @classmethod
+    def for_sampler(cls, mode, imsize, batch_size=32, device=0, seed=0):
+        from .third_person import ConvDiscriminator, DomainConfusionVelocityDiscriminator, ThirdPersonCost
+        if mode not in ("tpil", "gail"):
+            raise ValueError(f"mode must be 'tpil' or 'gail', got {mode!r}")
+        dim = [int(imsize[0]), int(imsize[1]), 3]
+        disc = (DomainConfusionVelocityDiscriminator(dim, 2, 2, max_batch=batch_size, device=device, seed=seed) if mode == "tpil"
+                else ConvDiscriminator(dim, max_batch=batch_size, device=device, seed=seed))
+        return cls(ThirdPersonCost(disc, batch_size=batch_size), mode)
+
+    def set_data(self, expert, on_policy, expert_fail=None):
+        return self.cost.set_data(expert, on_policy, expert_fail)
+
+    def train_cost(self, n_epochs=None):
+        return self.cost.train_cost(self.N_EPOCHS[self.mode] if n_epochs is None else n_epochs)
+
+    def process_paths(self, paths):
+        """In place: path['rewards'] = P(expert) per frame (cyberpunk_rollout).  Returns the paths."""
+        return self.cost.path_rewards(paths)

@@ -500,6 +500,67 @@ int ctx_cnn_stats_read(ctx_cnn* h, int slot, float* means, float* stds, int* cou
 int ctx_cnn_reward_set_stats(ctx_cnn* h, int channels, const float* means, const float* stds, int nframes);
 int ctx_cnn_reward_costs(ctx_cnn* h, const uint8_t* frames, int npaths, float* costs);
 
+/* ---- third-person-imitation and GAIL baseline discriminators (modes 'tpil' / 'gail') ---------------------------
+ * The two learned image rewards the reference compares against, both retrained inside the RL loop
+ * (sandbox/bradly/third_person: discriminators/discriminator.py, algos/cyberpunk_trainer.py, algos/cyberpunk_trainer_gail.py).
+ * ABI 4, additions only.  Frames are RAW pixel values 0..255 (float32 or uint8; no scaling anywhere), NHWC.
+ *   TPIL  DomainConfusionVelocityDiscriminator (:357-548): a row is two frames (t and min(t + 3, T - 1)); both through
+ *         conv3x3+ReLU, 2x2 SAME max pool, conv3x3+ReLU, pool, flatten, FC 128 + ReLU; class MLP 256-128-128-2 on [f1 | f2],
+ *         domain MLP 128-128-128-2 behind flip_gradient(f1, 0.2); loss = CE_class + 0.2 CE_dom.
+ *   GAIL  ConvDiscriminator (:122-207): a row is one frame and its time step; conv, pool, [flatten | time] -> 128 (ReLU) -> 2.
+ *         wc2 / bc2 exist as in the reference (its second conv is commented out), receive no gradient and never move.
+ *         H and W must be even (the reference's conv_out_size).
+ * Parameters by name in the reference's creation order: wc1 wc2 bc1 bc2, then TPIL: w_feats_one b_feats_one w_targets0 b_targets0 ..
+ * w_targets2 b_targets2 w_dom0 b_dom0 .. w_dom2 b_dom2; GAIL: w_0 b_0 w_1 b_1.  Filters HWIO, FC weights [in][out].
+ * Arithmetic: f32, every sum in a fixed order (bit-identical from run to run); the max pool's gradient goes to the first maximum
+ * of a window in row-major order, ReLU'(0) = 0; cross-entropy in log-sum-exp form, its gradient softmax - labels; argmax ties -> 0;
+ * TF Adam (beta 0.9 / 0.999, eps 1e-8 outside the bias correction).  No CPU path: ctx_disc_create without a device is CTX_E_DEVICE.
+ *
+ * Host-array forms, one per reference call site (x1 [B,H,W,3]; x2_or_time: TPIL the second frames [B,H,W,3] in x1's type, GAIL the
+ * time column float [B]; cls / dom one-hot float [B,2]; 1 <= B <= max_batch):
+ *   ctx_disc_train     one Adam step; *loss = the loss before the update (sess.run([optimizer, loss])).
+ *   ctx_disc_logits    class logits, or their softmax, [B,2].       ctx_disc_accuracy  mean(argmax cls == argmax logits).
+ * Resident forms:
+ *   ctx_disc_data_upload  frames uint8 [N,T,H,W,3] and per-trajectory one-hot cls / dom [N,2] (dom nullable) into device memory.
+ *   ctx_disc_train_epoch  order[n]: flat row indices (trajectory * T + t) into that tensor.  Batch k = rows order[k batch ..): first
+ *                         frame t, second frame min(t + shift, T - 1) (GAIL: time = t), the trajectory's targets; one step per batch,
+ *                         then (with_accuracy) the accuracy of batch k on the UPDATED parameters -- all batches enqueued without a
+ *                         host synchronisation; losses / accs [ceil(n / batch)] come back once.  Bit-identical to the same rows
+ *                         through ctx_disc_train_u8 / ctx_disc_accuracy_u8 one batch at a time.
+ *   ctx_disc_reward_paths frames uint8 [P,T,H,W,3] -> probs[P T] = softmax(class logits)[:, 0] of the pairs (t, min(t + shift, T - 1))
+ *                         (GAIL: of (frame t, time t)).  Whole paths per pass, each frame through the conv stack ONCE; equal bit for
+ *                         bit to ctx_disc_logits_u8 on the materialised pairs (a row's sums do not depend on its neighbours).
+ * ctx_disc_debug_read (tests): pool1 sel1 pool2 sel2 f hc1 hc2 hd1 hd2 logits probs of the last forward; sel = the pool windows'
+ * winner (0..3, row-major) + 4 * (maximum > 0), as floats. */
+enum { CTX_DISC_TPIL = 0, CTX_DISC_GAIL = 1 };
+typedef struct ctx_disc_config { int32_t variant, H, W, C, max_batch; } ctx_disc_config;
+typedef struct ctx_disc ctx_disc;
+int64_t ctx_disc_param_total_for(const ctx_disc_config* cfg);      /* works without a device; CTX_E_INVALID for a bad config */
+int ctx_disc_create(const ctx_disc_config* cfg, int device, ctx_disc** out);
+void ctx_disc_destroy(ctx_disc* h);
+const char* ctx_disc_last_error(const ctx_disc* h);                /* h == NULL: last creation error of this thread */
+int ctx_disc_param_count(const ctx_disc* h);
+int ctx_disc_param_info(const ctx_disc* h, int index, const char** name, int* ndim, int64_t* shape4, int64_t* offset);
+int ctx_disc_set_params(ctx_disc* h, const float* flat, size_t n);
+int ctx_disc_get_params(ctx_disc* h, float* flat, size_t n);
+int ctx_disc_get_grads(ctx_disc* h, float* flat, size_t n);        /* of the last training step, taken at its pre-update parameters */
+int ctx_disc_set_adam_state(ctx_disc* h, const float* m, const float* v, size_t n, int64_t step);
+int ctx_disc_get_adam_state(ctx_disc* h, float* m, float* v, size_t n, int64_t* step);
+int ctx_disc_init_params(ctx_disc* h, uint64_t seed);              /* the reference's initialisers; fresh Adam slots */
+int ctx_disc_sync(ctx_disc* h);
+int ctx_disc_train(ctx_disc* h, const float* x1, const float* x2_or_time, const float* cls, const float* dom, int B, float lr, float* loss);
+int ctx_disc_train_u8(ctx_disc* h, const uint8_t* x1, const void* x2_or_time, const float* cls, const float* dom, int B, float lr,
+                      float* loss);
+int ctx_disc_logits(ctx_disc* h, const float* x1, const float* x2_or_time, int B, int softmax, float* out);
+int ctx_disc_logits_u8(ctx_disc* h, const uint8_t* x1, const void* x2_or_time, int B, int softmax, float* out);
+int ctx_disc_accuracy(ctx_disc* h, const float* x1, const float* x2_or_time, const float* cls, int B, float* acc);
+int ctx_disc_accuracy_u8(ctx_disc* h, const uint8_t* x1, const void* x2_or_time, const float* cls, int B, float* acc);
+int ctx_disc_data_upload(ctx_disc* h, const uint8_t* frames, int N, int T, const float* cls, const float* dom);
+int ctx_disc_train_epoch(ctx_disc* h, const int32_t* order, int64_t n, int batch, int shift, float lr, int with_accuracy, float* losses,
+                         float* accs);
+int ctx_disc_reward_paths(ctx_disc* h, const uint8_t* frames, int P, int T, int shift, float* probs);
+int ctx_disc_debug_read(ctx_disc* h, const char* name, float* host, size_t n);
+
 #ifdef __cplusplus
 }
 #endif
