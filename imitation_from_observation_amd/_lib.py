@@ -14,6 +14,7 @@ CTX_PREC_F32 = 0
 CTX_PREC_BF16X3 = 1
 CTX_DP_UNIQUE_ID_BYTES = 128
 CTX_DISC_TPIL, CTX_DISC_GAIL = 0, 1
+CTX_REWARD_STATS = ("d2h_bytes", "cost_calls", "split_launches", "plain_launches")      # ctx_reward_stats, in index order
 
 
 class CtxConfig(ctypes.Structure):
@@ -98,6 +99,13 @@ SIGNATURES = {
     "ctx_encode_dev": (_c.c_int, [_P, _P, _c.c_int, _F]),
     "ctx_reward_set_cache": (_c.c_int, [_P, _c.c_int, _F, _F, _c.c_int]),
     "ctx_reward_costs": (_c.c_int, [_P, _c.c_int, _U8, _c.c_int, _c.c_float, _c.c_int, _F]),
+    "ctx_reward_costs_dev": (_c.c_int, [_P, _c.c_int, _P, _c.c_int, _c.c_float, _c.c_int, _F]),
+    "ctx_reward_cache_begin": (_c.c_int, [_P, _c.c_int, _c.c_int]),
+    "ctx_reward_cache_add_dev": (_c.c_int, [_P, _c.c_int, _P, _P, _c.c_int]),
+    "ctx_reward_cache_add": (_c.c_int, [_P, _c.c_int, _U8, _U8, _c.c_int]),
+    "ctx_reward_cache_finish": (_c.c_int, [_P, _c.c_int, _c.c_int64, _c.c_int]),
+    "ctx_reward_get_cache": (_c.c_int, [_P, _c.c_int, _F, _F]),
+    "ctx_reward_stats": (_c.c_int, [_P, _c.POINTER(_c.c_int64)]),
     "ctx_train_step": (_c.c_int, [_P, _F, _F, _F, _c.c_int, _c.c_float, _F]),
     "ctx_set_dropout_seed": (_c.c_int, [_P, _c.c_uint64]),
     "ctx_train_step_u8": (_c.c_int, [_P, _U8, _U8, _U8, _c.c_int, _c.c_float, _F]),

@@ -138,6 +138,7 @@ void ctx_destroy(ctx_handle* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (void* p : h->allocs) (void)hipFree(p);
     for (auto& rc : h->rcache) { if (rc.means) (void)hipFree(rc.means); if (rc.imgs) (void)hipFree(rc.imgs); }
+    for (auto& a : h->racc) if (a.sum) (void)hipFree(a.sum);
     for (hipEvent_t e : h->prof_ev) (void)hipEventDestroy(e);
     if (h->vdata) (void)hipFree(h->vdata);
     if (h->dp_host_buf) (void)hipFree(h->dp_host_buf);
@@ -371,26 +372,48 @@ int ctx_encode(ctx_handle* h, const uint8_t* frames, int B, float* feat, float* 
     return finish(h);
 }
 
-int ctx_reward_set_cache(ctx_handle* h, int vp, const float* means, const float* imgs, int bs) {
-    if (!h) return CTX_E_INVALID;
-    if (vp < 0 || vp >= 64 || !means || !imgs || bs <= 0 || bs > h->Bm) return fail(h, CTX_E_INVALID, "bad viewpoint / batch_size");
-    if (h->cfg.variant == CTX_VARIANT_INCEPTION2) return fail(h, CTX_E_INVALID, "the device reward path takes frames, not feature maps");
-    HIP_TRY(h, hipSetDevice(h->device));
+// the viewpoint's RewardCache with room for bs rows (buffers kept when they fit), and the handle's cost scratch
+static int reward_cache_alloc(ctx_handle* h, int vp, int bs) {
     if ((int)h->rcache.size() <= vp) h->rcache.resize(vp + 1);
     ctx_handle::RewardCache& rc = h->rcache[vp];
     if (rc.means) { (void)hipFree(rc.means); (void)hipFree(rc.imgs); rc.means = rc.imgs = nullptr; }
     const size_t nm = (size_t)bs * h->F * sizeof(float), ni = (size_t)bs * h->npi * sizeof(float);
     if (hipMalloc((void**)&rc.means, nm) != hipSuccess || hipMalloc((void**)&rc.imgs, ni) != hipSuccess) return fail(h, CTX_E_NOMEM, "reward cache");
     rc.bs = bs;
-    HIP_TRY(h, hipMemcpyAsync(rc.means, means, nm, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(rc.imgs, imgs, ni, hipMemcpyHostToDevice, h->stream));
     if (!h->rcosts) TRY(dev_alloc(h, &h->rcosts, h->Bm));
+    return CTX_OK;
+}
+
+int ctx_reward_set_cache(ctx_handle* h, int vp, const float* means, const float* imgs, int bs) {
+    if (!h) return CTX_E_INVALID;
+    if (vp < 0 || vp >= 64 || !means || !imgs || bs <= 0 || bs > h->Bm) return fail(h, CTX_E_INVALID, "bad viewpoint / batch_size");
+    HIP_TRY(h, hipSetDevice(h->device));
+    TRY(reward_cache_alloc(h, vp, bs));
+    ctx_handle::RewardCache& rc = h->rcache[vp];
+    HIP_TRY(h, hipMemcpyAsync(rc.means, means, (size_t)bs * h->F * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(rc.imgs, imgs, (size_t)bs * h->npi * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    return finish(h);
+}
+
+// cost kernel(s) on input_z and on `x` = image_trans[0], then the B costs to the host: the tail of both cost entries
+static int reward_costs_tail(ctx_handle* h, const ctx_handle::RewardCache& rc, const float* x, int B, float scale, int ablation, float* costs) {
+    const int o = h->opt.v[OPT_REWARD_SPLIT];
+    const bool split = ablation != 2 && h->npi % 4 == 0 && (o < 0 ? h->npi >= RC_SPLIT_MIN_NPI : o != 0);
+    if (split && !h->rpart) TRY(dev_alloc(h, &h->rpart, (int64_t)h->Bm * reward_costs_slices(h->npi)));
+    reward_costs(h->stream, h->Z + 2ll * B * h->Fp, h->Fp, h->F, x, h->npi, rc.means, rc.imgs, rc.bs, B, scale, ablation, h->rcosts,
+                 split ? h->rpart : nullptr);
+    HIP_TRY(h, hipMemcpyAsync(costs, h->rcosts, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    h->rstats[CTX_REWARD_STAT_D2H_BYTES] += (int64_t)B * (int64_t)sizeof(float);
+    h->rstats[CTX_REWARD_STAT_COST_CALLS]++;
+    h->rstats[split ? CTX_REWARD_STAT_SPLIT_LAUNCHES : CTX_REWARD_STAT_PLAIN_LAUNCHES]++;
+    h->last_B = 0;
     return finish(h);
 }
 
 int ctx_reward_costs(ctx_handle* h, int vp, const uint8_t* frames, int npaths, float scale, int ablation, float* costs) {
     if (!h) return CTX_E_INVALID;
     if (vp < 0 || vp >= (int)h->rcache.size() || !h->rcache[vp].means) return fail(h, CTX_E_STATE, "ctx_reward_set_cache(vp = %d) first", vp);
+    TRY(need_frames(h));
     const ctx_handle::RewardCache& rc = h->rcache[vp];
     if (!frames || !costs || npaths <= 0 || ablation < 0 || ablation > 2) return fail(h, CTX_E_INVALID, "bad argument");
     const int B = npaths * rc.bs;
@@ -400,10 +423,131 @@ int ctx_reward_costs(ctx_handle* h, int vp, const uint8_t* frames, int npaths, f
     HIP_TRY(h, hipMemcpyAsync(h->u8, frames, (size_t)B * npi, hipMemcpyHostToDevice, h->stream));
     u8_to_f32(h->stream, h->u8, h->img + B * npi, B * npi);               // image_trans[0], base.py:116-119
     if (ablation != 1) TRY(forward_inference(h, B, MODE_ENCODE));         // input_z: the `conv` encoder on the frames (base.py:234-235)
-    reward_costs(h->stream, h->Z + 2ll * B * h->Fp, h->Fp, h->F, h->img + B * npi, npi, rc.means, rc.imgs, rc.bs, B, scale, ablation, h->rcosts);
-    HIP_TRY(h, hipMemcpyAsync(costs, h->rcosts, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    return reward_costs_tail(h, rc, h->img + B * npi, B, scale, ablation, costs);
+}
+
+// ... on frames (or, CTX_VARIANT_INCEPTION2, feature maps) that are on the device already: the image term reads them where they are,
+// the encoder its own slot
+int ctx_reward_costs_dev(ctx_handle* h, int vp, const float* d_frames, int npaths, float scale, int ablation, float* costs) {
+    if (!h) return CTX_E_INVALID;
+    if (vp < 0 || vp >= (int)h->rcache.size() || !h->rcache[vp].means) return fail(h, CTX_E_STATE, "no reward cache for viewpoint %d (ctx_reward_set_cache / ctx_reward_cache_finish first)", vp);
+    const ctx_handle::RewardCache& rc = h->rcache[vp];
+    if (!d_frames || !costs || npaths <= 0 || ablation < 0 || ablation > 2) return fail(h, CTX_E_INVALID, "bad argument");
+    const int B = npaths * rc.bs;
+    TRY(check_B(h, B));
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (ablation != 1) {
+        float* slot = h->img + B * h->npi;
+        if (d_frames != slot) HIP_TRY(h, hipMemcpyAsync(slot, d_frames, (size_t)B * h->npi * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+        TRY(forward_inference(h, B, MODE_ENCODE));
+    }
+    return reward_costs_tail(h, rc, d_frames, B, scale, ablation, costs);
+}
+
+// ---- the demo cache built on the device (base.py:195-223 without the host round trip of translated_z / out) ----------------------
+int ctx_reward_cache_begin(ctx_handle* h, int vp, int bs) {
+    if (!h) return CTX_E_INVALID;
+    if (vp < 0 || vp >= 64 || bs <= 0 || bs > h->Bm) return fail(h, CTX_E_INVALID, "bad viewpoint / batch_size");
+    if (h->F % 4 || h->Fp % 4 || h->npi % 4) return fail(h, CTX_E_INVALID, "the device demo cache needs featsize and H*W*C to be multiples of 4");
+    if (vp < (int)h->rcache.size() && h->rcache[vp].means && h->rcache[vp].bs != bs)
+        return fail(h, CTX_E_INVALID, "viewpoint %d holds a cache of batch_size %d, not %d", vp, h->rcache[vp].bs, bs);
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((int)h->racc.size() <= vp) h->racc.resize(vp + 1);
+    ctx_handle::RewardAcc& a = h->racc[vp];
+    const size_t n = (size_t)bs * (size_t)(h->F + h->npi);
+    if (a.sum && a.bs != bs) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(a.sum); a.sum = nullptr; }
+    if (!a.sum && hipMalloc((void**)&a.sum, n * sizeof(double)) != hipSuccess) { a.sum = nullptr; return fail(h, CTX_E_NOMEM, "hipMalloc(%zu bytes) for the demo-cache sums", n * sizeof(double)); }
+    a.bs = bs;
+    HIP_TRY(h, hipMemsetAsync(a.sum, 0, n * sizeof(double), h->stream));
+    a.live = true;
+    return CTX_OK;
+}
+
+static int reward_acc_of(ctx_handle* h, int vp, ctx_handle::RewardAcc** out) {
+    if (vp < 0 || vp >= (int)h->racc.size() || !h->racc[vp].live) return fail(h, CTX_E_STATE, "ctx_reward_cache_begin(vp = %d) first", vp);
+    *out = &h->racc[vp];
+    return CTX_OK;
+}
+
+// [src | ctx0] are in the handle's slots (ctx0 in row 0 of the ctx slot): translate against the ONE context, add the B = nvideos * bs
+// rows of translated_z and out to the sums.  Nothing is downloaded.
+static int reward_cache_add_tail(ctx_handle* h, ctx_handle::RewardAcc& a, int nvideos) {
+    const int B = nvideos * a.bs;
+    h->ctx_single = true;
+    if (residual_out(h)) bcast_row0(h->stream, h->img + 2ll * B * h->npi, h->npi, B);    // out = decode + tgtctx reads the context of every row
+    TRY(forward_inference(h, B, MODE_TRANSLATE));
+    cache_accum(h->stream, h->Z, h->Fp, h->F, a.bs, nvideos, a.sum);
+    cache_accum(h->stream, h->out, h->npi, h->npi, a.bs, nvideos, a.sum + (size_t)a.bs * h->F);
     h->last_B = 0;
     return finish(h);
+}
+
+int ctx_reward_cache_add_dev(ctx_handle* h, int vp, const float* d_src, const float* d_ctx0, int nvideos) {
+    if (!h) return CTX_E_INVALID;
+    ctx_handle::RewardAcc* a = nullptr;
+    TRY(reward_acc_of(h, vp, &a));
+    if (!d_src || !d_ctx0 || nvideos <= 0) return fail(h, CTX_E_INVALID, "bad argument");
+    if ((int64_t)nvideos * a->bs > h->Bm) return fail(h, CTX_E_INVALID, "B=%lld outside [1, max_batch=%d]", (long long)nvideos * a->bs, h->Bm);
+    const int B = nvideos * a->bs;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int64_t npi = h->npi;
+    HIP_TRY(h, hipMemcpyAsync(h->img + B * npi, d_src, (size_t)B * npi * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->img + 2ll * B * npi, d_ctx0, (size_t)npi * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    return reward_cache_add_tail(h, *a, nvideos);
+}
+
+int ctx_reward_cache_add(ctx_handle* h, int vp, const uint8_t* src, const uint8_t* ctx0, int nvideos) {
+    if (!h) return CTX_E_INVALID;
+    TRY(need_frames(h));
+    ctx_handle::RewardAcc* a = nullptr;
+    TRY(reward_acc_of(h, vp, &a));
+    if (!src || !ctx0 || nvideos <= 0) return fail(h, CTX_E_INVALID, "bad argument");
+    if ((int64_t)nvideos * a->bs > h->Bm) return fail(h, CTX_E_INVALID, "B=%lld outside [1, max_batch=%d]", (long long)nvideos * a->bs, h->Bm);
+    const int B = nvideos * a->bs;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int64_t npi = h->npi;
+    HIP_TRY(h, hipMemcpyAsync(h->u8, src, (size_t)B * npi, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->u8 + B * npi, ctx0, (size_t)npi, hipMemcpyHostToDevice, h->stream));
+    u8_to_f32(h->stream, h->u8, h->img + B * npi, (B + 1) * npi);          // [src | ctx] are adjacent in both buffers: one launch (ctx_translate)
+    return reward_cache_add_tail(h, *a, nvideos);
+}
+
+int ctx_reward_cache_finish(ctx_handle* h, int vp, int64_t nvideos_total, int distributed) {
+    if (!h) return CTX_E_INVALID;
+    ctx_handle::RewardAcc* a = nullptr;
+    TRY(reward_acc_of(h, vp, &a));
+    if (nvideos_total <= 0) return fail(h, CTX_E_INVALID, "nvideos_total must be positive");
+    if (distributed && !h->dp_comm) return fail(h, CTX_E_STATE, "distributed demo cache: ctx_dp_init first");
+    HIP_TRY(h, hipSetDevice(h->device));
+    TRY(reward_cache_alloc(h, vp, a->bs));
+    a = &h->racc[vp];
+    const ctx_handle::RewardCache& rc = h->rcache[vp];
+    const size_t nf = (size_t)a->bs * h->F, ni = (size_t)a->bs * h->npi;
+    if (distributed) TRY(dp_allreduce_dev_f64(h, a->sum, nf + ni));
+    cache_finish(h->stream, a->sum, (int64_t)nf, nvideos_total, rc.means);
+    cache_finish(h->stream, a->sum + nf, (int64_t)ni, nvideos_total, rc.imgs);
+    a->live = false;
+    TRY(finish(h));
+    (void)hipFree(a->sum);                                                  // 8 bytes per cache element: not kept between experiments
+    a->sum = nullptr;
+    return CTX_OK;
+}
+
+int ctx_reward_get_cache(ctx_handle* h, int vp, float* means, float* imgs) {
+    if (!h) return CTX_E_INVALID;
+    if (vp < 0 || vp >= (int)h->rcache.size() || !h->rcache[vp].means) return fail(h, CTX_E_STATE, "no reward cache for viewpoint %d", vp);
+    const ctx_handle::RewardCache& rc = h->rcache[vp];
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t nm = (size_t)rc.bs * h->F * sizeof(float), ni = (size_t)rc.bs * h->npi * sizeof(float);
+    if (means) { HIP_TRY(h, hipMemcpyAsync(means, rc.means, nm, hipMemcpyDeviceToHost, h->stream)); h->rstats[CTX_REWARD_STAT_D2H_BYTES] += (int64_t)nm; }
+    if (imgs) { TRY(copy_d2h(h, imgs, rc.imgs, ni)); h->rstats[CTX_REWARD_STAT_D2H_BYTES] += (int64_t)ni; }
+    return finish(h);
+}
+
+int ctx_reward_stats(const ctx_handle* h, int64_t stats[CTX_REWARD_NSTATS]) {
+    if (!h || !stats) return CTX_E_INVALID;
+    memcpy(stats, h->rstats, sizeof h->rstats);
+    return CTX_OK;
 }
 
 // d_src / d_ctx / d_tgt -> the handle's frame buffer [tgt | src | ctx]; a slot the caller filled IN PLACE (pointers of ctx_dev_frames) is not copied

@@ -80,6 +80,15 @@ int dp_wait(ctx_handle* h) {
     HIP_TRY(h, hipStreamWaitEvent(h->stream, h->dp_ev_done, 0));
     return CTX_OK;
 }
+// In-place SUM all-reduce of a DEVICE buffer of doubles (the reward hook's demo-cache accumulators, ctx_reward_cache_finish): behind
+// what the compute stream has queued, and the compute stream waits for it -- ctx_dp_allreduce_host_f64 without the host leg.
+int dp_allreduce_dev_f64(ctx_handle* h, double* d, size_t n) {
+    if (!h->dp_comm) return fail(h, CTX_E_STATE, "ctx_dp_init first");
+    HIP_TRY(h, hipEventRecord(h->dp_ev_ready, h->stream));
+    HIP_TRY(h, hipStreamWaitEvent(h->dp_stream, h->dp_ev_ready, 0));
+    RCCL_TRY(h, rccl().AllReduce(d, d, n, ncclDouble, ncclSum, h->dp_comm, h->dp_stream));
+    return dp_wait(h);
+}
 }  // namespace ctxi
 
 extern "C" {

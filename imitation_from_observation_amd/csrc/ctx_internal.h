@@ -169,6 +169,12 @@ struct ctx_handle {
     struct RewardCache { float* means = nullptr; float* imgs = nullptr; int bs = 0; };
     std::vector<RewardCache> rcache;
     float* rcosts = nullptr;
+    // ... and the cache built on the device (ctx_reward_cache_*): per viewpoint ONE float64 buffer [bs * F | bs * npi] of running sums
+    // (one buffer: ctx_reward_cache_finish all-reduces it in a single collective), live between begin and finish
+    struct RewardAcc { double* sum = nullptr; int bs = 0; bool live = false; };
+    std::vector<RewardAcc> racc;
+    float* rpart = nullptr;          // slice partials of the split cost kernel [max_batch * slices], allocated at its first launch
+    int64_t rstats[CTX_REWARD_NSTATS] = {};   // ctx_reward_stats
     float* P3 = nullptr;   // d_h4 scatter product [2B * H/2 * W/2][P3_LD]
     float* PP = nullptr;   // transposed-conv product of the starved inference launches (<= PP_IMG images): [images * hs * ws][25 ca], largest layer
     int64_t slab_floats = 0;
@@ -268,6 +274,7 @@ void fork(ctx_handle* h, int lane);
 void fire_bucket(ctx_handle* h, int64_t first);
 int dp_reduce_range(ctx_handle* h, int64_t first, int64_t count);    // ctx_dp.cpp
 void dp_teardown(ctx_handle* h);                                      // ctx_dp.cpp
+int dp_allreduce_dev_f64(ctx_handle* h, double* d, size_t n);         // ctx_dp.cpp: in place, ordered behind and in front of h->stream
 int stage_frames(ctx_handle* h, const float* d_src, const float* d_ctx, const float* d_tgt, int B);   // ctx_abi.cpp
 int nn_err_enqueue(ctx_handle* h, const float* tgt, int Bt, int nlen, int j0);                       // ctx_abi.cpp: h->nn_res[0]
 

@@ -48,7 +48,7 @@ namespace {
 struct OptDef { const char* name; int def; };
 const OptDef kOpts[OPT_COUNT] = {
     {"overlap", -1}, {"graphs", 1}, {"graph_lanes", 1}, {"posmajor", 1}, {"xcd_swizzle", 7}, {"balance", 9}, {"wconvt", 31}, {"direct3", 31}, {"dconv", 3},
-    {"rchain", 1}, {"early_adam", 1}, {"cnn_lanes", -1}, {"cnn_dconv", 1}, {"cnn_stem4", 1}, {"trace_launch", 0}, {"adam_prio", 2},
+    {"rchain", 1}, {"early_adam", 1}, {"cnn_lanes", -1}, {"cnn_dconv", 1}, {"cnn_stem4", 1}, {"trace_launch", 0}, {"adam_prio", 2}, {"reward_split", -1},
 };
 }  // namespace
 thread_local const Options* g_opt = nullptr;
@@ -737,10 +737,148 @@ __global__ __launch_bounds__(NTHREADS) void reward_cost_kernel(const float* __re
     if (threadIdx.x == 0) costs[j] = ablation == 0 ? rf + scale * ri : ablation == 1 ? scale * ri : rf;
 }
 
+// The split form for large frames (mode 'oursinception': a Mixed_7c map is 8 * 8 * 2048 = 131 072 floats at 299 x 299, and a launch
+// holds 75-250 of them): one block per (frame, slice of RC_SLICE elements) writes the slice's sum of squares to part[frame][slice];
+// reward_cost_final_kernel adds a frame's partials in slice order and applies scale and the ablation.
+// Summation order (fixed, independent of the grid): thread t of a slice adds its float4s i = t, t + 256, ... alternately into two
+// accumulators (4 terms each, left to right), a0 + a1, the wavefront tree of wave_sum, the 4 wave sums in order, then the slices in order.
+// Block order: the means / imgs rows are shared by the npaths frames j, j + bs, ... of a launch, so the PATH index runs fastest
+// through the logical block number -- and since blocks b and b + 8 share an XCD (its L2), the logical number is the block id dealt
+// back out of its round-robin: one XCD's L2 sees a contiguous run of logical blocks, i.e. all paths of a (row, slice) pair together.
+constexpr int RC_SLICE = 8192;           // floats per block: 8 float4 per thread and operand, all 16 loads issued before the first use
+__global__ __launch_bounds__(NTHREADS) void reward_cost_split_kernel(const float* __restrict__ x, int64_t npi, const float* __restrict__ imgs,
+                                                                     int bs, int npaths, int nsl, float* __restrict__ part) {
+    __shared__ float sh[4];
+    const unsigned total = gridDim.x;
+    unsigned w = blockIdx.x;
+    if (total % 8 == 0) w = (w % 8) * (total / 8) + w / 8;
+    const int p = (int)(w % (unsigned)npaths);
+    const unsigned rest = w / (unsigned)npaths;
+    const int sl = (int)(rest % (unsigned)nsl), jj = (int)(rest / (unsigned)nsl);
+    const int j = p * bs + jj;
+    const int64_t e0 = (int64_t)sl * RC_SLICE, e1 = e0 + RC_SLICE < npi ? e0 + RC_SLICE : npi;
+    const float* a = imgs + (int64_t)jj * npi;
+    const float* b = x + (int64_t)j * npi;
+    constexpr int U = RC_SLICE / (4 * NTHREADS);
+    float4 u[U], v[U];
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+        const int64_t e = e0 + ((int64_t)i * NTHREADS + threadIdx.x) * 4;
+        const bool in = e < e1;
+        u[i] = in ? ldg4(a + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+        v[i] = in ? ldg4(b + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    float acc[2] = {0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+        const float d0 = u[i].x - v[i].x, d1 = u[i].y - v[i].y, d2 = u[i].z - v[i].z, d3 = u[i].w - v[i].w;
+        acc[i & 1] += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
+    }
+    const float r = block_sum(acc[0] + acc[1], sh);
+    if (threadIdx.x == 0) part[(int64_t)j * nsl + sl] = r;
+}
+
+// one block per frame: the feature term exactly as reward_cost_kernel forms it, the image term from the slice partials
+__global__ __launch_bounds__(NTHREADS) void reward_cost_final_kernel(const float* __restrict__ feat, int ldf, int F, const float* __restrict__ means,
+                                                                     const float* __restrict__ part, int nsl, int bs, float scale,
+                                                                     int ablation, float* __restrict__ costs) {
+    __shared__ float sh[4];
+    const int j = blockIdx.x, jj = j % bs;
+    float cf = 0.f;
+    if (ablation != 1) {
+        const float* a = means + (int64_t)jj * F;
+        const float* b = feat + (int64_t)j * ldf;
+        for (int f = threadIdx.x; f < F; f += NTHREADS) { const float d = a[f] - b[f]; cf += d * d; }
+    }
+    const float rf = block_sum(cf, sh);
+    if (threadIdx.x == 0) {
+        float ri = 0.f;
+        for (int s = 0; s < nsl; ++s) ri += part[(int64_t)j * nsl + s];
+        costs[j] = ablation == 0 ? rf + scale * ri : scale * ri;
+    }
+}
+
+int reward_costs_slices(int64_t npi) { return (int)((npi + RC_SLICE - 1) / RC_SLICE); }
+
 void reward_costs(hipStream_t s, const float* feat, int ldf, int F, const float* x, int64_t npi, const float* means, const float* imgs,
-                  int bs, int nframes, float scale, int ablation, float* costs) {
+                  int bs, int nframes, float scale, int ablation, float* costs, float* part) {
+    if (part) {
+        const int nsl = reward_costs_slices(npi);
+        hipLaunchKernelGGL(reward_cost_split_kernel, dim3((unsigned)(nframes * nsl)), dim3(NTHREADS), 0, s, x, npi, imgs, bs, nframes / bs, nsl, part);
+        hipLaunchKernelGGL(reward_cost_final_kernel, dim3((unsigned)nframes), dim3(NTHREADS), 0, s, feat, ldf, F, means, (const float*)part, nsl, bs,
+                           scale, ablation, costs);
+        return;
+    }
     hipLaunchKernelGGL(reward_cost_kernel, dim3((unsigned)nframes), dim3(NTHREADS), 0, s, feat, ldf, F, x, npi, means, imgs, bs, scale,
                        ablation, costs);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The demo cache of the reward hook built where the translated videos already are (rllab/sampler/base.py:195-223):
+//   acc[j][e] += sum_v x[(v * bs + j) * ld + e]   (e < cols; videos v in index order, in float64 -- np.mean's accumulation of the
+//   host path, reward.py), then  out = f32(acc / n).  One pass over x, no atomics: an accumulator element belongs to one thread.
+// cols, ld multiples of 4; rows 16-byte aligned.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(NTHREADS) void cache_accum_kernel(const float* __restrict__ x, int64_t ld, int64_t cols, int bs, int nvid,
+                                                               double* __restrict__ acc) {
+    const int64_t c4 = cols / 4, n4 = c4 * bs;
+    for (int64_t i = (int64_t)blockIdx.x * NTHREADS + threadIdx.x; i < n4; i += (int64_t)gridDim.x * NTHREADS) {
+        const int64_t j = i / c4, e = (i - j * c4) * 4;
+        const float* src = x + j * ld + e;
+        const int64_t vstride = (int64_t)bs * ld;
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+        int v = 0;
+        for (; v + 4 <= nvid; v += 4) {        // four independent 16-byte loads in flight, added in video order
+            const float4 a = ldg4(src + v * vstride), b = ldg4(src + (v + 1) * vstride), c = ldg4(src + (v + 2) * vstride),
+                         d = ldg4(src + (v + 3) * vstride);
+            s0 += a.x; s1 += a.y; s2 += a.z; s3 += a.w;
+            s0 += b.x; s1 += b.y; s2 += b.z; s3 += b.w;
+            s0 += c.x; s1 += c.y; s2 += c.z; s3 += c.w;
+            s0 += d.x; s1 += d.y; s2 += d.z; s3 += d.w;
+        }
+        for (; v < nvid; ++v) {
+            const float4 a = ldg4(src + v * vstride);
+            s0 += a.x; s1 += a.y; s2 += a.z; s3 += a.w;
+        }
+        double2* dst = reinterpret_cast<double2*>(acc + j * cols + e);
+        double2 lo = dst[0], hi = dst[1];
+        lo.x += s0; lo.y += s1; hi.x += s2; hi.y += s3;
+        dst[0] = lo; dst[1] = hi;
+    }
+}
+
+void cache_accum(hipStream_t s, const float* x, int64_t ld, int64_t cols, int bs, int nvid, double* acc) {
+    const int64_t n4 = cols / 4 * bs;
+    const int64_t cap = (int64_t)dev_info().cus * 8;
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((n4 + NTHREADS - 1) / NTHREADS, cap));
+    hipLaunchKernelGGL(cache_accum_kernel, dim3((unsigned)blocks), dim3(NTHREADS), 0, s, x, ld, cols, bs, nvid, acc);
+}
+
+__global__ __launch_bounds__(NTHREADS) void cache_finish_kernel(const double* __restrict__ acc, int64_t n, double count, float* __restrict__ out) {
+    for (int64_t i = ((int64_t)blockIdx.x * NTHREADS + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * NTHREADS * 4) {
+        const double2 lo = *reinterpret_cast<const double2*>(acc + i), hi = *reinterpret_cast<const double2*>(acc + i + 2);
+        *reinterpret_cast<float4*>(out + i) = make_float4((float)(lo.x / count), (float)(lo.y / count), (float)(hi.x / count), (float)(hi.y / count));
+    }
+}
+
+void cache_finish(hipStream_t s, const double* acc, int64_t n, int64_t count, float* out) {
+    const int64_t cap = (int64_t)dev_info().cus * 8;
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((n / 4 + NTHREADS - 1) / NTHREADS, cap));
+    hipLaunchKernelGGL(cache_finish_kernel, dim3((unsigned)blocks), dim3(NTHREADS), 0, s, acc, n, (double)count, out);
+}
+
+// rows 1 .. rows-1 of buf [rows][n] = row 0 (n a multiple of 4): `[context] * batch_size` (base.py:217-218) in one launch
+__global__ __launch_bounds__(NTHREADS) void bcast_row0_kernel(float* __restrict__ buf, int64_t n, int64_t total) {
+    for (int64_t i = ((int64_t)blockIdx.x * NTHREADS + threadIdx.x) * 4; i < total; i += (int64_t)gridDim.x * NTHREADS * 4)
+        *reinterpret_cast<float4*>(buf + n + i) = ldg4(buf + i % n);
+}
+
+void bcast_row0(hipStream_t s, float* buf, int64_t n, int rows) {
+    if (rows < 2) return;
+    const int64_t total = n * (rows - 1);
+    const int64_t cap = (int64_t)dev_info().cus * 8;
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((total / 4 + NTHREADS - 1) / NTHREADS, cap));
+    hipLaunchKernelGGL(bcast_row0_kernel, dim3((unsigned)blocks), dim3(NTHREADS), 0, s, buf, n, total);
 }
 
 // ------------------------------------------------------------------------------------------------

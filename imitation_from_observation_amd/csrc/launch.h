@@ -186,8 +186,22 @@ void losses(hipStream_t s, const float* out, const float* tgt, float* dout, int6
 
 // per-frame reward cost (rllab/sampler/base.py:243-249): costs[j] = |means[j % bs] - feat[j]|^2 + scale * |imgs[j % bs] - x[j]|^2
 // (ablation 1: image term only, 2: feature term only)
+// part (nullable): scratch of nframes * reward_costs_slices(npi) floats.  With it (npi % 4 == 0, ablation != 2) the image term takes
+// the split form -- one block per (frame, 8192-element slice), then the slices in order (kernels.hip gives the summation order);
+// without it the one-block-per-frame kernel and its bits.  The handles split from RC_SPLIT_MIN_NPI elements per frame (option
+// reward_split): above every pixel frame of the reference's launchers (64x64x3 = 12 288, 36x64x3 = 48x48x3 = 6 912) and
+// ContextAEInception2's 2x2x2048 maps at 125 x 125 (8 192: one slice, nothing to split), below its 8x8x2048 maps at 299 x 299
+// (131 072: 16 slices).
+constexpr int64_t RC_SPLIT_MIN_NPI = 32768;
+int reward_costs_slices(int64_t npi);
 void reward_costs(hipStream_t s, const float* feat, int ldf, int F, const float* x, int64_t npi, const float* means, const float* imgs,
-                  int bs, int nframes, float scale, int ablation, float* costs);
+                  int bs, int nframes, float scale, int ablation, float* costs, float* part = nullptr);
+
+// the reward hook's demo cache on the device (base.py:195-223): acc[j][e] += sum over the nvid videos of x[(v * bs + j) * ld + e]
+// (e < cols, float64, video order), out = f32(acc / count); bcast_row0: rows 1.. of buf [rows][n] = row 0.  cols, ld, n: multiples of 4.
+void cache_accum(hipStream_t s, const float* x, int64_t ld, int64_t cols, int bs, int nvid, double* acc);
+void cache_finish(hipStream_t s, const double* acc, int64_t n, int64_t count, float* out);
+void bcast_row0(hipStream_t s, float* buf, int64_t n, int rows);
 
 // db[c] = sum_rows x[row][c], deterministic two-stage; scratch >= COLSUM_SPLITS * max(C, 4) floats
 constexpr int COLSUM_SPLITS = 512;

@@ -29,6 +29,8 @@ enum Opt {
     OPT_TRACE_LAUNCH,  // 1: one stderr line per distinct implicit-GEMM launch shape (diagnostics)
     OPT_ADAM_PRIO,     // HIP priority of the early-Adam stream, read at create: 1 low (its own hardware queue), 0 normal, -1 high; 2 (default) = 1 for
                        // exact-f32 handles, 0 for split-bf16 ones; reads back resolved
+    OPT_REWARD_SPLIT,  // the reward hook's cost on frames of a multiple of 4 elements: -1 (default) = the split kernel from 32768 elements per frame
+                       // (launch.h: RC_SPLIT_MIN_NPI), 0 = always one block per frame, 1 = always split (measurements)
     OPT_COUNT
 };
 

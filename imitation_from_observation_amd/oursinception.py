@@ -63,6 +63,44 @@ class InceptionTranslator:
         feat = self.tr.encode_dev(d, fr.shape[0])
         return feat, (self.front.output(fr.shape[0]) if return_frames else None)
 
+    # ------------------------------------------------------------------ the reward hook with maps and demo cache resident on the device
+    # (TranslatorReward(resident=True)).  Deliberately NOT named reward_set_cache / reward_costs: those names are what the host-path
+    # hook (resident=False) dispatches on, and with it this class keeps today's path bit for bit.
+    def reward_costs_u8(self, vp, frames, scale, ablation_type="None"):
+        """uint8 frames [npaths*bs,H,W,3] -> costs f32 [npaths, bs] of base.py:243-249: frames -> front end -> the translator's
+        encoder and cost kernel on the front end's output buffer (the image term compares feature maps, base.py:132).  Only the
+        costs come back."""
+        fr = np.asarray(frames)
+        bs = self.tr._reward_bs
+        if fr.shape[0] % bs:
+            raise ValueError(f"frames must be [npaths*{bs},H,W,3], got {fr.shape}")
+        d = self.front.features_u8_dev(fr)
+        return self.tr.reward_costs_dev(vp, d, fr.shape[0] // bs, scale, ablation_type)
+
+    def reward_cache_begin(self, vp, bs):
+        self.tr.reward_cache_begin(vp, bs)
+
+    def reward_cache_add(self, vp, obs_src, obs_tgt0):
+        """uint8 demo frames [nvideos*bs,H,W,3] and the ONE context frame [H,W,3]: [src | ctx] through the front end in one pass (as
+        translate), then the translator adds translated_z / out of every video to the device sums."""
+        src = np.asarray(obs_src)
+        ctx = np.asarray(obs_tgt0)
+        bs = getattr(self.tr, "_cache_bs", 0)
+        if not bs or ctx.ndim != 3 or src.shape[0] % bs:
+            raise ValueError(f"expected [nvideos*{bs},H,W,3] frames and one [H,W,3] context after reward_cache_begin")
+        B = src.shape[0]
+        d = self.front.features_u8_dev(np.concatenate([src, ctx[None]]))
+        self.tr.reward_cache_add_dev(vp, d, d + B * self._per, B // bs)
+
+    def reward_cache_finish(self, vp, nvideos_total, distributed=False):
+        self.tr.reward_cache_finish(vp, nvideos_total, distributed)
+
+    def reward_get_cache(self, vp, means=True, imgs=True):
+        return self.tr.reward_get_cache(vp, means, imgs)
+
+    def reward_stats(self):
+        return self.tr.reward_stats()
+
     def _triple_dev(self, src, ctx, tgt):
         B = len(src)
         if 3 * B > self.front.max_images:

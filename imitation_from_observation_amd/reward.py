@@ -17,22 +17,66 @@ from __future__ import annotations
 import numpy as np
 
 
+class _ResidentCacheView:
+    """TranslatorReward.means / .imgs of a resident hook: view[vp] fetches that viewpoint's cache from the device (reward_get_cache)."""
+
+    def __init__(self, tr, nvp, which):
+        self._tr, self._nvp, self._which = tr, nvp, which
+
+    def __len__(self):
+        return self._nvp
+
+    def __getitem__(self, vp):
+        if not 0 <= vp < self._nvp:
+            raise IndexError(vp)
+        return self._tr.reward_get_cache(vp, means=self._which == 0, imgs=self._which == 1)[self._which]
+
+    def __iter__(self):
+        return (self[vp] for vp in range(self._nvp))
+
+
 class TranslatorReward:
-    def __init__(self, translator, nvp, scale, name="strike", ablation_type="None", batch_size=25):
+    def __init__(self, translator, nvp, scale, name="strike", ablation_type="None", batch_size=25, resident=False):
+        """resident=True: demo cache and cost stay on the device for EVERY translator type (mode 'oursinception' included) -- the cache
+        is built there (reward_cache_begin / _add / _finish: neither the translated videos nor the finished cache cross PCIe), the
+        per-path cost is computed next to the encoder (reward_costs_u8: only [paths, bs] floats come back), and `means` / `imgs` are
+        views that fetch a viewpoint's cache on demand.  resident=False (default): today's paths, bit for bit."""
         if ablation_type not in ("None", "nofeat", "noimage"):
             # 'recon' reads an undefined `image_recon` in the reference (base.py:250-252; SURVEY.md 3.4-f)
             raise NotImplementedError(f"ablation_type {ablation_type!r} is not runnable in the reference either")
         self.tr, self.nvp, self.scale, self.name = translator, int(nvp), float(scale), name
         self.ablation_type, self.batch_size = ablation_type, int(batch_size)
         self.skip = 2 if name in ("real", "sweep") else 1        # base.py:209-211
-        self.means, self.imgs = None, None
+        self.resident = bool(resident)
+        self._means, self._imgs, self._resident_built = None, None, False
         self.validdata = None                                    # set_demos(): the cache is then built lazily on the first path
         # mode 'oursinception' caps the demo videos at 50 (base.py:203-204); every other mode uses them all
         self.nvideos_cap = 50 if hasattr(translator, "front") else None
 
+    # means[vp] [bs, featsize] / imgs[vp] [bs, H, W, C]: host lists (resident=False), device-backed views (resident=True); None = no cache yet
+    @property
+    def means(self):
+        if self.resident:
+            return _ResidentCacheView(self.tr, self.nvp, 0) if self._resident_built else None
+        return self._means
+
+    @means.setter
+    def means(self, v):
+        self._means = v
+
+    @property
+    def imgs(self):
+        if self.resident:
+            return _ResidentCacheView(self.tr, self.nvp, 1) if self._resident_built else None
+        return self._imgs
+
+    @imgs.setter
+    def imgs(self, v):
+        self._imgs = v
+
     @classmethod
     def for_sampler(cls, name, imsize, nvp, scale, modelname=None, ablation_type="None", batch_size=25,
-                    paths_per_launch=10, device=0, mode="ours", inception_ckpt=None):
+                    paths_per_launch=10, device=0, mode="ours", inception_ckpt=None, resident=False):
         """What BaseSampler.initialize() sets up for mode 'ours' (base.py:113-145): the model class follows the
         experiment name -- ContextAEReal for 'real'/'sweep', ContextSkipNew otherwise (:134-137) -- on the
         sampler's imsize, restored from `modelname` when given (:138).  mode 'oursinception' (:121-132): frames go
@@ -46,13 +90,13 @@ class TranslatorReward:
                 it.front.load(inception_ckpt)
             if modelname is not None:
                 it.tr.load(modelname)
-            return cls(it, nvp, scale, name=name, ablation_type=ablation_type, batch_size=batch_size)
+            return cls(it, nvp, scale, name=name, ablation_type=ablation_type, batch_size=batch_size, resident=resident)
         real = name in ("real", "sweep")
         tr = Translator(imsize[0], imsize[1], featsize=100 if real else 1024, max_batch=batch_size * paths_per_launch,
                         device=device, variant="real" if real else "skipnew")
         if modelname is not None:
             tr.load(modelname)
-        return cls(tr, nvp, scale, name=name, ablation_type=ablation_type, batch_size=batch_size)
+        return cls(tr, nvp, scale, name=name, ablation_type=ablation_type, batch_size=batch_size, resident=resident)
 
     # ------------------------------------------------------------------ base.py:195-223
     @staticmethod
@@ -75,6 +119,8 @@ class TranslatorReward:
         the partial feature / frame sums are combined with ONE all-reduce per viewpoint -- the demo means are a plain sum
         over videos.  The group is the translator's own RCCL group when it has one (Translator.dp_init:
         ctx_dp_allreduce_host_f64, no torch in the sampler process), else an initialised torch.distributed group."""
+        if self.resident:
+            return self._build_demo_cache_resident(validdata, first_frames, distributed)
         validdata = np.asarray(validdata)
         nvid = validdata.shape[1]
         if self.nvideos_cap is not None:
@@ -122,6 +168,38 @@ class TranslatorReward:
             self.imgs.append((isum / nvid).astype(np.float32))             # np.mean(timgs, axis=0), base.py:222
             if hasattr(self.tr, "reward_set_cache"):                       # the cost is then computed on the device, next to the encoder
                 self.tr.reward_set_cache(vp, self.means[vp], self.imgs[vp])
+        return self
+
+    def _build_demo_cache_resident(self, validdata, first_frames, distributed):
+        """build_demo_cache with sums and cache on the device: the same videos in the same order through the same translate launches,
+        added in float64 and divided once (what the host path does with numpy), but nothing is downloaded and nothing uploaded.
+        distributed=True needs the translator's own RCCL group (dp_init): the sums are all-reduced where they are."""
+        validdata = np.asarray(validdata)
+        nvid = validdata.shape[1]
+        if self.nvideos_cap is not None:
+            nvid = min(nvid, self.nvideos_cap)
+        raw_u8 = validdata.dtype == np.uint8
+        bs = self.batch_size
+        per_call = max(1, self.tr.max_batch // bs)
+        rank, world = 0, 1
+        if distributed:
+            own = getattr(self.tr, "dp_world", None)
+            rank, world = own() if callable(own) else (0, 0)
+            if world < 1:
+                raise RuntimeError("a distributed resident demo cache is all-reduced on the device: the translator needs its own RCCL "
+                                   "group (dp_init) -- or build it with resident=False over torch.distributed")
+        mine = list(range(rank, nvid, world))
+        self._resident_built = False
+        for vp in range(self.nvp):
+            ctx = np.ascontiguousarray(first_frames[vp], dtype=np.uint8)
+            self.tr.reward_cache_begin(vp, bs)
+            for i0 in range(0, len(mine), per_call):
+                vids = mine[i0:i0 + per_call]
+                u8 = np.concatenate([validdata[::self.skip, i][:bs] if raw_u8 else
+                                     ((validdata[::self.skip, i][:bs] + 1) * 127.5).astype(np.uint8) for i in vids])
+                self.tr.reward_cache_add(vp, u8, ctx)
+            self.tr.reward_cache_finish(vp, nvid, distributed=distributed and world > 1)
+        self._resident_built = True
         return self
 
     # ------------------------------------------------------------------ base.py:232-252
@@ -186,14 +264,17 @@ class TranslatorReward:
             for p0 in range(0, len(paths), per_call):
                 grp = range(p0, min(len(paths), p0 + per_call))
                 u8 = np.concatenate([np.stack([fr[vp] for fr in frames[p]]).astype(np.uint8) for p in grp])
-                if hasattr(self.tr, "reward_costs"):
+                if self.resident:
+                    # every translator type: encoder (behind the front end in mode 'oursinception') + cost on the device
+                    dev = self.tr.reward_costs_u8(vp, u8, self.scale, self.ablation_type)
+                elif hasattr(self.tr, "reward_costs"):
                     # encoder + cost on the device: only the [paths, bs] costs cross PCIe (not the 4-bytes-per-pixel frames)
                     dev = self.tr.reward_costs(vp, u8, self.scale, self.ablation_type)
                 else:
                     feats, x = self.tr.encode(u8)                          # [input_z, image_trans[0]], base.py:234-235
                 for k, p in enumerate(grp):
                     sl = slice(k * bs, (k + 1) * bs)
-                    c = dev[k] if hasattr(self.tr, "reward_costs") else self._costs_from(feats[sl], x[sl], vp)
+                    c = dev[k] if self.resident or hasattr(self.tr, "reward_costs") else self._costs_from(feats[sl], x[sl], vp)
                     # 'None' accumulates over viewpoints (costs += ...); the ablations overwrite (costs = ...)
                     costs[p] = costs[p] + c if self.ablation_type == "None" else c
         return costs

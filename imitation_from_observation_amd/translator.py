@@ -350,10 +350,11 @@ class Translator:
     ABLATIONS = {"None": 0, "nofeat": 1, "noimage": 2}
 
     def reward_set_cache(self, vp, means, imgs):
-        """Keep the demo cache of viewpoint vp (means [bs, featsize], imgs [bs,H,W,3]; base.py:221-222) on the device."""
+        """Keep the demo cache of viewpoint vp (means [bs, featsize], imgs [bs,H,W,3] -- feature maps [bs,H,W,C] for variant
+        "inception2"; base.py:221-222) on the device."""
         means = _f32(means)
         bs = means.shape[0]
-        means, imgs = _f32(means, (bs, self.featsize)), _f32(imgs, (bs, self.H, self.W, 3))
+        means, imgs = _f32(means, (bs, self.featsize)), _f32(imgs, (bs, self.H, self.W, self.C))
         self._ck(self._lib.ctx_reward_set_cache(self._h, int(vp), _fp(means), _fp(imgs), bs))
         self._reward_bs = bs
 
@@ -367,6 +368,58 @@ class Translator:
         costs = np.empty((npaths, bs), np.float32)
         self._ck(self._lib.ctx_reward_costs(self._h, int(vp), _up(fr), npaths, float(scale), self.ABLATIONS[ablation_type], _fp(costs)))
         return costs
+
+    # ------------------------------------------------------------------ ... with frames and demo cache resident on the device
+    def reward_costs_dev(self, vp, d_frames, npaths, scale, ablation_type="None"):
+        """reward_costs on frames that are on the device already: d_frames = integer address of f32 [npaths*bs,H,W,C] (frames in
+        [-1,1]; feature maps for variant "inception2"), complete in this handle's stream order.  costs f32 [npaths, bs]."""
+        costs = np.empty((int(npaths), self._reward_bs), np.float32)
+        self._ck(self._lib.ctx_reward_costs_dev(self._h, int(vp), ctypes.c_void_p(d_frames), int(npaths), float(scale),
+                                                self.ABLATIONS[ablation_type], _fp(costs)))
+        return costs
+
+    def reward_costs_u8(self, vp, frames, scale, ablation_type="None"):
+        """The resident reward hook's cost call on uint8 frames (TranslatorReward(resident=True)): reward_costs."""
+        return self.reward_costs(vp, frames, scale, ablation_type)
+
+    def reward_cache_begin(self, vp, bs):
+        """Start the demo cache of viewpoint vp ON THE DEVICE (base.py:195-223): zeroed float64 sums [bs, featsize], [bs,H,W,C]."""
+        self._ck(self._lib.ctx_reward_cache_begin(self._h, int(vp), int(bs)))
+        self._cache_bs = int(bs)
+
+    def reward_cache_add(self, vp, obs_src, obs_tgt0):
+        """Translate uint8 demo frames [nvideos*bs,H,W,3] against the ONE context frame [H,W,3] and add translated_z / out of every
+        video to the sums, in video order; nothing comes back."""
+        bs = getattr(self, "_cache_bs", 0)
+        src = _u8(obs_src)
+        if not bs or src.ndim != 4 or src.shape[1:] != (self.H, self.W, 3) or src.shape[0] % bs:
+            raise ValueError(f"obs_src must be [nvideos*{bs},{self.H},{self.W},3] after reward_cache_begin, got {src.shape}")
+        ctx0 = _u8(obs_tgt0, (self.H, self.W, 3))
+        self._ck(self._lib.ctx_reward_cache_add(self._h, int(vp), _up(src), _up(ctx0), src.shape[0] // bs))
+
+    def reward_cache_add_dev(self, vp, d_src, d_ctx0, nvideos):
+        """reward_cache_add on DEVICE inputs: integer addresses of f32 [nvideos*bs,H,W,C] and [H,W,C]."""
+        self._ck(self._lib.ctx_reward_cache_add_dev(self._h, int(vp), ctypes.c_void_p(d_src), ctypes.c_void_p(d_ctx0), int(nvideos)))
+
+    def reward_cache_finish(self, vp, nvideos_total, distributed=False):
+        """cache = f32(sums / nvideos_total) into the viewpoint's device cache (what reward_set_cache would have uploaded).
+        distributed=True (collective, after dp_init): the ranks' sums are all-reduced on the device first."""
+        self._ck(self._lib.ctx_reward_cache_finish(self._h, int(vp), int(nvideos_total), int(bool(distributed))))
+        self._reward_bs = self._cache_bs
+
+    def reward_get_cache(self, vp, means=True, imgs=True):
+        """Host copies (means [bs, featsize], imgs [bs,H,W,C]) of viewpoint vp's device cache; None where not asked for."""
+        bs = self._reward_bs
+        m = np.empty((bs, self.featsize), np.float32) if means else None
+        i = np.empty((bs, self.H, self.W, self.C), np.float32) if imgs else None
+        self._ck(self._lib.ctx_reward_get_cache(self._h, int(vp), _fp(m) if means else None, _fp(i) if imgs else None))
+        return m, i
+
+    def reward_stats(self):
+        """Counters of this handle's reward calls (ctx_reward_stats): d2h_bytes, cost_calls, split_launches, plain_launches."""
+        st = (ctypes.c_int64 * len(_lib.CTX_REWARD_STATS))()
+        self._ck(self._lib.ctx_reward_stats(self._h, st))
+        return dict(zip(_lib.CTX_REWARD_STATS, (int(v) for v in st)))
 
     # ------------------------------------------------------------------ training
     def _triple(self, src, ctx, tgt):

@@ -47,7 +47,8 @@ extern "C" {
                                ctx_dp_train_step_sampled / ctx_dp_eval_sampled, ctx_prof_entry.useful_frac; 4: ctx_dev_frames;
                                still 4 (additions only): ctx_vjp_args, ctx_dev_forward_vjp, ctx_dev_backward_vjp, ctx_params_written;
                                CTX_CNN_AVGPOOL_VALID / CTX_CNN_CONV_LINEAR, ctx_cnn_stats_*, ctx_cnn_reward_*; ctx_nn_err,
-                               ctx_dp_nn_err, ctx_cnn_demos_upload, ctx_cnn_forward_sampled_dev */
+                               ctx_dp_nn_err, ctx_cnn_demos_upload, ctx_cnn_forward_sampled_dev; ctx_reward_costs_dev, ctx_reward_cache_*,
+                               ctx_reward_get_cache, ctx_reward_stats, option reward_split */
 
 enum {
     CTX_OK = 0,
@@ -144,6 +145,8 @@ const char* ctx_last_error(const ctx_handle* h);
  *   trace_launch 0   one stderr line per distinct implicit-GEMM launch shape
  *   adam_prio    2   HIP priority of the early-Adam stream (1 low: its own hardware queue; 0 normal; -1 high; 2 = low for exact-f32 handles,
  *                    normal for split-bf16 ones, reads back resolved)  [fixed at create]
+ *   reward_split -1  the reward hook's image term (ctx_reward_costs / ctx_reward_costs_dev): -1 = the split kernel for frames of >= 32768
+ *                    elements, 0 = always one block per frame, 1 = always split (frames of a multiple of 4 elements; measurements)
  * Results never depend on a switch beyond f32 summation order -- tested value by value (tests/test_gpu_options.py, against the default
  * switches on the bench's launch shapes; the defaults themselves are what every oracle suite runs):
  *   ContextSkipNew 64x64 B = 256:  overlap 0 | posmajor 0 | xcd_swizzle 0 1 2 3 4 5 6 | balance 0 1 2 3 4 5 8 13 | wconvt 0 1 3 5 7 15 23 29 |
@@ -208,6 +211,48 @@ int ctx_encode_dev(ctx_handle* h, const float* d_frames, int B, float* feat);
  * over PCIe instead of the preprocessed frames (49 MB at 40 paths). */
 int ctx_reward_set_cache(ctx_handle* h, int vp, const float* means, const float* imgs, int bs);
 int ctx_reward_costs(ctx_handle* h, int vp, const uint8_t* frames, int npaths, float scale, int ablation, float* costs);
+/* For CTX_VARIANT_INCEPTION2 -- mode 'oursinception', where image_trans IS the feature tensor (base.py:132) -- ctx_reward_set_cache
+ * takes  imgs [bs,H,W,C]  feature maps; ctx_reward_costs (uint8 frames) is refused there like the other uint8 entries.
+ * ctx_reward_costs_dev: the same cost on frames that are ALREADY on the device:  d_frames  f32 [npaths*bs,H,W,C] -- frames in [-1,1]
+ * for the pixel variants, Mixed_7c maps for CTX_VARIANT_INCEPTION2 (e.g. the output buffer of ctx_cnn_forward_u8_dev on the same
+ * stream).  The `conv` encoder runs on a copy in the handle's own slot (not for ablation 1; no copy when d_frames is that slot,
+ * ctx_dev_frames), the image term reads d_frames where they are; npaths*bs floats come back.  Stream contract of ctx_encode_dev:
+ * d_frames must be complete in the handle's stream order; the call returns after the stream has drained.
+ * Frames of >= 32768 elements (8x8x2048 maps at 299 x 299: 131072) take a split cost kernel -- one block per (frame, 8192-element
+ * slice), the slices then added in order; smaller frames the one-block-per-frame kernel, in both entries. */
+int ctx_reward_costs_dev(ctx_handle* h, int vp, const float* d_frames, int npaths, float scale, int ablation, float* costs);
+
+/* The demo cache built on the device (base.py:195-223: translate every demo video into the rollout's context, np.mean over the
+ * videos of translated_z and out) -- neither the translated frames / maps nor the finished cache cross PCIe:
+ *   ctx_reward_cache_begin(h, vp, bs)      zeroed float64 sums [bs, featsize] and [bs, H*W*C] for viewpoint vp; again = reset.
+ *                                          CTX_E_INVALID when vp already holds a cache of another bs.
+ *   ctx_reward_cache_add_dev(h, vp, d_src, d_ctx0, nvideos)
+ *                                          d_src f32 [nvideos*bs,H,W,C] and ONE context d_ctx0 [H,W,C] on the device (`[context] *
+ *                                          batch_size`, base.py:217-218): one translate of nvideos*bs rows (<= max_batch), then
+ *                                          sums[j] += translated_z / out of row v*bs + j, v = 0 .. nvideos-1 in order (float64).
+ *   ctx_reward_cache_add(h, vp, src, ctx0, nvideos)   the same from host uint8 frames (pixel variants).
+ *   ctx_reward_cache_finish(h, vp, nvideos_total, distributed)
+ *                                          cache = f32(sums / nvideos_total), rounded once (np.mean(tfeats, axis=0), :221-222), written
+ *                                          into the viewpoint's cache -- what ctx_reward_set_cache would have received.
+ *                                          distributed != 0 (handle inside a ctx_dp_init group, else CTX_E_STATE; collective): the
+ *                                          sums are first SUM-all-reduced in place over the ranks (ncclDouble), each rank having
+ *                                          added its shard of the videos.  Ends the accumulation: add / finish need a new begin.
+ *   ctx_reward_get_cache(h, vp, means, imgs)   host copies of the cache [bs, featsize] / [bs,H,W,C] (either nullable).
+ * add / finish before begin: CTX_E_STATE.
+ * ctx_reward_stats: counters of this handle's ctx_reward_* calls since create (tests read the PCIe property from them):
+ *   [CTX_REWARD_STAT_D2H_BYTES] bytes of device-to-host copies issued, [.._COST_CALLS] cost calls, [.._SPLIT_LAUNCHES] /
+ *   [.._PLAIN_LAUNCHES] cost calls that took the split / the one-block-per-frame kernel. */
+#define CTX_REWARD_STAT_D2H_BYTES 0
+#define CTX_REWARD_STAT_COST_CALLS 1
+#define CTX_REWARD_STAT_SPLIT_LAUNCHES 2
+#define CTX_REWARD_STAT_PLAIN_LAUNCHES 3
+#define CTX_REWARD_NSTATS 4
+int ctx_reward_cache_begin(ctx_handle* h, int vp, int bs);
+int ctx_reward_cache_add_dev(ctx_handle* h, int vp, const float* d_src, const float* d_ctx0, int nvideos);
+int ctx_reward_cache_add(ctx_handle* h, int vp, const uint8_t* src, const uint8_t* ctx0, int nvideos);
+int ctx_reward_cache_finish(ctx_handle* h, int vp, int64_t nvideos_total, int distributed);
+int ctx_reward_get_cache(ctx_handle* h, int vp, float* means, float* imgs);
+int ctx_reward_stats(const ctx_handle* h, int64_t stats[CTX_REWARD_NSTATS]);
 
 /* ---- training --------------------------------------------------------------------------------- */
 /* src/ctx/tgt [B,H,W,3] f32 in [-1,1] (tfinput[0], [1], [2]).  scalars = {loss, simloss, recon1,
