@@ -5,5 +5,6 @@ this package is the thin Python host the reference's rllab reward hook / trainin
 """
 from .translator import CtxError, Translator  # noqa: F401
 from .third_person import ConvDiscriminator, DomainConfusionVelocityDiscriminator, ThirdPersonCost  # noqa: F401
+from .resize import FrameResizer  # noqa: F401
 
-__all__ = ["Translator", "CtxError", "DomainConfusionVelocityDiscriminator", "ConvDiscriminator", "ThirdPersonCost"]
+__all__ = ["Translator", "CtxError", "DomainConfusionVelocityDiscriminator", "ConvDiscriminator", "ThirdPersonCost", "FrameResizer"]

@@ -56,6 +56,7 @@ _c = ctypes
 _P = _c.c_void_p
 _F = _c.POINTER(_c.c_float)
 _U8 = _c.POINTER(_c.c_uint8)
+_I32 = _c.POINTER(_c.c_int32)
 _CFG = _c.POINTER(CtxConfig)
 _DCFG = _c.POINTER(CtxDiscConfig)
 
@@ -194,6 +195,14 @@ SIGNATURES = {
     "ctx_disc_train_epoch": (_c.c_int, [_P, _c.POINTER(_c.c_int32), _c.c_int64, _c.c_int, _c.c_int, _c.c_float, _c.c_int, _F, _F]),
     "ctx_disc_reward_paths": (_c.c_int, [_P, _U8, _c.c_int, _c.c_int, _c.c_int, _F]),
     "ctx_disc_debug_read": (_c.c_int, [_P, _c.c_char_p, _F, _c.c_size_t]),
+    "ctx_resize_coeffs": (_c.c_int, [_c.c_int, _c.c_int, _I32, _I32, _I32, _c.POINTER(_c.c_int)]),
+    "ctx_resize_create": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _c.POINTER(_P)]),
+    "ctx_resize_destroy": (None, [_P]),
+    "ctx_resize_last_error": (_c.c_char_p, [_P]),
+    "ctx_resize_u8": (_c.c_int, [_P, _U8, _c.c_int, _U8]),
+    "ctx_resize_f32_dev": (_c.c_int, [_P, _U8, _c.c_int, _P, _c.POINTER(_P)]),
+    "ctx_resize_sync": (_c.c_int, [_P]),
+    "ctx_resize_profile": (_c.c_int, [_P, _U8, _c.c_int, _c.c_int, _F, _F]),
 }
 
 _lib = None

@@ -15,7 +15,10 @@ What is here:
   * `build_vdata` -- the loop :59-96 over DECODED videos (arrays [frames, H, W, 3] uint8 or a callable that returns them): mp4
     decoding itself needs imageio + ffmpeg, which this image does not have, so the container of frames comes in from outside;
     everything after `vid.get_data(j)` is the reference's.
-Host-side integer / float arithmetic only (it runs once per experiment, before training): no device code.
+  * `device_resize` -- the same resize as HIP kernels (resize.FrameResizer, csrc/resize.hip), bit-identical to the host
+    statement; `build_vdata(..., resize=device_resize())` sends the kept frames of a video through it in one call.
+Everything else here is host-side integer / float arithmetic; the host statement of the resize stays the definition the device
+kernels are tested against.
 """
 from __future__ import annotations
 
@@ -94,7 +97,23 @@ def inverse_transform(images):
     return (images + 1.) / 2.
 
 
-def build_vdata(videos, idims, nvideos, nlen, nskip, rescale=True, inception=False, log=None, max_fail=10, shuffle=True, return_count=False):
+def device_resize(device=0):
+    """A `resize=` callable for build_vdata that runs on the device: (frames [k, H, W, 3] uint8, h, w) -> [k, h, w, 3] uint8, equal to
+    imresize_bilinear_u8 frame by frame.  Keeps one FrameResizer per input geometry (demo videos of one experiment share one)."""
+    from .resize import FrameResizer
+    plans = {}
+
+    def resize(frames, h, w):
+        frames = np.asarray(frames)
+        key = (frames.shape[1], frames.shape[2], int(h), int(w))
+        if key not in plans:
+            plans[key] = FrameResizer(key[:2], key[2:], max_frames=64, device=device)
+        return plans[key].resize(frames)
+    return resize
+
+
+def build_vdata(videos, idims, nvideos, nlen, nskip, rescale=True, inception=False, log=None, max_fail=10, shuffle=True, return_count=False,
+                resize=None):
     """train_script.py:59-96 from `videos`, an iterable of decoded demo videos: arrays [nframes, H, W, 3] uint8 or zero-argument
     callables returning one (so that decoding errors are counted like the reference's `except:`).  Only videos of exactly 51 frames
     are used (:72); frames 1, 1 + nskip, ... < 51 are transformed (:74-75); a video whose first kept frames contain an all -1 frame
@@ -102,6 +121,9 @@ def build_vdata(videos, idims, nvideos, nlen, nskip, rescale=True, inception=Fal
     LOOKED AT (the reference counts every readable 51-frame video, kept or not, :87, :94) or after more than `max_fail` read errors.
     shuffle (default, as the reference): `np.random.shuffle(videos)` on the list first (:66) -- it decides which videos land in the
     train / validation split and moves the global np.random stream the trainer draws its batches from afterwards, exactly as there.
+    resize: a callable (frames [k, H, W, 3] uint8, h, w) -> [k, h, w, 3] uint8 (device_resize()) that resizes the kept frames
+    vid[1:51:nskip] of one video in ONE call instead of imresize_bilinear_u8 frame by frame; everything else -- the black-frame drop,
+    the `rescale` arithmetic in float64, counting, logging, the shuffle -- is the same code on the same values.
     Returns vdata [nlen, n_kept, h, w, 3] (float64 in [-1, 1] when rescale, else uint8); with return_count also `itr`, the number of
     videos looked at -- the reference names its saved tensor after it (`vdata_strike` + str(itr), :95)."""
     log = log or (lambda s: None)
@@ -118,8 +140,13 @@ def build_vdata(videos, idims, nvideos, nlen, nskip, rescale=True, inception=Fal
                 log("%s %s" % (itr, len(idata[0])))
             if len(vid) == 51:
                 frames = []
-                for j in range(1, 51, nskip):
-                    frame = transform(vid[j], idims[0], idims[1], rescale)
+                if resize is not None:
+                    small = resize(np.stack([np.asarray(vid[j]) for j in range(1, 51, nskip)]), idims[0], idims[1])
+                for i, j in enumerate(range(1, 51, nskip)):
+                    if resize is None:
+                        frame = transform(vid[j], idims[0], idims[1], rescale)
+                    else:
+                        frame = np.array(small[i]) / 127.5 - 1. if rescale else small[i]     # transform()'s arithmetic on the resized frame
                     if not inception and np.max(frame) == -1:
                         log("rip %s" % itr)
                         frames = []

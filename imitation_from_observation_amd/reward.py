@@ -36,11 +36,16 @@ class _ResidentCacheView:
 
 
 class TranslatorReward:
-    def __init__(self, translator, nvp, scale, name="strike", ablation_type="None", batch_size=25, resident=False):
+    def __init__(self, translator, nvp, scale, name="strike", ablation_type="None", batch_size=25, resident=False, render_size=None):
         """resident=True: demo cache and cost stay on the device for EVERY translator type (mode 'oursinception' included) -- the cache
         is built there (reward_cache_begin / _add / _finish: neither the translated videos nor the finished cache cross PCIe), the
         per-path cost is computed next to the encoder (reward_costs_u8: only [paths, bs] floats come back), and `means` / `imgs` are
-        views that fetch a viewpoint's cache on demand.  resident=False (default): today's paths, bit for bit."""
+        views that fetch a viewpoint's cache on demand.  resident=False (default): today's paths, bit for bit.
+        render_size=(Hr, Wr): env_infos['imgs'] holds the frames as RENDERED, uint8 [Hr, Wr, 3], and the hook resizes them to the
+        translator's size itself (scipy.misc.imresize of the environments, on the device: resize.FrameResizer on the translator's
+        stream).  Per launch group the raw frames go up once, are resized into f32 where the encoder reads them and go through the
+        device cost entry; only the [paths, bs] costs come back.  The costs equal, bit for bit, those of a hook without render_size
+        fed the same frames resized on the host.  None (default): frames arrive at the translator's size, as before."""
         if ablation_type not in ("None", "nofeat", "noimage"):
             # 'recon' reads an undefined `image_recon` in the reference (base.py:250-252; SURVEY.md 3.4-f)
             raise NotImplementedError(f"ablation_type {ablation_type!r} is not runnable in the reference either")
@@ -52,6 +57,8 @@ class TranslatorReward:
         self.validdata = None                                    # set_demos(): the cache is then built lazily on the first path
         # mode 'oursinception' caps the demo videos at 50 (base.py:203-204); every other mode uses them all
         self.nvideos_cap = 50 if hasattr(translator, "front") else None
+        self.render_size = None if render_size is None else (int(render_size[0]), int(render_size[1]))
+        self._rs = None                                          # the FrameResizer, made at the first use
 
     # means[vp] [bs, featsize] / imgs[vp] [bs, H, W, C]: host lists (resident=False), device-backed views (resident=True); None = no cache yet
     @property
@@ -76,7 +83,7 @@ class TranslatorReward:
 
     @classmethod
     def for_sampler(cls, name, imsize, nvp, scale, modelname=None, ablation_type="None", batch_size=25,
-                    paths_per_launch=10, device=0, mode="ours", inception_ckpt=None, resident=False):
+                    paths_per_launch=10, device=0, mode="ours", inception_ckpt=None, resident=False, render_size=None):
         """What BaseSampler.initialize() sets up for mode 'ours' (base.py:113-145): the model class follows the
         experiment name -- ContextAEReal for 'real'/'sweep', ContextSkipNew otherwise (:134-137) -- on the
         sampler's imsize, restored from `modelname` when given (:138).  mode 'oursinception' (:121-132): frames go
@@ -90,19 +97,41 @@ class TranslatorReward:
                 it.front.load(inception_ckpt)
             if modelname is not None:
                 it.tr.load(modelname)
-            return cls(it, nvp, scale, name=name, ablation_type=ablation_type, batch_size=batch_size, resident=resident)
+            return cls(it, nvp, scale, name=name, ablation_type=ablation_type, batch_size=batch_size, resident=resident,
+                       render_size=render_size)
         real = name in ("real", "sweep")
         tr = Translator(imsize[0], imsize[1], featsize=100 if real else 1024, max_batch=batch_size * paths_per_launch,
                         device=device, variant="real" if real else "skipnew")
         if modelname is not None:
             tr.load(modelname)
-        return cls(tr, nvp, scale, name=name, ablation_type=ablation_type, batch_size=batch_size, resident=resident)
+        return cls(tr, nvp, scale, name=name, ablation_type=ablation_type, batch_size=batch_size, resident=resident, render_size=render_size)
 
     # ------------------------------------------------------------------ base.py:195-223
     @staticmethod
     def _frames_of(path):
         """env_infos['imgs'] holds, every other step, a list over viewpoints of uint8 frames (base.py:193)."""
         return [img for img in path["env_infos"]["imgs"] if img is not None]
+
+    def _resizer(self):
+        """render_size -> the translator's frame size, on the stream the translator's device entries run on (the front end's in mode
+        'oursinception'); a translator without a device stream (a host stand-in) gets a private one and the host-array form."""
+        if self._rs is None:
+            from .resize import FrameResizer
+            front = getattr(self.tr, "front", None)
+            stream = front.stream if front is not None else getattr(self.tr, "stream_ptr", None)
+            self._rs = FrameResizer(self.render_size, (self.tr.H, self.tr.W), max_frames=max(self.tr.max_batch, self.batch_size),
+                                    device=getattr(self.tr, "device", getattr(front, "device", 0)), stream=stream or None)
+        return self._rs
+
+    def _context_frames(self, first_frames):
+        """The context frame of every viewpoint (base.py:200) at the translator's size: rendered-size ones are resized to host uint8."""
+        if self.render_size is None:
+            return first_frames
+        out = []
+        for f in first_frames:
+            f = np.ascontiguousarray(f, dtype=np.uint8)
+            out.append(self._resizer().resize(f) if f.shape[:2] == self.render_size else f)
+        return out
 
     def set_demos(self, validdata):
         """np.load(self.algo._kwargs['modeldata']) (base.py:198), kept for the lazy cache build of process_paths."""
@@ -119,6 +148,7 @@ class TranslatorReward:
         the partial feature / frame sums are combined with ONE all-reduce per viewpoint -- the demo means are a plain sum
         over videos.  The group is the translator's own RCCL group when it has one (Translator.dp_init:
         ctx_dp_allreduce_host_f64, no torch in the sampler process), else an initialised torch.distributed group."""
+        first_frames = self._context_frames(first_frames)
         if self.resident:
             return self._build_demo_cache_resident(validdata, first_frames, distributed)
         validdata = np.asarray(validdata)
@@ -264,7 +294,22 @@ class TranslatorReward:
             for p0 in range(0, len(paths), per_call):
                 grp = range(p0, min(len(paths), p0 + per_call))
                 u8 = np.concatenate([np.stack([fr[vp] for fr in frames[p]]).astype(np.uint8) for p in grp])
-                if self.resident:
+                on_dev = False
+                if self.render_size is not None:
+                    rs = self._resizer()
+                    if hasattr(self.tr, "front") and self.resident:
+                        # raw frames up once -> f32 at the front end's size -> Mixed_7c -> encoder + cost; all on the front end's stream
+                        maps = self.tr.front.features_dev(rs.resize_dev(u8), u8.shape[0])
+                        dev, on_dev = self.tr.tr.reward_costs_dev(vp, maps, len(grp), self.scale, self.ablation_type), True
+                    elif not hasattr(self.tr, "front") and hasattr(self.tr, "reward_costs_dev"):
+                        # ... resized straight into the encoder's own frame slot (no device-to-device copy), then encoder + cost
+                        slot = self.tr.dev_frames(u8.shape[0])[0]
+                        dev, on_dev = self.tr.reward_costs_dev(vp, rs.resize_dev(u8, dst=slot), len(grp), self.scale, self.ablation_type), True
+                    else:
+                        u8 = rs.resize(u8)                                 # no device cost entry: host uint8, then the path below
+                if on_dev:
+                    pass
+                elif self.resident:
                     # every translator type: encoder (behind the front end in mode 'oursinception') + cost on the device
                     dev = self.tr.reward_costs_u8(vp, u8, self.scale, self.ablation_type)
                 elif hasattr(self.tr, "reward_costs"):
@@ -274,7 +319,7 @@ class TranslatorReward:
                     feats, x = self.tr.encode(u8)                          # [input_z, image_trans[0]], base.py:234-235
                 for k, p in enumerate(grp):
                     sl = slice(k * bs, (k + 1) * bs)
-                    c = dev[k] if self.resident or hasattr(self.tr, "reward_costs") else self._costs_from(feats[sl], x[sl], vp)
+                    c = dev[k] if on_dev or self.resident or hasattr(self.tr, "reward_costs") else self._costs_from(feats[sl], x[sl], vp)
                     # 'None' accumulates over viewpoints (costs += ...); the ablations overwrite (costs = ...)
                     costs[p] = costs[p] + c if self.ablation_type == "None" else c
         return costs

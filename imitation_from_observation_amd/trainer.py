@@ -101,13 +101,15 @@ class ModelTrainer:
 
     def __init__(self, idims, nvideos, ntrain, batch_size, model, nitr, save_every, nlen, nskip, rescale=True, inception=False,
                  strides=None, kernels=None, filters=None, *, vdata=None, basedir="model/", device=0, seed=0, translator=None,
-                 precision=None, log=print, rank=0, world=1, dp_unique_id=None, videos=None):
+                 precision=None, log=print, rank=0, world=1, dp_unique_id=None, videos=None, device_resize=False):
         """The reference's 14 positional arguments (train_script.py:29-30; the launchers omit the last five, SURVEY.md 3.4-b,
         hence the defaults), then: vdata (array or .npy path of the demo tensor), basedir (logger._snapshot_dir), device,
         seed of the parameter initialiser, an optional ready-made translator (tests), the arithmetic, the log sink.
         rank / world: one trainer per GPU process (module docstring); `batch_size` stays the GLOBAL batch (a multiple of world).
         dp_unique_id: the 128-byte blob of Translator.dp_unique_id() made on rank 0 and shipped to every rank by the launcher (omitted:
-        broadcast through an initialised torch.distributed group; not needed when `translator` already went through dp_init)."""
+        broadcast through an initialised torch.distributed group; not needed when `translator` already went through dp_init).
+        device_resize: with `videos=`, the demo frames are resized on the device (demo_pipeline.device_resize: the same bytes as the
+        host resize, one call per video) instead of on the host."""
         if model not in self.MODELS:
             raise ValueError(f"model must be one of {sorted(self.MODELS)}")
         self.idims, self.nvideos, self.ntrain, self.batch_size = tuple(idims), nvideos, ntrain, batch_size
@@ -115,6 +117,7 @@ class ModelTrainer:
         self.rescale, self.inception = rescale, inception
         self.strides, self.kernels, self.filters = strides, kernels, filters
         self.vdata, self.basedir, self.device, self.seed = vdata, basedir, device, seed
+        self.device_resize = bool(device_resize)
         self.videos = videos       # decoded demo videos (arrays [51, H, W, 3] uint8 or callables returning them): train_script.py:59-96
         self.translator, self.precision, self.log = translator, precision, log
         self.rank, self.world, self.dp_unique_id = int(rank), int(world), dp_unique_id
@@ -182,9 +185,10 @@ class ModelTrainer:
             flat = allsum(flat)
             np.random.set_state((st[0], flat[:624].astype(np.uint32), int(flat[624]), int(flat[625]), float(flat[626])))
         if self.vdata is None and self.videos is not None:
-            from .demo_pipeline import build_vdata
+            from .demo_pipeline import build_vdata, device_resize
             vdata, looked_at = build_vdata(self.videos, self.idims, self.nvideos, self.nlen, self.nskip, self.rescale, self.inception,
-                                           log=self.log if self.rank == 0 else None, return_count=True)
+                                           log=self.log if self.rank == 0 else None, return_count=True,
+                                           resize=device_resize(self.device) if self.device_resize else None)
             if self.rank == 0:
                 np.save(basedir + "vdata_strike" + str(looked_at), vdata)                      # train_script.py:95 (named after `itr`, the videos looked at)
         else:

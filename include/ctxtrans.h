@@ -48,7 +48,7 @@ extern "C" {
                                still 4 (additions only): ctx_vjp_args, ctx_dev_forward_vjp, ctx_dev_backward_vjp, ctx_params_written;
                                CTX_CNN_AVGPOOL_VALID / CTX_CNN_CONV_LINEAR, ctx_cnn_stats_*, ctx_cnn_reward_*; ctx_nn_err,
                                ctx_dp_nn_err, ctx_cnn_demos_upload, ctx_cnn_forward_sampled_dev; ctx_reward_costs_dev, ctx_reward_cache_*,
-                               ctx_reward_get_cache, ctx_reward_stats, option reward_split */
+                               ctx_reward_get_cache, ctx_reward_stats, option reward_split; ctx_resize_* */
 
 enum {
     CTX_OK = 0,
@@ -605,6 +605,40 @@ int ctx_disc_train_epoch(ctx_disc* h, const int32_t* order, int64_t n, int batch
                          float* accs);
 int ctx_disc_reward_paths(ctx_disc* h, const uint8_t* frames, int P, int T, int shift, float* probs);
 int ctx_disc_debug_read(ctx_disc* h, const char* name, float* host, size_t n);
+
+/* ---- device-side frame resize: scipy.misc.imresize(img, idims) for uint8 RGB frames ------------------------------
+ * Every frame the reference uses goes through it first (the environments of gym/envs/mujoco on every rendered frame, scripts/train_script.py:16-19
+ * on every demo frame).  For uint8 RGB input it is Pillow's Image.resize(..., BILINEAR): a separable antialiased triangle filter,
+ * horizontal pass then vertical pass, each in 22-bit fixed point, rounded half-up and clipped to uint8 BETWEEN the passes
+ * (libImaging/Resample.c); a pass whose input and output extents are equal is skipped.  Integer arithmetic, so the device result
+ * equals Pillow's bit for bit.  ABI 4, additions only.  A plan is one geometry: 1 <= Hin, Win <= 4096, 1 <= Hout, Wout <= 1024,
+ * C == 3, 1 <= max_frames <= 65535, up- or downscaling on each axis independently; anything else is CTX_E_INVALID.
+ *   ctx_resize_coeffs    works without a device: the tables of one axis as Resample.c's precompute_coeffs / normalize_coeffs_8bpc
+ *                        make them (double, weights summed in order, divided, (int)(+-0.5 + w 2^22)).  xmin / count [out_size],
+ *                        kk [out_size][*ksize] row-major, zero beyond count[xx]; *ksize = 2 ceil(max(in/out, 1)) + 1; kk may be NULL
+ *                        to query *ksize.  CTX_E_INVALID for sizes < 1.
+ *   ctx_resize_create    arguments are validated BEFORE the device is touched (CTX_E_INVALID); no usable device: CTX_E_DEVICE,
+ *                        *out = NULL.  stream: a hipStream_t (ctx_stream / ctx_cnn_stream of the consumer) or NULL = private stream.
+ *                        A borrowed stream is never destroyed or, in ctx_resize_destroy, waited on: the plan may outlive its owner,
+ *                        but must not be CALLED after the owner is gone.
+ *   ctx_resize_u8        host uint8 [n,Hin,Win,C] -> host uint8 [n,Hout,Wout,C]; any n >= 1 (chunks of max_frames); synchronous.
+ *   ctx_resize_f32_dev   host uint8 in, DEVICE f32 out in the sampler's (x/255 - 0.5)*2 form (the three separately rounded f32
+ *                        operations of ctx_encode's image_trans, bit for bit), n <= max_frames.  d_dst NULL: the plan's own buffer
+ *                        (valid until the next call); else a device buffer of n*Hout*Wout*C floats, e.g. a slot of ctx_dev_frames.
+ *                        *d_out = where it was written -- what ctx_reward_costs_dev, ctx_reward_cache_add_dev, ctx_encode_dev,
+ *                        ctx_translate_dev and ctx_cnn_forward_dev take.  Asynchronous on the plan's stream: `frames` must stay
+ *                        untouched until the stream has passed the upload.
+ *   ctx_resize_profile   measurement only: one upload of n frames (pinned != 0: from a page-locked copy of them) and one run of the
+ *                        kernels into the plan's f32 buffer, each between HIP events on the plan's stream (ms). */
+typedef struct ctx_resize ctx_resize;
+int ctx_resize_coeffs(int in_size, int out_size, int32_t* xmin, int32_t* count, int32_t* kk, int* ksize);
+int ctx_resize_create(int Hin, int Win, int C, int Hout, int Wout, int max_frames, int device, void* stream, ctx_resize** out);
+void ctx_resize_destroy(ctx_resize* r);
+const char* ctx_resize_last_error(const ctx_resize* r);       /* r == NULL: last creation error of this thread */
+int ctx_resize_u8(ctx_resize* r, const uint8_t* frames, int n, uint8_t* out);
+int ctx_resize_f32_dev(ctx_resize* r, const uint8_t* frames, int n, float* d_dst, const float** d_out);
+int ctx_resize_sync(ctx_resize* r);
+int ctx_resize_profile(ctx_resize* r, const uint8_t* frames, int n, int pinned, float* h2d_ms, float* kernel_ms);
 
 #ifdef __cplusplus
 }
