@@ -158,6 +158,7 @@ SIGNATURES = {
     "ctx_cnn_forward_u8": (_c.c_int, [_P, _U8, _c.c_int, _F]),
     "ctx_cnn_forward_u8_dev": (_c.c_int, [_P, _U8, _c.c_int, _c.POINTER(_P)]),
     "ctx_cnn_forward_dev": (_c.c_int, [_P, _P, _c.c_int, _c.POINTER(_P)]),
+    "ctx_cnn_forward_dev_u8": (_c.c_int, [_P, _P, _c.c_int, _c.POINTER(_P)]),
     "ctx_cnn_demos_upload": (_c.c_int, [_P, _U8, _c.c_int, _c.c_int]),
     "ctx_cnn_forward_sampled_dev": (_c.c_int, [_P, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32), _c.c_int, _c.c_int, _c.c_int,
                                                _c.POINTER(_P)]),
@@ -171,6 +172,8 @@ SIGNATURES = {
     "ctx_cnn_stats_read": (_c.c_int, [_P, _c.c_int, _F, _F, _c.POINTER(_c.c_int)]),
     "ctx_cnn_reward_set_stats": (_c.c_int, [_P, _c.c_int, _F, _F, _c.c_int]),
     "ctx_cnn_reward_costs": (_c.c_int, [_P, _U8, _c.c_int, _F]),
+    "ctx_cnn_stats_add_dev_u8": (_c.c_int, [_P, _P, _c.c_int, _c.c_int]),
+    "ctx_cnn_reward_costs_dev_u8": (_c.c_int, [_P, _P, _c.c_int, _F]),
     "ctx_disc_param_total_for": (_c.c_int64, [_DCFG]),
     "ctx_disc_create": (_c.c_int, [_DCFG, _c.c_int, _c.POINTER(_P)]),
     "ctx_disc_destroy": (None, [_P]),
@@ -194,6 +197,9 @@ SIGNATURES = {
     "ctx_disc_data_upload": (_c.c_int, [_P, _U8, _c.c_int, _c.c_int, _F, _F]),
     "ctx_disc_train_epoch": (_c.c_int, [_P, _c.POINTER(_c.c_int32), _c.c_int64, _c.c_int, _c.c_int, _c.c_float, _c.c_int, _F, _F]),
     "ctx_disc_reward_paths": (_c.c_int, [_P, _U8, _c.c_int, _c.c_int, _c.c_int, _F]),
+    "ctx_disc_stream": (_P, [_P]),
+    "ctx_disc_data_begin": (_c.c_int, [_P, _c.c_int, _c.c_int, _F, _F, _c.POINTER(_P)]),
+    "ctx_disc_reward_paths_dev": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int, _F]),
     "ctx_disc_debug_read": (_c.c_int, [_P, _c.c_char_p, _F, _c.c_size_t]),
     "ctx_resize_coeffs": (_c.c_int, [_c.c_int, _c.c_int, _I32, _I32, _I32, _c.POINTER(_c.c_int)]),
     "ctx_resize_create": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _c.POINTER(_P)]),
@@ -201,6 +207,9 @@ SIGNATURES = {
     "ctx_resize_last_error": (_c.c_char_p, [_P]),
     "ctx_resize_u8": (_c.c_int, [_P, _U8, _c.c_int, _U8]),
     "ctx_resize_f32_dev": (_c.c_int, [_P, _U8, _c.c_int, _P, _c.POINTER(_P)]),
+    "ctx_resize_u8_dev": (_c.c_int, [_P, _U8, _c.c_int, _P, _c.POINTER(_P)]),
+    "ctx_resize_u8_dev_v": (_c.c_int, [_P, _c.POINTER(_P), _c.c_int, _P, _c.POINTER(_P)]),
+    "ctx_resize_f32_dev_v": (_c.c_int, [_P, _c.POINTER(_P), _c.c_int, _P, _c.POINTER(_P)]),
     "ctx_resize_sync": (_c.c_int, [_P]),
     "ctx_resize_profile": (_c.c_int, [_P, _U8, _c.c_int, _c.c_int, _F, _F]),
 }

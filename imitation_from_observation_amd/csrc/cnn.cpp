@@ -268,13 +268,59 @@ void free_reward(ctx_cnn* h) {
     h->r_frames = h->r_c = 0;
 }
 
-// Uploads m frames and runs one pass (the staging buffer is reused by the next chunk: callers sync before it)
-int forward_chunk(ctx_cnn* h, const uint8_t* frames, int m) {
+// Uploads m frames and runs one pass (the staging buffer is reused by the next chunk: callers sync before it).  on_dev: `frames` is
+// DEVICE memory at any byte address and pad_channels_u8 (byte loads) reads it in place of the staging buffer -- the same kernel on
+// the same bytes, so the same bits
+int forward_chunk(ctx_cnn* h, const uint8_t* frames, int m, bool on_dev = false) {
     const ctx_cnn_buf& b0 = h->bufs.front();
     const int64_t pix_in = (int64_t)b0.h * b0.w;
-    CNN_HIP(h, hipMemcpyAsync(h->u8, frames, (size_t)m * pix_in * 3, hipMemcpyHostToDevice, h->stream));
-    pad_channels_u8(h->stream, h->u8, h->dbuf[0], m * pix_in, h->stem4 ? 4 : b0.c);
+    if (!on_dev) CNN_HIP(h, hipMemcpyAsync(h->u8, frames, (size_t)m * pix_in * 3, hipMemcpyHostToDevice, h->stream));
+    pad_channels_u8(h->stream, on_dev ? frames : h->u8, h->dbuf[0], m * pix_in, h->stem4 ? 4 : b0.c);
     return run_cached(h, m);
+}
+
+int stats_add_any(ctx_cnn* h, const uint8_t* frames, int nvideos, int pass, bool on_dev) {
+    if (!h) return CTX_E_INVALID;
+    const char* who = on_dev ? "stats_add_dev_u8" : "stats_add_u8";
+    if (!frames || nvideos <= 0 || (pass != 0 && pass != 1)) return cfail(h, CTX_E_INVALID, "%s: bad arguments", who);
+    if (h->stats_stage != pass) return cfail(h, CTX_E_STATE, "%s: pass %d is not open (reset, then pass 0, finish(0), pass 1, finish(1))", who, pass);
+    CNN_HIP(h, hipSetDevice(h->device));
+    const int F = h->stats_frames, per = h->max_images / F;
+    const int64_t fbytes = (int64_t)F * h->bufs.front().h * h->bufs.front().w * 3;
+    for (int v0 = 0; v0 < nvideos; v0 += per) {
+        const int nv = nvideos - v0 < per ? nvideos - v0 : per;
+        int rc = forward_chunk(h, frames + v0 * fbytes, nv * F, on_dev);
+        if (rc != CTX_OK) return rc;
+        for (ctx_cnn::StatSlot& sl : h->stats) {
+            const ctx_cnn_buf& b = h->bufs[sl.buf];
+            incep_stats_accum(h->stream, h->dbuf[sl.buf], F, (int64_t)b.h * b.w, sl.c, b.c, nv, pass, sl.mean, sl.acc);
+        }
+        if (hipGetLastError() != hipSuccess) return cfail(h, CTX_E_DEVICE, "stats kernel launch failed");
+        CNN_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    h->stats_count[pass] += nvideos;
+    return CTX_OK;
+}
+
+int reward_costs_any(ctx_cnn* h, const uint8_t* frames, int npaths, float* costs, bool on_dev) {
+    if (!h) return CTX_E_INVALID;
+    const char* who = on_dev ? "reward_costs_dev_u8" : "reward_costs";
+    if (!frames || !costs || npaths <= 0) return cfail(h, CTX_E_INVALID, "%s: bad arguments", who);
+    if (!h->r_mean) return cfail(h, CTX_E_STATE, "%s: no statistics (ctx_cnn_reward_set_stats first)", who);
+    CNN_HIP(h, hipSetDevice(h->device));
+    const ctx_cnn_buf& b = h->bufs.back();
+    const int F = h->r_frames, per = h->max_images / F;
+    const int64_t fbytes = (int64_t)F * h->bufs.front().h * h->bufs.front().w * 3;
+    for (int p0 = 0; p0 < npaths; p0 += per) {
+        const int np = npaths - p0 < per ? npaths - p0 : per;
+        int rc = forward_chunk(h, frames + p0 * fbytes, np * F, on_dev);
+        if (rc != CTX_OK) return rc;
+        incep_costs(h->stream, h->dbuf.back(), np * F, F, (int64_t)b.h * b.w, h->r_c, b.c, h->r_mean, h->r_std, h->r_cost);
+        if (hipGetLastError() != hipSuccess) return cfail(h, CTX_E_DEVICE, "cost kernel launch failed");
+        CNN_HIP(h, hipMemcpyAsync(costs + (int64_t)p0 * F, h->r_cost, (size_t)np * F * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        CNN_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    return CTX_OK;
 }
 }  // namespace
 
@@ -477,6 +523,17 @@ int ctx_cnn_forward_dev(ctx_cnn* h, const float* d_frames, int n, const float** 
     return CTX_OK;
 }
 
+// d_frames: DEVICE uint8 [n, H, W, 3] at any byte address (written on the handle's stream or before a synchronisation), n <= max_images;
+// otherwise ctx_cnn_forward_u8_dev without the upload.  Asynchronous on the handle's stream.
+int ctx_cnn_forward_dev_u8(ctx_cnn* h, const uint8_t* d_frames, int n, const float** d_out) {
+    if (!h || !d_frames || n <= 0 || n > h->max_images) return h ? cfail(h, CTX_E_INVALID, "n must be in [1, max_images]") : CTX_E_INVALID;
+    CNN_HIP(h, hipSetDevice(h->device));
+    const int rc = forward_chunk(h, d_frames, n, true);
+    if (rc != CTX_OK) return rc;
+    if (d_out) *d_out = h->dbuf.back();
+    return CTX_OK;
+}
+
 // copies buffer `index` (n images) to the host: bring-up and the end-point tests
 int ctx_cnn_read_buffer(ctx_cnn* h, int index, int n, float* out) {
     if (!h || !out || index < 0 || index >= (int)h->bufs.size() || n <= 0 || n > h->max_images) return CTX_E_INVALID;
@@ -546,26 +603,9 @@ int ctx_cnn_stats_reset(ctx_cnn* h, const int32_t* buffers, const int32_t* chann
     return CTX_OK;
 }
 
-int ctx_cnn_stats_add_u8(ctx_cnn* h, const uint8_t* frames, int nvideos, int pass) {
-    if (!h) return CTX_E_INVALID;
-    if (!frames || nvideos <= 0 || (pass != 0 && pass != 1)) return cfail(h, CTX_E_INVALID, "stats_add_u8: bad arguments");
-    if (h->stats_stage != pass) return cfail(h, CTX_E_STATE, "stats_add_u8: pass %d is not open (reset, then pass 0, finish(0), pass 1, finish(1))", pass);
-    CNN_HIP(h, hipSetDevice(h->device));
-    const int F = h->stats_frames, per = h->max_images / F;
-    const int64_t fbytes = (int64_t)F * h->bufs.front().h * h->bufs.front().w * 3;
-    for (int v0 = 0; v0 < nvideos; v0 += per) {
-        const int nv = nvideos - v0 < per ? nvideos - v0 : per;
-        int rc = forward_chunk(h, frames + v0 * fbytes, nv * F);
-        if (rc != CTX_OK) return rc;
-        for (ctx_cnn::StatSlot& sl : h->stats) {
-            const ctx_cnn_buf& b = h->bufs[sl.buf];
-            incep_stats_accum(h->stream, h->dbuf[sl.buf], F, (int64_t)b.h * b.w, sl.c, b.c, nv, pass, sl.mean, sl.acc);
-        }
-        if (hipGetLastError() != hipSuccess) return cfail(h, CTX_E_DEVICE, "stats kernel launch failed");
-        CNN_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    h->stats_count[pass] += nvideos;
-    return CTX_OK;
+int ctx_cnn_stats_add_u8(ctx_cnn* h, const uint8_t* frames, int nvideos, int pass) { return stats_add_any(h, frames, nvideos, pass, false); }
+int ctx_cnn_stats_add_dev_u8(ctx_cnn* h, const uint8_t* d_frames, int nvideos, int pass) {
+    return stats_add_any(h, d_frames, nvideos, pass, true);
 }
 
 int ctx_cnn_stats_finish(ctx_cnn* h, int pass) {
@@ -619,24 +659,9 @@ int ctx_cnn_reward_set_stats(ctx_cnn* h, int channels, const float* means, const
     return CTX_OK;
 }
 
-int ctx_cnn_reward_costs(ctx_cnn* h, const uint8_t* frames, int npaths, float* costs) {
-    if (!h) return CTX_E_INVALID;
-    if (!frames || !costs || npaths <= 0) return cfail(h, CTX_E_INVALID, "reward_costs: bad arguments");
-    if (!h->r_mean) return cfail(h, CTX_E_STATE, "reward_costs: no statistics (ctx_cnn_reward_set_stats first)");
-    CNN_HIP(h, hipSetDevice(h->device));
-    const ctx_cnn_buf& b = h->bufs.back();
-    const int F = h->r_frames, per = h->max_images / F;
-    const int64_t fbytes = (int64_t)F * h->bufs.front().h * h->bufs.front().w * 3;
-    for (int p0 = 0; p0 < npaths; p0 += per) {
-        const int np = npaths - p0 < per ? npaths - p0 : per;
-        int rc = forward_chunk(h, frames + p0 * fbytes, np * F);
-        if (rc != CTX_OK) return rc;
-        incep_costs(h->stream, h->dbuf.back(), np * F, F, (int64_t)b.h * b.w, h->r_c, b.c, h->r_mean, h->r_std, h->r_cost);
-        if (hipGetLastError() != hipSuccess) return cfail(h, CTX_E_DEVICE, "cost kernel launch failed");
-        CNN_HIP(h, hipMemcpyAsync(costs + (int64_t)p0 * F, h->r_cost, (size_t)np * F * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        CNN_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    return CTX_OK;
+int ctx_cnn_reward_costs(ctx_cnn* h, const uint8_t* frames, int npaths, float* costs) { return reward_costs_any(h, frames, npaths, costs, false); }
+int ctx_cnn_reward_costs_dev_u8(ctx_cnn* h, const uint8_t* d_frames, int npaths, float* costs) {
+    return reward_costs_any(h, d_frames, npaths, costs, true);
 }
 
 void* ctx_cnn_stream(ctx_cnn* h) { return h ? (void*)h->stream : nullptr; }

@@ -47,6 +47,7 @@ struct ctx_disc {
     uint8_t* xu8 = nullptr;
     float* xf = nullptr;                                // 2 * max_batch images only (the float forms are per-batch calls)
     bool in_u8 = false;
+    const uint8_t* x_ext = nullptr;                     // ctx_disc_reward_paths_dev: the forward reads the caller's device frames in place of xu8
     float *time = nullptr, *cls = nullptr, *dom = nullptr;
     // activations
     float *pool1 = nullptr, *pool2 = nullptr, *f = nullptr, *hc1 = nullptr, *hc2 = nullptr, *hd1 = nullptr, *hd2 = nullptr;
@@ -155,7 +156,7 @@ int64_t fpix(const ctx_disc* h) { return (int64_t)h->H * h->W * 3; }
 // through the conv stack once.  GAIL: nimg = M, the time column comes from h->time.
 void forward(ctx_disc* h, int nimg, int M, int T, int shift, bool with_dom) {
     hipStream_t s = h->stream;
-    const void* x = h->in_u8 ? (const void*)h->xu8 : (const void*)h->xf;
+    const void* x = h->in_u8 ? (const void*)(h->x_ext ? h->x_ext : h->xu8) : (const void*)h->xf;
     disc_conv_pool(s, x, h->in_u8, 3, W_(h, "wc1"), W_(h, "bc1"), h->pool1, h->sel1, nimg, h->H, h->W);
     if (tpil(h)) {
         disc_conv_pool(s, h->pool1, false, DISC_F, W_(h, "wc2"), W_(h, "bc2"), h->pool2, h->sel2, nimg, h->H2, h->W2);
@@ -467,6 +468,8 @@ int ctx_disc_init_params(ctx_disc* h, uint64_t seed) {
     return finish(h);
 }
 
+void* ctx_disc_stream(ctx_disc* h) { return h ? (void*)h->stream : nullptr; }
+
 int ctx_disc_sync(ctx_disc* h) {
     if (!h) return CTX_E_INVALID;
     DISC_HIP(h, hipSetDevice(h->device));
@@ -493,9 +496,10 @@ int ctx_disc_accuracy_u8(ctx_disc* h, const uint8_t* x1, const void* x2_or_time,
     return accuracy_any(h, x1, x2_or_time, true, cls, B, acc);
 }
 
-int ctx_disc_data_upload(ctx_disc* h, const uint8_t* frames, int N, int T, const float* cls, const float* dom) {
+int ctx_disc_data_begin(ctx_disc* h, int N, int T, const float* cls, const float* dom, uint8_t** d_frames) {
     if (!h) return CTX_E_INVALID;
-    if (!frames || !cls || N <= 0 || T <= 0 || (int64_t)N * T >= (1ll << 31)) return dfail(h, CTX_E_INVALID, "bad data set");
+    if (!cls || !d_frames || N <= 0 || T <= 0 || (int64_t)N * T >= (1ll << 31)) return dfail(h, CTX_E_INVALID, "bad data set");
+    *d_frames = nullptr;
     DISC_HIP(h, hipSetDevice(h->device));
     DISC_HIP(h, hipStreamSynchronize(h->stream));
     for (void* p : {(void*)h->frames, (void*)h->cls_all, (void*)h->dom_all}) if (p) (void)hipFree(p);
@@ -504,12 +508,23 @@ int ctx_disc_data_upload(ctx_disc* h, const uint8_t* frames, int N, int T, const
     if (hipMalloc((void**)&h->frames, bytes) != hipSuccess || hipMalloc((void**)&h->cls_all, tb) != hipSuccess ||
         hipMalloc((void**)&h->dom_all, tb) != hipSuccess)
         return dfail(h, CTX_E_NOMEM, "the data set (%zu bytes) does not fit", bytes);
-    DISC_HIP(h, hipMemcpyAsync(h->frames, frames, bytes, hipMemcpyHostToDevice, h->stream));
     DISC_HIP(h, hipMemcpyAsync(h->cls_all, cls, tb, hipMemcpyHostToDevice, h->stream));
     if (dom) DISC_HIP(h, hipMemcpyAsync(h->dom_all, dom, tb, hipMemcpyHostToDevice, h->stream));
     else DISC_HIP(h, hipMemsetAsync(h->dom_all, 0, tb, h->stream));
     h->dN = N; h->dT = T;
-    return finish(h);
+    int rc = finish(h);                                  // cls / dom may be freed by the caller from here on
+    if (rc == CTX_OK) *d_frames = h->frames;
+    return rc;
+}
+
+int ctx_disc_data_upload(ctx_disc* h, const uint8_t* frames, int N, int T, const float* cls, const float* dom) {
+    if (!h) return CTX_E_INVALID;
+    if (!frames) return dfail(h, CTX_E_INVALID, "bad data set");
+    uint8_t* d = nullptr;
+    int rc = ctx_disc_data_begin(h, N, T, cls, dom, &d);
+    if (rc != CTX_OK) return rc;
+    DISC_HIP(h, hipMemcpyAsync(d, frames, (size_t)N * T * fpix(h), hipMemcpyHostToDevice, h->stream));
+    return finish(h);                                    // second drain (data_begin made the first): `frames` may be freed from here on
 }
 
 int ctx_disc_train_epoch(ctx_disc* h, const int32_t* order, int64_t n, int batch, int shift, float lr, int with_accuracy, float* losses,
@@ -549,7 +564,7 @@ int ctx_disc_train_epoch(ctx_disc* h, const int32_t* order, int64_t n, int batch
     return finish(h);
 }
 
-int ctx_disc_reward_paths(ctx_disc* h, const uint8_t* frames, int P, int T, int shift, float* probs) {
+static int reward_paths_any(ctx_disc* h, const uint8_t* frames, int P, int T, int shift, float* probs, bool on_dev) {
     if (!h) return CTX_E_INVALID;
     if (!frames || !probs || P <= 0 || T <= 0 || shift < 0) return dfail(h, CTX_E_INVALID, "bad arguments");
     if (T > h->R) return dfail(h, CTX_E_INVALID, "paths of %d frames exceed the handle's %d rows", T, h->R);
@@ -559,9 +574,12 @@ int ctx_disc_reward_paths(ctx_disc* h, const uint8_t* frames, int P, int T, int 
     h->in_u8 = true;
     for (int p0 = 0; p0 < P; p0 += per) {
         const int np = std::min(per, P - p0), M = np * T;
-        DISC_HIP(h, hipMemcpyAsync(h->xu8, frames + (int64_t)p0 * T * fpix(h), (size_t)M * fpix(h), hipMemcpyHostToDevice, h->stream));
+        const uint8_t* src = frames + (int64_t)p0 * T * fpix(h);
+        if (!on_dev) DISC_HIP(h, hipMemcpyAsync(h->xu8, src, (size_t)M * fpix(h), hipMemcpyHostToDevice, h->stream));
         if (!tpil(h)) disc_fill_time(h->stream, h->time, M, T);
+        h->x_ext = on_dev ? src : nullptr;               // disc_conv_pool loads bytes: any address serves
         forward(h, M, M, T, shift, false);
+        h->x_ext = nullptr;
         head(h, M, false, false, nullptr, nullptr);
         DISC_HIP(h, hipMemcpyAsync(out.data(), h->probs, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         int rc = finish(h);
@@ -569,6 +587,13 @@ int ctx_disc_reward_paths(ctx_disc* h, const uint8_t* frames, int P, int T, int 
         for (int i = 0; i < M; ++i) probs[(int64_t)p0 * T + i] = out[2 * (size_t)i];      // P(expert) = softmax[:, 0]
     }
     return CTX_OK;
+}
+
+int ctx_disc_reward_paths(ctx_disc* h, const uint8_t* frames, int P, int T, int shift, float* probs) {
+    return reward_paths_any(h, frames, P, T, shift, probs, false);
+}
+int ctx_disc_reward_paths_dev(ctx_disc* h, const uint8_t* d_frames, int P, int T, int shift, float* probs) {
+    return reward_paths_any(h, d_frames, P, T, shift, probs, true);
 }
 
 int ctx_disc_debug_read(ctx_disc* h, const char* name, float* host, size_t n) {

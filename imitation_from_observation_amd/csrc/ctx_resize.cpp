@@ -1,8 +1,9 @@
 // ctx_resize.cpp -- the ctx_resize handle of include/ctxtrans.h: scipy.misc.imresize(img, idims) for uint8 RGB frames on the device
 // (every rendered frame of gym/envs/mujoco/*.py, every demo frame of scripts/train_script.py:16-19).  A plan is one geometry
 // (Hin x Win -> Hout x Wout): the coefficient tables of both axes are computed on the host in double, in Pillow's order
-// (libImaging/Resample.c: precompute_coeffs, normalize_coeffs_8bpc), and uploaded once; a call uploads the raw frames, runs the
-// horizontal and the vertical pass (resize.hip) and leaves uint8 on the host or f32 in [-1,1] on the device.
+// (libImaging/Resample.c: precompute_coeffs, normalize_coeffs_8bpc), and uploaded once; a call uploads the raw frames (one block, or
+// frame by frame from a list of pointers), runs the horizontal and the vertical pass (resize.hip) and leaves uint8 on the host, or
+// uint8 or f32 in [-1,1] on the device.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -113,6 +114,62 @@ void run(ctx_resize* r, int n, void* dst, bool f32_out) {
     if (r->vpass) resize_vpass(r->stream, src, dst, f32_out, n, r->Hin, r->Hout, r->Wout * 3, r->ax_v);
     if (!r->hpass && !r->vpass && f32_out) resize_prep(r->stream, src, (float*)dst, (int64_t)out_elems(r, n));
 }
+// n frames -> d_in: one block (frames) or one copy per frame into consecutive slots (frames_v); everything is checked by the callers
+int upload(ctx_resize* r, const uint8_t* frames, const uint8_t* const* frames_v, int n) {
+    if (frames) {
+        RS_HIP(r, hipMemcpyAsync(r->d_in, frames, in_bytes(r, n), hipMemcpyHostToDevice, r->stream));
+        return CTX_OK;
+    }
+    const size_t fb = in_bytes(r, 1);
+    for (int i = 0; i < n; ++i) RS_HIP(r, hipMemcpyAsync(r->d_in + (size_t)i * fb, frames_v[i], fb, hipMemcpyHostToDevice, r->stream));
+    return CTX_OK;
+}
+
+int check_call(ctx_resize* r, const uint8_t* frames, const uint8_t* const* frames_v, int n) {
+    if ((!frames && !frames_v) || n < 1 || n > r->max_frames)
+        return rfail(r, CTX_E_INVALID, "frames is NULL or n = %d outside [1, max_frames = %d]", n, r->max_frames);
+    if (frames_v)
+        for (int i = 0; i < n; ++i)
+            if (!frames_v[i]) return rfail(r, CTX_E_INVALID, "frames[%d] is NULL", i);
+    return CTX_OK;
+}
+
+int u8_dev_any(ctx_resize* r, const uint8_t* frames, const uint8_t* const* frames_v, int n, uint8_t* d_dst, const uint8_t** d_out) {
+    if (!r) return CTX_E_INVALID;
+    if (check_call(r, frames, frames_v, n) != CTX_OK) return CTX_E_INVALID;
+    RS_HIP(r, hipSetDevice(r->device));
+    int rc = upload(r, frames, frames_v, n);
+    if (rc != CTX_OK) return rc;
+    const uint8_t* res = d_dst;
+    if (r->hpass || r->vpass) {
+        if (!d_dst) res = r->d_u8;
+        run(r, n, (void*)res, false);
+        RS_HIP(r, hipGetLastError());
+    } else if (d_dst) {
+        RS_HIP(r, hipMemcpyAsync(d_dst, r->d_in, out_elems(r, n), hipMemcpyDeviceToDevice, r->stream));
+    } else res = r->d_in;                                  // neither pass: the copy of the input is the result
+    if (d_out) *d_out = res;
+    return CTX_OK;
+}
+
+int f32_dev_any(ctx_resize* r, const uint8_t* frames, const uint8_t* const* frames_v, int n, float* d_dst, const float** d_out) {
+    if (!r) return CTX_E_INVALID;
+    if (check_call(r, frames, frames_v, n) != CTX_OK) return CTX_E_INVALID;
+    RS_HIP(r, hipSetDevice(r->device));
+    if (!d_dst) {
+        if (!r->d_f32 && hipMalloc((void**)&r->d_f32, out_elems(r, r->max_frames) * sizeof(float)) != hipSuccess) {
+            r->d_f32 = nullptr;
+            return rfail(r, CTX_E_NOMEM, "device allocation of the f32 output failed");
+        }
+        d_dst = r->d_f32;
+    }
+    int rc = upload(r, frames, frames_v, n);
+    if (rc != CTX_OK) return rc;
+    run(r, n, d_dst, true);
+    RS_HIP(r, hipGetLastError());
+    if (d_out) *d_out = d_dst;
+    return CTX_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -214,21 +271,16 @@ int ctx_resize_u8(ctx_resize* r, const uint8_t* frames, int n, uint8_t* out) {
 }
 
 int ctx_resize_f32_dev(ctx_resize* r, const uint8_t* frames, int n, float* d_dst, const float** d_out) {
-    if (!r) return CTX_E_INVALID;
-    if (!frames || n < 1 || n > r->max_frames) return rfail(r, CTX_E_INVALID, "frames is NULL or n = %d outside [1, max_frames = %d]", n, r->max_frames);
-    RS_HIP(r, hipSetDevice(r->device));
-    if (!d_dst) {
-        if (!r->d_f32 && hipMalloc((void**)&r->d_f32, out_elems(r, r->max_frames) * sizeof(float)) != hipSuccess) {
-            r->d_f32 = nullptr;
-            return rfail(r, CTX_E_NOMEM, "device allocation of the f32 output failed");
-        }
-        d_dst = r->d_f32;
-    }
-    RS_HIP(r, hipMemcpyAsync(r->d_in, frames, in_bytes(r, n), hipMemcpyHostToDevice, r->stream));
-    run(r, n, d_dst, true);
-    RS_HIP(r, hipGetLastError());
-    if (d_out) *d_out = d_dst;
-    return CTX_OK;
+    return f32_dev_any(r, frames, nullptr, n, d_dst, d_out);
+}
+int ctx_resize_f32_dev_v(ctx_resize* r, const uint8_t* const* frames, int n, float* d_dst, const float** d_out) {
+    return f32_dev_any(r, nullptr, frames, n, d_dst, d_out);
+}
+int ctx_resize_u8_dev(ctx_resize* r, const uint8_t* frames, int n, uint8_t* d_dst, const uint8_t** d_out) {
+    return u8_dev_any(r, frames, nullptr, n, d_dst, d_out);
+}
+int ctx_resize_u8_dev_v(ctx_resize* r, const uint8_t* const* frames, int n, uint8_t* d_dst, const uint8_t** d_out) {
+    return u8_dev_any(r, nullptr, frames, n, d_dst, d_out);
 }
 
 int ctx_resize_sync(ctx_resize* r) {

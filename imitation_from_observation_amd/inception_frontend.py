@@ -264,7 +264,7 @@ class InceptionFrontend:
 
     def __init__(self, H=125, W=125, max_images=75, device=0, precision="f32", stream=None, merge_heads=None, final="Mixed_7c"):
         self._lib = _lib.load()
-        self.H, self.W = H, W
+        self.H, self.W, self.device = H, W, device
         if merge_heads is None:
             import os
             merge_heads = os.environ.get("CTX_CNN_MERGE", "1") != "0"
@@ -462,6 +462,13 @@ class InceptionFrontend:
         self._ck(self._lib.ctx_cnn_forward_dev(self._h, ctypes.c_void_p(d_frames_f32), n, ctypes.byref(d_out)))
         return d_out.value
 
+    def features_from_dev_u8(self, d_frames_u8, n):
+        """Device uint8 frames [n,H,W,3] (integer address, any byte alignment; e.g. FrameResizer.resize_u8_dev on this stream) ->
+        integer device address of the `final` end point [n,h,w,c]: features_u8_dev without the upload, same bits.  Asynchronous."""
+        d_out = ctypes.c_void_p()
+        self._ck(self._lib.ctx_cnn_forward_dev_u8(self._h, ctypes.c_void_p(d_frames_u8), int(n), ctypes.byref(d_out)))
+        return d_out.value
+
     def endpoint(self, name, n):
         """Activations of a named end point after the last forward over n images (tests)."""
         bid, h, w, c = self.endpoints[name]
@@ -498,16 +505,22 @@ class InceptionFrontend:
         return out
 
     # ------------------------------------------------------------------ Inception-feature reward (ctx_cnn_stats_* / ctx_cnn_reward_*)
-    def stats(self, videos, layers, nframes=None):
+    def stats(self, videos, layers, nframes=None, resize=None):
         """Per-timestep means and stds of end points over videos, computed on the device: {layer: (means, stds)}, each
         [nframes, h, w, c] f32, equal to numpy's float32  np.mean / np.std(axis=0)  over the videos' features bit for bit.
         videos: iterable of uint8 [nframes, H, W, 3] (lists of frames are stacked); two passes over it, one forward per video each,
-        max_images // nframes videos per device pass.  layers: end points at or before `final`."""
-        videos = [self._check_frames(np.stack(v) if isinstance(v, (list, tuple)) else v) for v in videos]
+        max_images // nframes videos per device pass.  layers: end points at or before `final`.
+        resize: a FrameResizer on this front end's stream (render size -> (H, W), max_frames >= the frames of one device pass): the
+        videos are then frames AS RENDERED (a list of frames is uploaded frame by frame, an array as one block) and every device pass
+        is upload -> resize -> ctx_cnn_stats_add_dev_u8; the statistics equal those of the same videos resized on the host."""
+        if resize is not None:
+            videos = [self._check_render(v, resize) for v in videos]
+        else:
+            videos = [self._check_frames(np.stack(v) if isinstance(v, (list, tuple)) else v) for v in videos]
         if not videos:
             raise ValueError("no videos")
-        F = videos[0].shape[0] if nframes is None else int(nframes)
-        if any(v.shape[0] != F for v in videos):
+        F = len(videos[0]) if nframes is None else int(nframes)
+        if any(len(v) != F for v in videos):
             raise ValueError(f"every video must hold {F} frames")
         layers = list(layers)
         for name in layers:
@@ -519,8 +532,14 @@ class InceptionFrontend:
         per = max(1, self.max_images // F)
         for pas in (0, 1):
             for i0 in range(0, len(videos), per):
-                fr = np.ascontiguousarray(np.concatenate(videos[i0:i0 + per]))
-                self._ck(self._lib.ctx_cnn_stats_add_u8(self._h, fr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), len(videos[i0:i0 + per]), pas))
+                grp = videos[i0:i0 + per]
+                if resize is not None:
+                    # lists stay lists (one upload per frame from where it is); arrays go up as one block
+                    src = [f for v in grp for f in v] if all(isinstance(v, list) for v in grp) else np.concatenate([np.asarray(v) for v in grp])
+                    self._ck(self._lib.ctx_cnn_stats_add_dev_u8(self._h, ctypes.c_void_p(resize.resize_u8_dev(src)), len(grp), pas))
+                    continue
+                fr = np.ascontiguousarray(np.concatenate(grp))
+                self._ck(self._lib.ctx_cnn_stats_add_u8(self._h, fr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), len(grp), pas))
             self._ck(self._lib.ctx_cnn_stats_finish(self._h, pas))
         out = OrderedDict()
         for i, name in enumerate(layers):
@@ -530,6 +549,27 @@ class InceptionFrontend:
                                                   sd.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), None))
             out[name] = (m, sd)
         return out
+
+    @staticmethod
+    def _check_render(video, resize):
+        """One video of frames as rendered: a list of uint8 [Hr, Wr, 3] arrays (kept as a list) or one uint8 [n, Hr, Wr, 3] array."""
+        size = tuple(resize.in_size) + (3,)
+        if isinstance(video, (list, tuple)):
+            video = [np.asarray(f) for f in video]
+            frames = video
+        else:
+            video = np.asarray(video)
+            if video.ndim != 4:
+                raise ValueError(f"a video must be [n,{size[0]},{size[1]},3], got {video.shape}")
+            frames = [video[0]] if len(video) else []
+            if video.shape[1:] != size:
+                raise ValueError(f"frames as rendered must be uint8 [{size[0]},{size[1]},3], got {video.shape[1:]}")
+        for f in frames:
+            if f.dtype != np.uint8:
+                raise TypeError(f"frames as rendered must be uint8, got {f.dtype} (float frames are not resized)")
+            if f.shape != size:
+                raise ValueError(f"frames as rendered must be uint8 [{size[0]},{size[1]},3], got {f.shape}")
+        return video
 
     def reward_set_stats(self, means, stds):
         """Demo statistics [nframes, h, w, c] of the `final` end point for reward_costs (uploaded once)."""
@@ -552,6 +592,17 @@ class InceptionFrontend:
         costs = np.empty((npaths, F), np.float32)
         self._ck(self._lib.ctx_cnn_reward_costs(self._h, fr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), npaths,
                                                 costs.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        return costs
+
+    def reward_costs_dev_u8(self, d_frames_u8, npaths):
+        """reward_costs on device uint8 frames [npaths * nframes, H, W, 3] (integer address, any byte alignment, written on this
+        stream or before a sync) -> costs [npaths, nframes]; same bits as reward_costs on the same bytes."""
+        F = getattr(self, "_reward_frames", 0)
+        if not F:
+            raise CtxError(_lib.CTX_E_STATE, "reward_costs: reward_set_stats first")
+        costs = np.empty((int(npaths), F), np.float32)
+        self._ck(self._lib.ctx_cnn_reward_costs_dev_u8(self._h, ctypes.c_void_p(d_frames_u8), int(npaths),
+                                                       costs.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
         return costs
 
     @property

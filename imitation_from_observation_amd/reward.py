@@ -348,7 +348,21 @@ class InceptionFeatureReward:
     ('inceptionsame': np.mean / np.std over axis 0 of their features).  Forward, statistics and cost run on the device
     (InceptionFrontend.stats / reward_costs); only the [paths, 25] costs cross PCIe.  `front` must be built with final=layer."""
 
-    def __init__(self, front, layer, batch_size=25, paths_per_launch=None):
+    # how render-size frames reach the device: "block" = gathered into one array on the host and uploaded once, "list" = one upload
+    # per frame from where the environment left it (FrameResizer's list form).  Measured (profiles/render_size_rewards.txt,
+    # DESIGN.md section 10): equal at 25 frames, list 12 ms of 63 ms faster at 250 -- not a win at both counts, so the hook gathers;
+    # an instance that always scores many paths per call may set `upload = "list"`.
+    upload = "block"
+
+    def __init__(self, front, layer, batch_size=25, paths_per_launch=None, render_size=None, resizer=None):
+        """render_size=(Hr, Wr): env_infos['imgs'] (and the rollouts / videos of build_stats / build_meanfile) hold the frames as
+        RENDERED, uint8 [Hr, Wr, 3]; the hook resizes them to the front end's size on the device (resize.FrameResizer on the front
+        end's stream, max_frames = the frames of one forward): per forward the raw frames go up once, are resized to uint8 where the
+        front end's conversion kernel reads them, and only the [paths, batch_size] costs (or the statistics) come back.  Results equal,
+        bit for bit, those of a hook without render_size fed the same frames resized on the host.  Float frames are refused (imresize
+        rescales floats by their range, which is not what the rollout does).  resizer: an object with resize(frames) (and, for the
+        device chain, resize_u8_dev) to use instead of a FrameResizer; a front end without the device entries gets resizer.resize()
+        followed by the host entry.  None (default): frames arrive at the front end's size, as before."""
         if layer == "Logits":
             raise ValueError("Logits is 2-D after TF's squeeze: the reference's mean over axes (1, 2, 3) is not defined on it")
         if getattr(front, "final", None) != layer:
@@ -358,13 +372,16 @@ class InceptionFeatureReward:
         if self.batch_size > front.max_images:
             raise ValueError(f"a path's {self.batch_size} frames exceed the front end's max_images {front.max_images}")
         self.means, self.std = None, None
+        self.render_size = None if render_size is None else (int(render_size[0]), int(render_size[1]))
+        self._rs = resizer                                       # else the FrameResizer, made at the first use
 
     @classmethod
     def for_sampler(cls, mode, layer, imsize, meanfile=None, expert_rollouts=None, inception_ckpt=None, batch_size=25,
-                    paths_per_launch=10, device=0):
+                    paths_per_launch=10, device=0, render_size=None):
         """What BaseSampler.initialize() sets up for mode.startswith('inception') (base.py:69-111): the front end on the sampler's
         imsize up to `layer` (variables from `inception_ckpt`, an .npz keyed by the TF names), and the statistics from `meanfile`
-        (mode 'inception') or from the frames of expert rollouts (mode 'inceptionsame'; the reference rolls out 20)."""
+        (mode 'inception') or from the frames of expert rollouts (mode 'inceptionsame'; the reference rolls out 20).  render_size:
+        the expert rollouts' and the paths' frames arrive as rendered (see __init__)."""
         from .inception_frontend import InceptionFrontend
         if mode not in ("inception", "inceptionsame"):
             raise ValueError(f"mode must be 'inception' or 'inceptionsame', got {mode!r}")
@@ -373,7 +390,7 @@ class InceptionFeatureReward:
         front = InceptionFrontend(imsize[0], imsize[1], max_images=batch_size * per_forward, device=device, final=layer)
         if inception_ckpt is not None:
             front.load(inception_ckpt)
-        r = cls(front, layer, batch_size=batch_size, paths_per_launch=paths_per_launch)
+        r = cls(front, layer, batch_size=batch_size, paths_per_launch=paths_per_launch, render_size=render_size)
         if mode == "inception":
             if meanfile is None:
                 raise ValueError("mode 'inception' reads its statistics from a meanfile")
@@ -383,6 +400,41 @@ class InceptionFeatureReward:
                 raise ValueError("mode 'inceptionsame' builds its statistics from expert rollouts' frames")
             r.build_stats(expert_rollouts)
         return r
+
+    # ------------------------------------------------------------------ frames as rendered
+    def _per_forward(self):
+        return max(1, self.front.max_images // self.batch_size)
+
+    def _resizer(self):
+        """render_size -> the front end's frame size, on the front end's stream; holds the frames of one forward."""
+        if self._rs is None:
+            from .resize import FrameResizer
+            self._rs = FrameResizer(self.render_size, (self.front.H, self.front.W), max_frames=self._per_forward() * self.batch_size,
+                                    device=getattr(self.front, "device", 0), stream=self.front.stream or None)
+        return self._rs
+
+    def _on_device(self):
+        return hasattr(self.front, "reward_costs_dev_u8") and hasattr(self._resizer(), "resize_u8_dev")
+
+    def _check_render(self, frames):
+        """Every frame as rendered is uint8 of exactly render_size: checked before anything is launched."""
+        want = self.render_size + (3,)
+        for f in frames:
+            f = np.asarray(f) if not isinstance(f, np.ndarray) else f
+            if f.dtype != np.uint8:
+                raise TypeError(f"with render_size the frames must be uint8 as rendered, got {f.dtype} (float frames are not resized)")
+            if f.shape != want:
+                raise ValueError(f"with render_size={self.render_size} every frame must be [{want[0]}, {want[1]}, 3], got {f.shape}")
+
+    def _render_videos(self, videos):
+        """videos of frames as rendered -> what front.stats takes: (videos, resize=) for the device chain, host-resized videos else."""
+        videos = [list(v) for v in videos]
+        for v in videos:
+            self._check_render(v)
+        rs = self._resizer()
+        if self._on_device():
+            return [v if self.upload == "list" else np.stack(v) for v in videos], dict(resize=rs)
+        return [rs.resize(np.stack(v)) for v in videos], {}
 
     # ------------------------------------------------------------------ statistics
     def set_stats(self, means, std):
@@ -398,15 +450,20 @@ class InceptionFeatureReward:
     def build_stats(self, rollouts):
         """rollouts: per expert rollout, its batch_size uint8 frames [H, W, 3] (viewpoint 0; base.py:94-105).  means / std are
         float32 np.mean / np.std over axis 0 of their features, bit for bit."""
-        (m, sd), = self.front.stats(rollouts, [self.layer], self.batch_size).values()
+        kw = {}
+        if self.render_size is not None:
+            rollouts, kw = self._render_videos(rollouts)
+        (m, sd), = self.front.stats(rollouts, [self.layer], self.batch_size, **kw).values()
         return self.set_stats(m, sd)
 
     def build_meanfile(self, videos, layers, path=None):
         """The two-pass meanfile builder of the notebooks (per layer: sum over videos / count, then sum of (v - mean)^2 / count, sqrt;
         float32): one forward per video per pass through the front end for every end point in `layers` (at or before its `final`).  Writes
         {layer: means, layer + 'std': std} to `path` (np.savez) when given; returns the dict."""
-        out = {}
-        for name, (m, sd) in self.front.stats(videos, layers, self.batch_size).items():
+        out, kw = {}, {}
+        if self.render_size is not None:
+            videos, kw = self._render_videos(videos)
+        for name, (m, sd) in self.front.stats(videos, layers, self.batch_size, **kw).items():
             out[name], out[name + "std"] = m, sd
         if path is not None:
             np.savez(path, **out)
@@ -428,10 +485,29 @@ class InceptionFeatureReward:
             if len(f) != bs:
                 raise ValueError(f"a path has {len(f)} rendered frames, the sampler's placeholder holds {bs} (base.py:72)")
         costs = np.zeros((len(paths), bs), np.float32)
+        if self.render_size is not None:
+            return self._render_costs(frames, costs)
         for p0 in range(0, len(paths), self.paths_per_launch):
             grp = frames[p0:p0 + self.paths_per_launch]
             u8 = np.stack([fr for f in grp for fr in f]).astype(np.uint8, copy=False)
             costs[p0:p0 + len(grp)] = self.front.reward_costs(u8, len(grp))
+        return costs
+
+    def _render_costs(self, frames, costs):
+        """paths_costs on frames as rendered: min(paths_per_launch, the paths of one forward) paths per call -- the resizer holds one
+        forward's frames -- each upload -> resize -> forward + cost on the front end's stream."""
+        for f in frames:
+            self._check_render(f)
+        rs, dev = self._resizer(), self._on_device()
+        per = min(self.paths_per_launch, self._per_forward())
+        for p0 in range(0, len(frames), per):
+            grp = frames[p0:p0 + per]
+            flat = [fr for f in grp for fr in f]
+            if dev:
+                addr = rs.resize_u8_dev(flat if self.upload == "list" else np.stack(flat))
+                costs[p0:p0 + len(grp)] = self.front.reward_costs_dev_u8(addr, len(grp))      # returns after the stream is drained
+            else:
+                costs[p0:p0 + len(grp)] = self.front.reward_costs(rs.resize(np.stack(flat)), len(grp))
         return costs
 
     def process_paths(self, paths):
@@ -454,14 +530,16 @@ class ThirdPersonReward:
         self.cost, self.mode = cost, mode
 
     @classmethod
-    def for_sampler(cls, mode, imsize, batch_size=32, device=0, seed=0):
+    def for_sampler(cls, mode, imsize, batch_size=32, device=0, seed=0, render_size=None):
+        """render_size=(Hr, Wr): set_data's trajectories and the paths' im_observations hold frames as rendered, resized on the device
+        (third_person.ThirdPersonCost)."""
         from .third_person import ConvDiscriminator, DomainConfusionVelocityDiscriminator, ThirdPersonCost
         if mode not in ("tpil", "gail"):
             raise ValueError(f"mode must be 'tpil' or 'gail', got {mode!r}")
         dim = [int(imsize[0]), int(imsize[1]), 3]
         disc = (DomainConfusionVelocityDiscriminator(dim, 2, 2, max_batch=batch_size, device=device, seed=seed) if mode == "tpil"
                 else ConvDiscriminator(dim, max_batch=batch_size, device=device, seed=seed))
-        return cls(ThirdPersonCost(disc, batch_size=batch_size), mode)
+        return cls(ThirdPersonCost(disc, batch_size=batch_size, render_size=render_size), mode)
 
     def set_data(self, expert, on_policy, expert_fail=None):
         return self.cost.set_data(expert, on_policy, expert_fail)

@@ -30,7 +30,7 @@ class _Discriminator:
         self._h = ctypes.c_void_p()
         self.input_dim = tuple(int(d) for d in input_dim)
         self.H, self.W, C = self.input_dim
-        self.max_batch = int(max_batch)
+        self.max_batch, self.device = int(max_batch), int(device)
         cfg = CtxDiscConfig(variant=self.variant, H=self.H, W=self.W, C=C, max_batch=self.max_batch)
         rc = self._lib.ctx_disc_create(ctypes.byref(cfg), int(device), ctypes.byref(self._h))
         if rc != _lib.CTX_OK:
@@ -219,6 +219,32 @@ class _Discriminator:
         self._ck(self._lib.ctx_disc_reward_paths(self._h, frames.ctypes.data_as(_U8), P, T, int(shift), _fp(out)))
         return out
 
+    @property
+    def stream(self):
+        """Integer hipStream_t of the handle: a FrameResizer made on it writes where the entries below read, in stream order."""
+        return self._lib.ctx_disc_stream(self._h)
+
+    def sync(self):
+        self._ck(self._lib.ctx_disc_sync(self._h))
+
+    def data_begin(self, N, T, classes, domains=None):
+        """Sizes the resident data set for uint8 [N, T, H, W, 3] and uploads the per-trajectory targets like data_upload; returns the
+        integer DEVICE address of the tensor, to be filled on `stream` (FrameResizer.resize_u8_dev(dst=address + offset)) before the
+        next train_epoch."""
+        N, T = int(N), int(T)
+        cls = np.ascontiguousarray(classes, np.float32).reshape(N, 2)
+        dom = None if domains is None else np.ascontiguousarray(domains, np.float32).reshape(N, 2)
+        d = ctypes.c_void_p()
+        self._ck(self._lib.ctx_disc_data_begin(self._h, N, T, _fp(cls), None if dom is None else _fp(dom), ctypes.byref(d)))
+        return int(d.value)
+
+    def reward_paths_dev(self, d_frames, P, T, shift=3):
+        """reward_paths on DEVICE uint8 frames [P, T, H, W, 3] (integer address, any byte alignment, written on `stream` or before a
+        sync) -> P(expert) [P, T]; same bits as reward_paths on the same bytes."""
+        out = np.empty((int(P), int(T)), np.float32)
+        self._ck(self._lib.ctx_disc_reward_paths_dev(self._h, ctypes.c_void_p(d_frames), int(P), int(T), int(shift), _fp(out)))
+        return out
+
 
 class DomainConfusionVelocityDiscriminator(_Discriminator):
     """discriminator.py:357-548 (mode 'tpil').  data_batch = [frames t, frames min(t+3, T-1)], targets_batch = dict(classes, domains)."""
@@ -265,11 +291,28 @@ class ThirdPersonCost:
     materialising the shuffled matrices, path_rewards scores policy paths many per call."""
     shift = 3
 
-    def __init__(self, disc, batch_size=32, logger=None):
+    # how render-size frames reach the device: "block" = contiguous runs of frames, gathered on the host where a chunk spans several
+    # arrays, one upload per chunk; "list" = one upload per frame from where it lies.  Measured (profiles/render_size_rewards.txt,
+    # DESIGN.md section 10): the list form is 0.05-0.8 ms slower at 25 and at 250 frames, so the hook gathers.
+    upload = "block"
+
+    def __init__(self, disc, batch_size=32, logger=None, render_size=None, resize_chunk=256, resizer=None):
+        """render_size=(Hr, Wr): set_data's trajectories and the paths' im_observations hold the frames as RENDERED, uint8
+        [.., Hr, Wr, 3]; they are resized to the discriminator's size on the device (resize.FrameResizer on the discriminator's
+        stream, resize_chunk frames per pass) and never come back: set_data resizes straight into the resident tensor, path_rewards
+        into the buffer the first conv reads.  Results equal, bit for bit, those of the same object without render_size fed the
+        frames resized on the host.  Float frames are refused (imresize rescales floats by their range, which is not what the rollout
+        does).  resizer: an object with resize(frames) (and resize_u8_dev for the device chain) used instead of a FrameResizer; a
+        discriminator without the device entries gets resizer.resize() followed by the host entry."""
         self.disc, self.batch_size, self.logger = disc, int(batch_size), logger
         self.gail = disc.variant == CTX_DISC_GAIL
         self.order = None
         self.log = []
+        self.render_size = None if render_size is None else (int(render_size[0]), int(render_size[1]))
+        self.resize_chunk = int(resize_chunk)
+        if self.render_size is not None and self.resize_chunk < 1:
+            raise ValueError(f"resize_chunk must be >= 1, got {resize_chunk}")
+        self._rs, self._own_rs = resizer, resizer is None
 
     @staticmethod
     def _per_traj(a, what):
@@ -280,17 +323,86 @@ class ThirdPersonCost:
             a = a[:, 0]
         return a
 
+    # ------------------------------------------------------------------ frames as rendered
+    def _resizer(self):
+        if self._rs is None:
+            from .resize import FrameResizer
+            self._rs = FrameResizer(self.render_size, (self.disc.H, self.disc.W), max_frames=self.resize_chunk,
+                                    device=getattr(self.disc, "device", 0), stream=self.disc.stream or None)
+        return self._rs
+
+    def _on_device(self):
+        return hasattr(self.disc, "reward_paths_dev") and hasattr(self.disc, "data_begin") and hasattr(self._resizer(), "resize_u8_dev")
+
+    def _check_render(self, a, ndim, what):
+        """a: frames as rendered with `ndim` dimensions, uint8, trailing [Hr, Wr, 3]: checked before anything is launched."""
+        a = np.asarray(a)
+        if a.dtype != np.uint8:
+            raise TypeError(f"with render_size {what} must be uint8 as rendered, got {a.dtype} (float frames are not resized)")
+        want = self.render_size + (3,)
+        if a.ndim != ndim or a.shape[-3:] != want:
+            lead = {5: "n, T, ", 4: "n, ", 3: ""}[ndim]
+            raise ValueError(f"with render_size={self.render_size} {what} must be [{lead}{want[0]}, {want[1]}, 3], got {a.shape}")
+        return np.ascontiguousarray(a)
+
+    def _chunks_of(self, runs):
+        """runs: arrays [m_i, Hr, Wr, 3] laid end to end -> per chunk of resize_chunk frames (chunks cross the arrays' boundaries)
+        (first frame index, the chunk as one contiguous array or, in the list form, as a list of frames)."""
+        total = sum(len(r) for r in runs)
+        starts = np.cumsum([0] + [len(r) for r in runs])
+        for i0 in range(0, total, self.resize_chunk):
+            i1 = min(total, i0 + self.resize_chunk)
+            parts = [r[max(i0 - s0, 0):i1 - s0] for r, s0 in zip(runs, starts[:-1]) if s0 < i1 and s0 + len(r) > i0]
+            if self.upload == "list":
+                yield i0, [f for part in parts for f in part]
+            else:
+                yield i0, (parts[0] if len(parts) == 1 else np.concatenate(parts))
+
+    def _set_data_render(self, sets, cls, dom):
+        datas = [self._check_render(s["data"], 5, "a set's data") for s in sets]
+        T = datas[0].shape[1]
+        if any(d.shape[1] != T for d in datas):
+            raise ValueError("every set must hold trajectories of the same length")
+        N = sum(d.shape[0] for d in datas)
+        if N * T == 0:
+            raise ValueError("no frames")
+        rs = self._resizer()
+        runs = [d.reshape((-1,) + d.shape[2:]) for d in datas]
+        if self._on_device():
+            base, fbytes = self.disc.data_begin(N, T, cls, dom), self.disc.H * self.disc.W * 3
+            # No sync happens between the chunks, and the resizer keeps only the latest call's frames (it waits only for copies it
+            # made itself).  A chunk that spans arrays is an np.concatenate made HERE, which the resizer takes for the caller's: this
+            # list is all that keeps those blocks, and the slices, alive until the uploads that read them are over (the sync below).
+            held = []
+            for i0, chunk in self._chunks_of(runs):
+                held.append(chunk)
+                rs.resize_u8_dev(chunk, dst=base + i0 * fbytes)
+            rs.sync()                                             # the tensor is complete (and the frames released) before train_cost
+        else:
+            small = rs.resize(np.concatenate(runs))
+            self.disc.data_upload(small.reshape((N, T) + small.shape[1:]), cls, dom)
+        return N, T
+
     def set_data(self, expert, on_policy, expert_fail=None):
         """Each argument: dict(data [n, T, H, W, 3], classes [n, T, 2] or [n, 2], domains likewise) as collect_trajs_for_cost returns
-        them; stacked in the reference's order (expert, on-policy, expert-fail; GAIL has no third set)."""
+        them; stacked in the reference's order (expert, on-policy, expert-fail; GAIL has no third set).  With render_size: data
+        [n, T, Hr, Wr, 3] uint8 as rendered, resized resize_chunk frames at a time (chunks cross trajectory and set boundaries)
+        straight into the resident tensor; the same single np.random.permutation is drawn."""
         sets = [s for s in (expert, on_policy, expert_fail) if s is not None]
+
+        def targets():
+            cls = np.concatenate([self._per_traj(s["classes"], "classes") for s in sets])
+            return cls, None if self.gail else np.concatenate([self._per_traj(s["domains"], "domains") for s in sets])
+        if self.render_size is not None:
+            self.n_traj, self.T = self._set_data_render(sets, *targets())
+            self.order = shuffled_order(self.n_traj, self.T)
+            return self.order
         data = np.concatenate([np.asarray(s["data"]) for s in sets])
         if data.dtype != np.uint8:
             if (data != np.rint(data)).any() or data.min() < 0 or data.max() > 255:
                 raise ValueError("the resident data set holds uint8 frames: pass pixel values 0..255")
             data = data.astype(np.uint8)
-        cls = np.concatenate([self._per_traj(s["classes"], "classes") for s in sets])
-        dom = None if self.gail else np.concatenate([self._per_traj(s["domains"], "domains") for s in sets])
+        cls, dom = targets()
         self.disc.data_upload(data, cls, dom)
         self.n_traj, self.T = data.shape[:2]
         self.order = shuffled_order(self.n_traj, self.T)
@@ -316,10 +428,14 @@ class ThirdPersonCost:
     def path_rewards(self, paths):
         """path['rewards'] = P(expert) of the path's frames (path['im_observations'] [n, H, W, 3]).  A rollout that ends early has fewer
         frames than the horizon: paths are grouped by length, one device call per length, the +3 partner clamped to each path's own
-        last frame."""
+        last frame.  With render_size: im_observations [n, Hr, Wr, 3] uint8 as rendered; per length as many whole paths per call as
+        fit resize_chunk frames are resized on the device and scored where they lie.  A path longer than resize_chunk raises
+        resize_chunk to that path's length, once and for good (the resizer is remade at that size)."""
         by_len = {}
         for i, p in enumerate(paths):
             by_len.setdefault(len(p["im_observations"]), []).append(i)
+        if self.render_size is not None:
+            return self._path_rewards_render(paths, by_len)
         for n, idx in by_len.items():
             if n == 0:
                 for i in idx:
@@ -331,4 +447,43 @@ class ThirdPersonCost:
             r = self.disc.reward_paths(frames, self.shift)
             for k, i in enumerate(idx):
                 paths[i]["rewards"] = r[k].copy()
+        return paths
+
+    def _path_frames(self, im_obs):
+        """One path's frames as rendered, where they lie: an array [n, Hr, Wr, 3] stays one block, a list of frames stays a list."""
+        if isinstance(im_obs, (list, tuple)):
+            return [self._check_render(f, 3, "a frame of im_observations") for f in im_obs]
+        return self._check_render(im_obs, 4, "im_observations")
+
+    def _path_rewards_render(self, paths, by_len):
+        obs = {i: self._path_frames(paths[i]["im_observations"]) for n, idx in by_len.items() if n for i in idx}
+        longest = max([n for n in by_len], default=0)
+        if longest > self.resize_chunk:                            # one path must fit one pass
+            self.resize_chunk = longest
+            if self._own_rs and self._rs is not None:
+                self._rs.close()
+                self._rs = None
+        rs = self._resizer() if obs else None
+        dev = bool(obs) and self._on_device()
+        for n, idx in by_len.items():
+            if n == 0:
+                for i in idx:
+                    paths[i]["rewards"] = np.zeros(0, np.float32)
+                continue
+            per = max(1, self.resize_chunk // n)
+            for k0 in range(0, len(idx), per):
+                grp = idx[k0:k0 + per]
+                if dev and self.upload == "list":
+                    src = [f for i in grp for f in obs[i]]
+                elif len(grp) == 1 and isinstance(obs[grp[0]], np.ndarray):
+                    src = obs[grp[0]]
+                else:
+                    src = np.stack([f for i in grp for f in obs[i]])
+                if dev:
+                    r = self.disc.reward_paths_dev(rs.resize_u8_dev(src), len(grp), n, self.shift)      # returns after the stream is drained
+                else:
+                    small = rs.resize(src)
+                    r = self.disc.reward_paths(small.reshape((len(grp), n) + small.shape[1:]), self.shift)
+                for k, i in enumerate(grp):
+                    paths[i]["rewards"] = r[k].copy()
         return paths

@@ -48,7 +48,8 @@ extern "C" {
                                still 4 (additions only): ctx_vjp_args, ctx_dev_forward_vjp, ctx_dev_backward_vjp, ctx_params_written;
                                CTX_CNN_AVGPOOL_VALID / CTX_CNN_CONV_LINEAR, ctx_cnn_stats_*, ctx_cnn_reward_*; ctx_nn_err,
                                ctx_dp_nn_err, ctx_cnn_demos_upload, ctx_cnn_forward_sampled_dev; ctx_reward_costs_dev, ctx_reward_cache_*,
-                               ctx_reward_get_cache, ctx_reward_stats, option reward_split; ctx_resize_* */
+                               ctx_reward_get_cache, ctx_reward_stats, option reward_split; ctx_resize_*; the device-uint8 forms
+                               ctx_resize_u8_dev / _v, ctx_cnn_*_dev_u8, ctx_disc_stream / _data_begin / _reward_paths_dev */
 
 enum {
     CTX_OK = 0,
@@ -500,6 +501,11 @@ int ctx_cnn_forward_u8_dev(ctx_cnn* h, const uint8_t* frames, int n, const float
 /* d_frames: DEVICE f32 [n,H,W,3] in [-1,1], n <= max_images; *d_out: device pointer of the last buffer.
  * Asynchronous on the handle's stream (ctx_cnn_stream / ctx_cnn_sync). */
 int ctx_cnn_forward_dev(ctx_cnn* h, const float* d_frames, int n, const float** d_out);
+/* d_frames: DEVICE uint8 [n,H,W,3] at the front end's size (e.g. what ctx_resize_u8_dev left on ctx_cnn_stream(h)), n <= max_images:
+ * ctx_cnn_forward_u8_dev without the upload -- the frames go straight into the conversion kernel in place of the handle's staging
+ * buffer, so the result equals ctx_cnn_forward_u8_dev on the same bytes bit for bit.  Any byte address (the kernel loads bytes);
+ * d_frames must have been written on ctx_cnn_stream(h) or before a synchronisation.  Asynchronous on the handle's stream. */
+int ctx_cnn_forward_dev_u8(ctx_cnn* h, const uint8_t* d_frames, int n, const float** d_out);
 /* The trainer's input pipeline in front of the front end (mode 'oursinception', scripts/train_script.py:144-163; data parallel as
  * ctx_dp_train_step_sampled).  ctx_cnn_demos_upload keeps vdata[T][N][H][W][3] (uint8 frames at the front end's input size) in HBM on
  * the handle's device, replacing an earlier upload (CTX_E_NOMEM when it does not fit: 33 GB at 299x299, T = 25, N = 5000).
@@ -537,13 +543,21 @@ int ctx_cnn_sync(ctx_cnn* h);
  *   ctx_cnn_reward_costs      frames: host uint8 [npaths * nframes, H, W, 3] -> costs [npaths * nframes]:
  *                             costs[f] = mean over (h, w, c) of d^2 / (std + 1e-5),  d = means[f % nframes] - x[f], d = 0 where std == 0
  *                             (terms in f32, summed in f64 in a fixed order).  Whole paths per forward; only the costs cross PCIe.
- *                             CTX_E_STATE before ctx_cnn_reward_set_stats. */
+ *                             CTX_E_STATE before ctx_cnn_reward_set_stats.
+ * Device-frame forms (frames that ctx_resize_u8_dev left on the device; no new arithmetic -- the same launches read the caller's
+ * pointer in place of the staging buffer, results bit-identical to the host forms on the same bytes).  d_frames: DEVICE uint8 at any
+ * byte address, written on ctx_cnn_stream(h) or before a synchronisation; arguments are checked as in the host forms:
+ *   ctx_cnn_stats_add_dev_u8     d_frames [nvideos * nframes, H, W, 3]; whole videos per forward, chunked and ordered exactly as
+ *                                ctx_cnn_stats_add_u8.  Synchronous (returns after the last chunk's accumulation).
+ *   ctx_cnn_reward_costs_dev_u8  d_frames [npaths * nframes, H, W, 3] -> host costs, as ctx_cnn_reward_costs.  Synchronous. */
 int ctx_cnn_stats_reset(ctx_cnn* h, const int32_t* buffers, const int32_t* channels, int nslots, int nframes);
 int ctx_cnn_stats_add_u8(ctx_cnn* h, const uint8_t* frames, int nvideos, int pass);
 int ctx_cnn_stats_finish(ctx_cnn* h, int pass);
 int ctx_cnn_stats_read(ctx_cnn* h, int slot, float* means, float* stds, int* count);
 int ctx_cnn_reward_set_stats(ctx_cnn* h, int channels, const float* means, const float* stds, int nframes);
 int ctx_cnn_reward_costs(ctx_cnn* h, const uint8_t* frames, int npaths, float* costs);
+int ctx_cnn_stats_add_dev_u8(ctx_cnn* h, const uint8_t* d_frames, int nvideos, int pass);
+int ctx_cnn_reward_costs_dev_u8(ctx_cnn* h, const uint8_t* d_frames, int npaths, float* costs);
 
 /* ---- third-person-imitation and GAIL baseline discriminators (modes 'tpil' / 'gail') ---------------------------
  * The two learned image rewards the reference compares against, both retrained inside the RL loop
@@ -575,6 +589,16 @@ int ctx_cnn_reward_costs(ctx_cnn* h, const uint8_t* frames, int npaths, float* c
  *   ctx_disc_reward_paths frames uint8 [P,T,H,W,3] -> probs[P T] = softmax(class logits)[:, 0] of the pairs (t, min(t + shift, T - 1))
  *                         (GAIL: of (frame t, time t)).  Whole paths per pass, each frame through the conv stack ONCE; equal bit for
  *                         bit to ctx_disc_logits_u8 on the materialised pairs (a row's sums do not depend on its neighbours).
+ * Device-frame forms (frames resized on the device by a ctx_resize plan that shares ctx_disc_stream(h)):
+ *   ctx_disc_stream           the handle's hipStream_t, for ctx_resize_create.
+ *   ctx_disc_reward_paths_dev d_frames: DEVICE uint8 [P,T,H,W,3] at any byte address (the conv kernel loads bytes), written on
+ *                             ctx_disc_stream(h) or before a synchronisation; otherwise ctx_disc_reward_paths, bit for bit: the first
+ *                             conv reads the caller's memory in place of the handle's input buffer.  Synchronous.
+ *   ctx_disc_data_begin       sizes the resident data set for [N,T,H,W,3] and uploads the per-trajectory targets as
+ *                             ctx_disc_data_upload does; *d_frames = the device address of the resident uint8 tensor, which the
+ *                             caller fills on ctx_disc_stream(h) (ctx_resize_u8_dev with a destination inside it) before the next
+ *                             ctx_disc_train_epoch.  Valid until the next ctx_disc_data_begin / _upload / _destroy.
+ *                             ctx_disc_data_upload == ctx_disc_data_begin followed by a copy of the same bytes.
  * ctx_disc_debug_read (tests): pool1 sel1 pool2 sel2 f hc1 hc2 hd1 hd2 logits probs of the last forward; sel = the pool windows'
  * winner (0..3, row-major) + 4 * (maximum > 0), as floats. */
 enum { CTX_DISC_TPIL = 0, CTX_DISC_GAIL = 1 };
@@ -593,6 +617,7 @@ int ctx_disc_set_adam_state(ctx_disc* h, const float* m, const float* v, size_t 
 int ctx_disc_get_adam_state(ctx_disc* h, float* m, float* v, size_t n, int64_t* step);
 int ctx_disc_init_params(ctx_disc* h, uint64_t seed);              /* the reference's initialisers; fresh Adam slots */
 int ctx_disc_sync(ctx_disc* h);
+void* ctx_disc_stream(ctx_disc* h);
 int ctx_disc_train(ctx_disc* h, const float* x1, const float* x2_or_time, const float* cls, const float* dom, int B, float lr, float* loss);
 int ctx_disc_train_u8(ctx_disc* h, const uint8_t* x1, const void* x2_or_time, const float* cls, const float* dom, int B, float lr,
                       float* loss);
@@ -604,6 +629,8 @@ int ctx_disc_data_upload(ctx_disc* h, const uint8_t* frames, int N, int T, const
 int ctx_disc_train_epoch(ctx_disc* h, const int32_t* order, int64_t n, int batch, int shift, float lr, int with_accuracy, float* losses,
                          float* accs);
 int ctx_disc_reward_paths(ctx_disc* h, const uint8_t* frames, int P, int T, int shift, float* probs);
+int ctx_disc_data_begin(ctx_disc* h, int N, int T, const float* cls, const float* dom, uint8_t** d_frames);
+int ctx_disc_reward_paths_dev(ctx_disc* h, const uint8_t* d_frames, int P, int T, int shift, float* probs);
 int ctx_disc_debug_read(ctx_disc* h, const char* name, float* host, size_t n);
 
 /* ---- device-side frame resize: scipy.misc.imresize(img, idims) for uint8 RGB frames ------------------------------
@@ -628,6 +655,17 @@ int ctx_disc_debug_read(ctx_disc* h, const char* name, float* host, size_t n);
  *                        *d_out = where it was written -- what ctx_reward_costs_dev, ctx_reward_cache_add_dev, ctx_encode_dev,
  *                        ctx_translate_dev and ctx_cnn_forward_dev take.  Asynchronous on the plan's stream: `frames` must stay
  *                        untouched until the stream has passed the upload.
+ *   ctx_resize_u8_dev    host uint8 in, DEVICE uint8 [n,Hout,Wout,C] out, written by the same launches as ctx_resize_u8 (same bits),
+ *                        n <= max_frames.  d_dst NULL: the plan's own uint8 buffer, valid until the plan's next call; else ANY byte
+ *                        address in device memory with n*Hout*Wout*C bytes behind it (the kernels store bytes), e.g. an offset into
+ *                        the tensor of ctx_disc_data_begin.  *d_out = where the result is -- what ctx_cnn_forward_dev_u8,
+ *                        ctx_cnn_stats_add_dev_u8, ctx_cnn_reward_costs_dev_u8 and ctx_disc_reward_paths_dev take.  Both passes
+ *                        skipped (equal sizes): the result is the uploaded bytes; without a destination *d_out points at the plan's
+ *                        input buffer, with one they are copied device-to-device on the stream.  Asynchronous like ctx_resize_f32_dev.
+ *   ctx_resize_u8_dev_v / ctx_resize_f32_dev_v   the same with `frames` an array of n pointers, one contiguous [Hin,Win,C] frame each
+ *                        (frames where the environment left them: no gather on the host): one hipMemcpyAsync per frame into
+ *                        consecutive slots of the plan's input buffer, then the same launches.  A NULL entry is CTX_E_INVALID before
+ *                        anything is enqueued.  Every frame must stay untouched until the stream has passed its upload.
  *   ctx_resize_profile   measurement only: one upload of n frames (pinned != 0: from a page-locked copy of them) and one run of the
  *                        kernels into the plan's f32 buffer, each between HIP events on the plan's stream (ms). */
 typedef struct ctx_resize ctx_resize;
@@ -637,6 +675,9 @@ void ctx_resize_destroy(ctx_resize* r);
 const char* ctx_resize_last_error(const ctx_resize* r);       /* r == NULL: last creation error of this thread */
 int ctx_resize_u8(ctx_resize* r, const uint8_t* frames, int n, uint8_t* out);
 int ctx_resize_f32_dev(ctx_resize* r, const uint8_t* frames, int n, float* d_dst, const float** d_out);
+int ctx_resize_u8_dev(ctx_resize* r, const uint8_t* frames, int n, uint8_t* d_dst, const uint8_t** d_out);
+int ctx_resize_u8_dev_v(ctx_resize* r, const uint8_t* const* frames, int n, uint8_t* d_dst, const uint8_t** d_out);
+int ctx_resize_f32_dev_v(ctx_resize* r, const uint8_t* const* frames, int n, float* d_dst, const float** d_out);
 int ctx_resize_sync(ctx_resize* r);
 int ctx_resize_profile(ctx_resize* r, const uint8_t* frames, int n, int pinned, float* h2d_ms, float* kernel_ms);
 
