@@ -25,6 +25,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import CnnBuf, CnnOp, CtxError
+from .render_frames import check_rendered
 
 BN_EPS = 0.001   # nets/inception_utils.py:34 (slim.batch_norm: center=True, scale=False)
 
@@ -514,7 +515,7 @@ class InceptionFrontend:
         videos are then frames AS RENDERED (a list of frames is uploaded frame by frame, an array as one block) and every device pass
         is upload -> resize -> ctx_cnn_stats_add_dev_u8; the statistics equal those of the same videos resized on the host."""
         if resize is not None:
-            videos = [self._check_render(v, resize) for v in videos]
+            videos = [check_rendered(v, resize.in_size) for v in videos]
         else:
             videos = [self._check_frames(np.stack(v) if isinstance(v, (list, tuple)) else v) for v in videos]
         if not videos:
@@ -549,27 +550,6 @@ class InceptionFrontend:
                                                   sd.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), None))
             out[name] = (m, sd)
         return out
-
-    @staticmethod
-    def _check_render(video, resize):
-        """One video of frames as rendered: a list of uint8 [Hr, Wr, 3] arrays (kept as a list) or one uint8 [n, Hr, Wr, 3] array."""
-        size = tuple(resize.in_size) + (3,)
-        if isinstance(video, (list, tuple)):
-            video = [np.asarray(f) for f in video]
-            frames = video
-        else:
-            video = np.asarray(video)
-            if video.ndim != 4:
-                raise ValueError(f"a video must be [n,{size[0]},{size[1]},3], got {video.shape}")
-            frames = [video[0]] if len(video) else []
-            if video.shape[1:] != size:
-                raise ValueError(f"frames as rendered must be uint8 [{size[0]},{size[1]},3], got {video.shape[1:]}")
-        for f in frames:
-            if f.dtype != np.uint8:
-                raise TypeError(f"frames as rendered must be uint8, got {f.dtype} (float frames are not resized)")
-            if f.shape != size:
-                raise ValueError(f"frames as rendered must be uint8 [{size[0]},{size[1]},3], got {f.shape}")
-        return video
 
     def reward_set_stats(self, means, stds):
         """Demo statistics [nframes, h, w, c] of the `final` end point for reward_costs (uploaded once)."""

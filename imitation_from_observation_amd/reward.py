@@ -16,6 +16,15 @@ from __future__ import annotations
 
 import numpy as np
 
+from .render_frames import RenderFrames, gather
+
+
+def apply_costs(paths, costs, batch_size):
+    """In place: path['rewards'][2j+1] -= costs[p][j] * j**2 (base.py:256-257; :188-189 in the Inception modes)."""
+    for p, c in zip(paths, costs):
+        for j in range(batch_size):
+            p["rewards"][j * 2 + 1] -= c[j] * (j ** 2)
+
 
 class _ResidentCacheView:
     """TranslatorReward.means / .imgs of a resident hook: view[vp] fetches that viewpoint's cache from the device (reward_get_cache)."""
@@ -57,8 +66,10 @@ class TranslatorReward:
         self.validdata = None                                    # set_demos(): the cache is then built lazily on the first path
         # mode 'oursinception' caps the demo videos at 50 (base.py:203-204); every other mode uses them all
         self.nvideos_cap = 50 if hasattr(translator, "front") else None
-        self.render_size = None if render_size is None else (int(render_size[0]), int(render_size[1]))
-        self._rs = None                                          # the FrameResizer, made at the first use
+        self._render = RenderFrames(render_size, self._resize_plan)
+        self.render_size = self._render.size
+
+    _rs = property(lambda self: self._render.rs)                 # the resizer in use (a FrameResizer, made at the first use)
 
     # means[vp] [bs, featsize] / imgs[vp] [bs, H, W, C]: host lists (resident=False), device-backed views (resident=True); None = no cache yet
     @property
@@ -112,16 +123,12 @@ class TranslatorReward:
         """env_infos['imgs'] holds, every other step, a list over viewpoints of uint8 frames (base.py:193)."""
         return [img for img in path["env_infos"]["imgs"] if img is not None]
 
-    def _resizer(self):
+    def _resize_plan(self):
         """render_size -> the translator's frame size, on the stream the translator's device entries run on (the front end's in mode
         'oursinception'); a translator without a device stream (a host stand-in) gets a private one and the host-array form."""
-        if self._rs is None:
-            from .resize import FrameResizer
-            front = getattr(self.tr, "front", None)
-            stream = front.stream if front is not None else getattr(self.tr, "stream_ptr", None)
-            self._rs = FrameResizer(self.render_size, (self.tr.H, self.tr.W), max_frames=max(self.tr.max_batch, self.batch_size),
-                                    device=getattr(self.tr, "device", getattr(front, "device", 0)), stream=stream or None)
-        return self._rs
+        front = getattr(self.tr, "front", None)
+        stream = front.stream if front is not None else getattr(self.tr, "stream_ptr", None)
+        return (self.tr.H, self.tr.W), max(self.tr.max_batch, self.batch_size), getattr(self.tr, "device", getattr(front, "device", 0)), stream
 
     def _context_frames(self, first_frames):
         """The context frame of every viewpoint (base.py:200) at the translator's size: rendered-size ones are resized to host uint8."""
@@ -130,7 +137,7 @@ class TranslatorReward:
         out = []
         for f in first_frames:
             f = np.ascontiguousarray(f, dtype=np.uint8)
-            out.append(self._resizer().resize(f) if f.shape[:2] == self.render_size else f)
+            out.append(self._render.resizer().resize(f) if f.shape[:2] == self.render_size else f)
         return out
 
     def set_demos(self, validdata):
@@ -152,47 +159,20 @@ class TranslatorReward:
         if self.resident:
             return self._build_demo_cache_resident(validdata, first_frames, distributed)
         validdata = np.asarray(validdata)
-        nvid = validdata.shape[1]
-        if self.nvideos_cap is not None:
-            nvid = min(nvid, self.nvideos_cap)
-        raw_u8 = validdata.dtype == np.uint8
-        bs = self.batch_size
+        nvid, bs = self._nvideos(validdata), self.batch_size
         self.means, self.imgs = [], []
-        per_call = max(1, self.tr.max_batch // bs)
-        rank, world = 0, 1
-        cabi = False
-        if distributed:
-            own = getattr(self.tr, "dp_world", None)
-            if callable(own) and own()[1] > 1:
-                rank, world = own()
-                cabi = True
-            else:
-                import torch
-                import torch.distributed as dist
-                rank, world = dist.get_rank(), dist.get_world_size()
-        mine = list(range(rank, nvid, world))
+        rank, world, allsum = self._group(distributed)
         for vp in range(self.nvp):
             ctx = np.ascontiguousarray(first_frames[vp], dtype=np.uint8)
             fsum = np.zeros((bs, self.tr.featsize), np.float64)
             pshape = tuple(getattr(self.tr, "pred_shape", (self.tr.H, self.tr.W, 3)))   # feature maps in mode 'oursinception'
             isum = np.zeros((bs,) + pshape, np.float64)
-            for i0 in range(0, len(mine), per_call):
-                vids = mine[i0:i0 + per_call]
-                # ((validdata[::skip, i] + 1) * 127.5).astype(np.uint8), base.py:215
-                u8 = np.concatenate([validdata[::self.skip, i][:bs] if raw_u8 else
-                                     ((validdata[::self.skip, i][:bs] + 1) * 127.5).astype(np.uint8) for i in vids])
+            for n, u8 in self._demo_batches(validdata, rank, world):
                 timg, tfeat = self.tr.translate(u8, ctx)                   # [translated_z, out], base.py:216-218
-                fsum += tfeat.reshape(len(vids), bs, -1).sum(0)
-                isum += timg.reshape((len(vids), bs) + pshape).sum(0)
-            if cabi:
-                flat = self.tr.dp_allreduce_host(np.concatenate([fsum.ravel(), isum.ravel()]))
-                fsum, isum = flat[:fsum.size].reshape(fsum.shape), flat[fsum.size:].reshape(isum.shape)
-            elif distributed and world > 1:
-                flat = torch.from_numpy(np.concatenate([fsum.ravel(), isum.ravel()]))
-                if dist.get_backend() == "nccl":
-                    flat = flat.cuda()
-                dist.all_reduce(flat, op=dist.ReduceOp.SUM)
-                flat = flat.cpu().numpy()
+                fsum += tfeat.reshape(n, bs, -1).sum(0)
+                isum += timg.reshape((n, bs) + pshape).sum(0)
+            if world > 1:
+                flat = allsum(np.concatenate([fsum.ravel(), isum.ravel()]))
                 fsum, isum = flat[:fsum.size].reshape(fsum.shape), flat[fsum.size:].reshape(isum.shape)
             self.means.append((fsum / nvid).astype(np.float32))            # np.mean(tfeats, axis=0), base.py:221
             self.imgs.append((isum / nvid).astype(np.float32))             # np.mean(timgs, axis=0), base.py:222
@@ -200,17 +180,27 @@ class TranslatorReward:
                 self.tr.reward_set_cache(vp, self.means[vp], self.imgs[vp])
         return self
 
+    def _nvideos(self, validdata):
+        return validdata.shape[1] if self.nvideos_cap is None else min(validdata.shape[1], self.nvideos_cap)
+
+    def _demo_batches(self, validdata, rank, world):
+        """(videos in the batch, their uint8 frames [videos * bs, H, W, 3]) for the demo videos rank::world below the cap, as many
+        whole videos per batch as one translate launch holds."""
+        raw_u8 = validdata.dtype == np.uint8
+        bs = self.batch_size
+        per_call = max(1, self.tr.max_batch // bs)
+        mine = list(range(rank, self._nvideos(validdata), world))
+        for i0 in range(0, len(mine), per_call):
+            vids = mine[i0:i0 + per_call]
+            # ((validdata[::skip, i] + 1) * 127.5).astype(np.uint8), base.py:215
+            yield len(vids), np.concatenate([validdata[::self.skip, i][:bs] if raw_u8 else
+                                             ((validdata[::self.skip, i][:bs] + 1) * 127.5).astype(np.uint8) for i in vids])
+
     def _build_demo_cache_resident(self, validdata, first_frames, distributed):
         """build_demo_cache with sums and cache on the device: the same videos in the same order through the same translate launches,
         added in float64 and divided once (what the host path does with numpy), but nothing is downloaded and nothing uploaded.
         distributed=True needs the translator's own RCCL group (dp_init): the sums are all-reduced where they are."""
         validdata = np.asarray(validdata)
-        nvid = validdata.shape[1]
-        if self.nvideos_cap is not None:
-            nvid = min(nvid, self.nvideos_cap)
-        raw_u8 = validdata.dtype == np.uint8
-        bs = self.batch_size
-        per_call = max(1, self.tr.max_batch // bs)
         rank, world = 0, 1
         if distributed:
             own = getattr(self.tr, "dp_world", None)
@@ -218,17 +208,13 @@ class TranslatorReward:
             if world < 1:
                 raise RuntimeError("a distributed resident demo cache is all-reduced on the device: the translator needs its own RCCL "
                                    "group (dp_init) -- or build it with resident=False over torch.distributed")
-        mine = list(range(rank, nvid, world))
         self._resident_built = False
         for vp in range(self.nvp):
             ctx = np.ascontiguousarray(first_frames[vp], dtype=np.uint8)
-            self.tr.reward_cache_begin(vp, bs)
-            for i0 in range(0, len(mine), per_call):
-                vids = mine[i0:i0 + per_call]
-                u8 = np.concatenate([validdata[::self.skip, i][:bs] if raw_u8 else
-                                     ((validdata[::self.skip, i][:bs] + 1) * 127.5).astype(np.uint8) for i in vids])
+            self.tr.reward_cache_begin(vp, self.batch_size)
+            for _, u8 in self._demo_batches(validdata, rank, world):
                 self.tr.reward_cache_add(vp, u8, ctx)
-            self.tr.reward_cache_finish(vp, nvid, distributed=distributed and world > 1)
+            self.tr.reward_cache_finish(vp, self._nvideos(validdata), distributed=distributed and world > 1)
         self._resident_built = True
         return self
 
@@ -294,35 +280,35 @@ class TranslatorReward:
             for p0 in range(0, len(paths), per_call):
                 grp = range(p0, min(len(paths), p0 + per_call))
                 u8 = np.concatenate([np.stack([fr[vp] for fr in frames[p]]).astype(np.uint8) for p in grp])
-                on_dev = False
-                if self.render_size is not None:
-                    rs = self._resizer()
-                    if hasattr(self.tr, "front") and self.resident:
-                        # raw frames up once -> f32 at the front end's size -> Mixed_7c -> encoder + cost; all on the front end's stream
-                        maps = self.tr.front.features_dev(rs.resize_dev(u8), u8.shape[0])
-                        dev, on_dev = self.tr.tr.reward_costs_dev(vp, maps, len(grp), self.scale, self.ablation_type), True
-                    elif not hasattr(self.tr, "front") and hasattr(self.tr, "reward_costs_dev"):
-                        # ... resized straight into the encoder's own frame slot (no device-to-device copy), then encoder + cost
-                        slot = self.tr.dev_frames(u8.shape[0])[0]
-                        dev, on_dev = self.tr.reward_costs_dev(vp, rs.resize_dev(u8, dst=slot), len(grp), self.scale, self.ablation_type), True
-                    else:
-                        u8 = rs.resize(u8)                                 # no device cost entry: host uint8, then the path below
-                if on_dev:
-                    pass
-                elif self.resident:
-                    # every translator type: encoder (behind the front end in mode 'oursinception') + cost on the device
-                    dev = self.tr.reward_costs_u8(vp, u8, self.scale, self.ablation_type)
-                elif hasattr(self.tr, "reward_costs"):
-                    # encoder + cost on the device: only the [paths, bs] costs cross PCIe (not the 4-bytes-per-pixel frames)
-                    dev = self.tr.reward_costs(vp, u8, self.scale, self.ablation_type)
-                else:
-                    feats, x = self.tr.encode(u8)                          # [input_z, image_trans[0]], base.py:234-235
-                for k, p in enumerate(grp):
-                    sl = slice(k * bs, (k + 1) * bs)
-                    c = dev[k] if on_dev or self.resident or hasattr(self.tr, "reward_costs") else self._costs_from(feats[sl], x[sl], vp)
+                for p, c in zip(grp, self._group_costs(vp, u8, len(grp))):
                     # 'None' accumulates over viewpoints (costs += ...); the ablations overwrite (costs = ...)
                     costs[p] = costs[p] + c if self.ablation_type == "None" else c
         return costs
+
+    def _group_costs(self, vp, u8, npaths):
+        """costs [npaths, bs] of viewpoint vp for the uint8 frames [npaths * bs, ...] of one launch group, by the first route the
+        hook and its translator allow."""
+        tr, how = self.tr, (self.scale, self.ablation_type)
+        if self.render_size is not None:
+            rs = self._render.resizer()
+            if hasattr(tr, "front") and self.resident:
+                # raw frames up once -> f32 at the front end's size -> Mixed_7c -> encoder + cost; all on the front end's stream
+                maps = tr.front.features_dev(rs.resize_dev(u8), u8.shape[0])
+                return tr.tr.reward_costs_dev(vp, maps, npaths, *how)
+            if not hasattr(tr, "front") and hasattr(tr, "reward_costs_dev"):
+                # ... resized straight into the encoder's own frame slot (no device-to-device copy), then encoder + cost
+                slot = tr.dev_frames(u8.shape[0])[0]
+                return tr.reward_costs_dev(vp, rs.resize_dev(u8, dst=slot), npaths, *how)
+            u8 = rs.resize(u8)                                             # no device cost entry: host uint8, then the routes below
+        if self.resident:
+            # every translator type: encoder (behind the front end in mode 'oursinception') + cost on the device
+            return tr.reward_costs_u8(vp, u8, *how)
+        if hasattr(tr, "reward_costs"):
+            # encoder + cost on the device: only the [paths, bs] costs cross PCIe (not the 4-bytes-per-pixel frames)
+            return tr.reward_costs(vp, u8, *how)
+        feats, x = tr.encode(u8)                                           # [input_z, image_trans[0]], base.py:234-235
+        bs = self.batch_size
+        return np.stack([self._costs_from(feats[k * bs:(k + 1) * bs], x[k * bs:(k + 1) * bs], vp) for k in range(npaths)])
 
     # ------------------------------------------------------------------ base.py:256-257
     def process_paths(self, paths, distributed=False):
@@ -334,9 +320,7 @@ class TranslatorReward:
             frames0 = self._frames_of(paths[0])
             self.build_demo_cache(self.validdata, [frames0[0][vp] for vp in range(self.nvp)], distributed=True)
         costs = self.paths_costs(paths, distributed=distributed)
-        for p, c in zip(paths, costs):
-            for j in range(self.batch_size):
-                p["rewards"][j * 2 + 1] -= c[j] * (j ** 2)
+        apply_costs(paths, costs, self.batch_size)
         return costs
 
 
@@ -372,8 +356,12 @@ class InceptionFeatureReward:
         if self.batch_size > front.max_images:
             raise ValueError(f"a path's {self.batch_size} frames exceed the front end's max_images {front.max_images}")
         self.means, self.std = None, None
-        self.render_size = None if render_size is None else (int(render_size[0]), int(render_size[1]))
-        self._rs = resizer                                       # else the FrameResizer, made at the first use
+        # render_size -> the front end's frame size, on the front end's stream; holds the frames of one forward
+        self._render = RenderFrames(render_size, lambda: ((front.H, front.W), self._per_forward() * self.batch_size,
+                                                          getattr(front, "device", 0), front.stream), resizer)
+        self.render_size = self._render.size
+
+    _rs = property(lambda self: self._render.rs)                 # the resizer in use: the injected one, else a FrameResizer
 
     @classmethod
     def for_sampler(cls, mode, layer, imsize, meanfile=None, expert_rollouts=None, inception_ckpt=None, batch_size=25,
@@ -405,36 +393,18 @@ class InceptionFeatureReward:
     def _per_forward(self):
         return max(1, self.front.max_images // self.batch_size)
 
-    def _resizer(self):
-        """render_size -> the front end's frame size, on the front end's stream; holds the frames of one forward."""
-        if self._rs is None:
-            from .resize import FrameResizer
-            self._rs = FrameResizer(self.render_size, (self.front.H, self.front.W), max_frames=self._per_forward() * self.batch_size,
-                                    device=getattr(self.front, "device", 0), stream=self.front.stream or None)
-        return self._rs
-
     def _on_device(self):
-        return hasattr(self.front, "reward_costs_dev_u8") and hasattr(self._resizer(), "resize_u8_dev")
-
-    def _check_render(self, frames):
-        """Every frame as rendered is uint8 of exactly render_size: checked before anything is launched."""
-        want = self.render_size + (3,)
-        for f in frames:
-            f = np.asarray(f) if not isinstance(f, np.ndarray) else f
-            if f.dtype != np.uint8:
-                raise TypeError(f"with render_size the frames must be uint8 as rendered, got {f.dtype} (float frames are not resized)")
-            if f.shape != want:
-                raise ValueError(f"with render_size={self.render_size} every frame must be [{want[0]}, {want[1]}, 3], got {f.shape}")
+        return self._render.on_device(self.front, "reward_costs_dev_u8")
 
     def _render_videos(self, videos):
         """videos of frames as rendered -> what front.stats takes: (videos, resize=) for the device chain, host-resized videos else."""
         videos = [list(v) for v in videos]
         for v in videos:
-            self._check_render(v)
-        rs = self._resizer()
+            self._render.check(v)
+        rs = self._render.resizer()
         if self._on_device():
-            return [v if self.upload == "list" else np.stack(v) for v in videos], dict(resize=rs)
-        return [rs.resize(np.stack(v)) for v in videos], {}
+            return [gather([v], self.upload == "list") for v in videos], dict(resize=rs)
+        return [rs.resize(gather([v])) for v in videos], {}
 
     # ------------------------------------------------------------------ statistics
     def set_stats(self, means, std):
@@ -485,37 +455,31 @@ class InceptionFeatureReward:
             if len(f) != bs:
                 raise ValueError(f"a path has {len(f)} rendered frames, the sampler's placeholder holds {bs} (base.py:72)")
         costs = np.zeros((len(paths), bs), np.float32)
-        if self.render_size is not None:
-            return self._render_costs(frames, costs)
-        for p0 in range(0, len(paths), self.paths_per_launch):
-            grp = frames[p0:p0 + self.paths_per_launch]
-            u8 = np.stack([fr for f in grp for fr in f]).astype(np.uint8, copy=False)
-            costs[p0:p0 + len(grp)] = self.front.reward_costs(u8, len(grp))
-        return costs
+        per = self.paths_per_launch
 
-    def _render_costs(self, frames, costs):
-        """paths_costs on frames as rendered: min(paths_per_launch, the paths of one forward) paths per call -- the resizer holds one
-        forward's frames -- each upload -> resize -> forward + cost on the front end's stream."""
-        for f in frames:
-            self._check_render(f)
-        rs, dev = self._resizer(), self._on_device()
-        per = min(self.paths_per_launch, self._per_forward())
-        for p0 in range(0, len(frames), per):
-            grp = frames[p0:p0 + per]
-            flat = [fr for f in grp for fr in f]
-            if dev:
-                addr = rs.resize_u8_dev(flat if self.upload == "list" else np.stack(flat))
-                costs[p0:p0 + len(grp)] = self.front.reward_costs_dev_u8(addr, len(grp))      # returns after the stream is drained
+        def score(grp):
+            return self.front.reward_costs(gather(grp).astype(np.uint8, copy=False), len(grp))
+        if self.render_size is not None:
+            # frames as rendered: min(paths_per_launch, the paths of one forward) paths per call -- the resizer holds one forward's
+            # frames -- each upload -> resize -> forward + cost on the front end's stream
+            for f in frames:
+                self._render.check(f)
+            rs, per = self._render.resizer(), min(per, self._per_forward())
+            if self._on_device():
+                def score(grp):                                    # returns after the stream is drained
+                    return self.front.reward_costs_dev_u8(rs.resize_u8_dev(gather(grp, self.upload == "list")), len(grp))
             else:
-                costs[p0:p0 + len(grp)] = self.front.reward_costs(rs.resize(np.stack(flat)), len(grp))
+                def score(grp):
+                    return self.front.reward_costs(rs.resize(gather(grp)), len(grp))
+        for p0 in range(0, len(paths), per):
+            grp = frames[p0:p0 + per]
+            costs[p0:p0 + len(grp)] = score(grp)
         return costs
 
     def process_paths(self, paths):
         """In place: path['rewards'][2j+1] -= cost_j * j**2 (base.py:188-189).  Returns the costs."""
         costs = self.paths_costs(paths)
-        for p, c in zip(paths, costs):
-            for j in range(self.batch_size):
-                p["rewards"][j * 2 + 1] -= c[j] * (j ** 2)
+        apply_costs(paths, costs, self.batch_size)
         return costs
 
 

@@ -10,6 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import CTX_DISC_GAIL, CTX_DISC_TPIL, CtxDiscConfig, CtxError
+from .render_frames import RenderFrames, gather
 
 _F = ctypes.POINTER(ctypes.c_float)
 _U8 = ctypes.POINTER(ctypes.c_uint8)
@@ -308,11 +309,15 @@ class ThirdPersonCost:
         self.gail = disc.variant == CTX_DISC_GAIL
         self.order = None
         self.log = []
-        self.render_size = None if render_size is None else (int(render_size[0]), int(render_size[1]))
+        # render_size -> the discriminator's frame size, on the discriminator's stream, resize_chunk frames per pass
+        self._render = RenderFrames(render_size, lambda: ((disc.H, disc.W), self.resize_chunk, getattr(disc, "device", 0), disc.stream),
+                                    resizer)
+        self.render_size = self._render.size
         self.resize_chunk = int(resize_chunk)
         if self.render_size is not None and self.resize_chunk < 1:
             raise ValueError(f"resize_chunk must be >= 1, got {resize_chunk}")
-        self._rs, self._own_rs = resizer, resizer is None
+
+    _rs = property(lambda self: self._render.rs)                 # the resizer in use: the injected one, else a FrameResizer
 
     @staticmethod
     def _per_traj(a, what):
@@ -324,26 +329,8 @@ class ThirdPersonCost:
         return a
 
     # ------------------------------------------------------------------ frames as rendered
-    def _resizer(self):
-        if self._rs is None:
-            from .resize import FrameResizer
-            self._rs = FrameResizer(self.render_size, (self.disc.H, self.disc.W), max_frames=self.resize_chunk,
-                                    device=getattr(self.disc, "device", 0), stream=self.disc.stream or None)
-        return self._rs
-
     def _on_device(self):
-        return hasattr(self.disc, "reward_paths_dev") and hasattr(self.disc, "data_begin") and hasattr(self._resizer(), "resize_u8_dev")
-
-    def _check_render(self, a, ndim, what):
-        """a: frames as rendered with `ndim` dimensions, uint8, trailing [Hr, Wr, 3]: checked before anything is launched."""
-        a = np.asarray(a)
-        if a.dtype != np.uint8:
-            raise TypeError(f"with render_size {what} must be uint8 as rendered, got {a.dtype} (float frames are not resized)")
-        want = self.render_size + (3,)
-        if a.ndim != ndim or a.shape[-3:] != want:
-            lead = {5: "n, T, ", 4: "n, ", 3: ""}[ndim]
-            raise ValueError(f"with render_size={self.render_size} {what} must be [{lead}{want[0]}, {want[1]}, 3], got {a.shape}")
-        return np.ascontiguousarray(a)
+        return self._render.on_device(self.disc, "reward_paths_dev", "data_begin")
 
     def _chunks_of(self, runs):
         """runs: arrays [m_i, Hr, Wr, 3] laid end to end -> per chunk of resize_chunk frames (chunks cross the arrays' boundaries)
@@ -359,14 +346,14 @@ class ThirdPersonCost:
                 yield i0, (parts[0] if len(parts) == 1 else np.concatenate(parts))
 
     def _set_data_render(self, sets, cls, dom):
-        datas = [self._check_render(s["data"], 5, "a set's data") for s in sets]
+        datas = [self._render.check(np.asarray(s["data"]), 5, "a set's data") for s in sets]
         T = datas[0].shape[1]
         if any(d.shape[1] != T for d in datas):
             raise ValueError("every set must hold trajectories of the same length")
         N = sum(d.shape[0] for d in datas)
         if N * T == 0:
             raise ValueError("no frames")
-        rs = self._resizer()
+        rs = self._render.resizer()
         runs = [d.reshape((-1,) + d.shape[2:]) for d in datas]
         if self._on_device():
             base, fbytes = self.disc.data_begin(N, T, cls, dom), self.disc.H * self.disc.W * 3
@@ -395,16 +382,14 @@ class ThirdPersonCost:
             return cls, None if self.gail else np.concatenate([self._per_traj(s["domains"], "domains") for s in sets])
         if self.render_size is not None:
             self.n_traj, self.T = self._set_data_render(sets, *targets())
-            self.order = shuffled_order(self.n_traj, self.T)
-            return self.order
-        data = np.concatenate([np.asarray(s["data"]) for s in sets])
-        if data.dtype != np.uint8:
-            if (data != np.rint(data)).any() or data.min() < 0 or data.max() > 255:
-                raise ValueError("the resident data set holds uint8 frames: pass pixel values 0..255")
-            data = data.astype(np.uint8)
-        cls, dom = targets()
-        self.disc.data_upload(data, cls, dom)
-        self.n_traj, self.T = data.shape[:2]
+        else:
+            data = np.concatenate([np.asarray(s["data"]) for s in sets])
+            if data.dtype != np.uint8:
+                if (data != np.rint(data)).any() or data.min() < 0 or data.max() > 255:
+                    raise ValueError("the resident data set holds uint8 frames: pass pixel values 0..255")
+                data = data.astype(np.uint8)
+            self.disc.data_upload(data, *targets())
+            self.n_traj, self.T = data.shape[:2]
         self.order = shuffled_order(self.n_traj, self.T)
         return self.order
 
@@ -435,55 +420,41 @@ class ThirdPersonCost:
         for i, p in enumerate(paths):
             by_len.setdefault(len(p["im_observations"]), []).append(i)
         if self.render_size is not None:
-            return self._path_rewards_render(paths, by_len)
+            score = self._render_scorer(paths, by_len)
+        else:
+            def score(grp, n):
+                frames = np.stack([np.asarray(paths[i]["im_observations"]) for i in grp])
+                if frames.dtype != np.uint8:
+                    frames = np.rint(frames).astype(np.uint8)
+                return self.disc.reward_paths(frames, self.shift)
         for n, idx in by_len.items():
             if n == 0:
                 for i in idx:
                     paths[i]["rewards"] = np.zeros(0, np.float32)
                 continue
-            frames = np.stack([np.asarray(paths[i]["im_observations"]) for i in idx])
-            if frames.dtype != np.uint8:
-                frames = np.rint(frames).astype(np.uint8)
-            r = self.disc.reward_paths(frames, self.shift)
-            for k, i in enumerate(idx):
-                paths[i]["rewards"] = r[k].copy()
-        return paths
-
-    def _path_frames(self, im_obs):
-        """One path's frames as rendered, where they lie: an array [n, Hr, Wr, 3] stays one block, a list of frames stays a list."""
-        if isinstance(im_obs, (list, tuple)):
-            return [self._check_render(f, 3, "a frame of im_observations") for f in im_obs]
-        return self._check_render(im_obs, 4, "im_observations")
-
-    def _path_rewards_render(self, paths, by_len):
-        obs = {i: self._path_frames(paths[i]["im_observations"]) for n, idx in by_len.items() if n for i in idx}
-        longest = max([n for n in by_len], default=0)
-        if longest > self.resize_chunk:                            # one path must fit one pass
-            self.resize_chunk = longest
-            if self._own_rs and self._rs is not None:
-                self._rs.close()
-                self._rs = None
-        rs = self._resizer() if obs else None
-        dev = bool(obs) and self._on_device()
-        for n, idx in by_len.items():
-            if n == 0:
-                for i in idx:
-                    paths[i]["rewards"] = np.zeros(0, np.float32)
-                continue
-            per = max(1, self.resize_chunk // n)
+            per = len(idx) if self.render_size is None else max(1, self.resize_chunk // n)
             for k0 in range(0, len(idx), per):
                 grp = idx[k0:k0 + per]
-                if dev and self.upload == "list":
-                    src = [f for i in grp for f in obs[i]]
-                elif len(grp) == 1 and isinstance(obs[grp[0]], np.ndarray):
-                    src = obs[grp[0]]
-                else:
-                    src = np.stack([f for i in grp for f in obs[i]])
-                if dev:
-                    r = self.disc.reward_paths_dev(rs.resize_u8_dev(src), len(grp), n, self.shift)      # returns after the stream is drained
-                else:
-                    small = rs.resize(src)
-                    r = self.disc.reward_paths(small.reshape((len(grp), n) + small.shape[1:]), self.shift)
+                r = score(grp, n)
                 for k, i in enumerate(grp):
                     paths[i]["rewards"] = r[k].copy()
         return paths
+
+    def _render_scorer(self, paths, by_len):
+        """score(grp, n) -> r[len(grp), n] for paths of n frames as rendered, checked here: an array [n, Hr, Wr, 3] stays one block,
+        a list of frames stays a list, where they lie."""
+        obs = {i: self._render.check(paths[i]["im_observations"], 4, "im_observations") for n, idx in by_len.items() if n for i in idx}
+        longest = max([n for n in by_len], default=0)
+        if longest > self.resize_chunk:                            # one path must fit one pass
+            self.resize_chunk = longest
+            self._render.drop()
+        rs = self._render.resizer() if obs else None
+        if obs and self._on_device():
+            def score(grp, n):                                     # returns after the stream is drained
+                src = gather([obs[i] for i in grp], self.upload == "list")
+                return self.disc.reward_paths_dev(rs.resize_u8_dev(src), len(grp), n, self.shift)
+        else:
+            def score(grp, n):
+                small = rs.resize(gather([obs[i] for i in grp]))
+                return self.disc.reward_paths(small.reshape((len(grp), n) + small.shape[1:]), self.shift)
+        return score

@@ -197,6 +197,98 @@ def test_inception_translator_is_not_picked_up_by_the_host_dispatch():
         assert callable(getattr(Translator, name))
 
 
+def test_group_costs_reaches_each_route_by_exactly_its_own_surface():
+    """TranslatorReward._group_costs: each of the five routes is taken by a stand-in that has that route's entries and no others
+    (anything else is an AttributeError), with the route's calls, arguments and order; the host-resize prefix of a render_size hook
+    without a device cost entry leads into the remaining three."""
+    from types import SimpleNamespace as NS
+    bs, npaths, vp, scale = 3, 2, 1, 0.25
+    u8 = np.arange(npaths * bs * 12, dtype=np.uint8).reshape(npaths * bs, 2, 2, 3)
+    small = u8[:, :1, :1]
+    want = np.arange(npaths * bs, dtype=np.float32).reshape(npaths, bs)
+
+    def entry(log, name, ret):
+        def f(*a, **k):
+            log.append((name,) + tuple(x.tobytes() if isinstance(x, np.ndarray) else x for x in a) + tuple(sorted(k.items())))
+            return ret
+        return f
+
+    def run(make_tr, resident, render, cache=(None, None)):
+        log = []
+        hook = TranslatorReward(make_tr(log), 2, scale, batch_size=bs, resident=resident, render_size=(2, 2) if render else None)
+        hook._render.rs = NS(resize=entry(log, "resize", small), resize_dev=entry(log, "resize_dev", "f32@dev"))
+        hook.means, hook.imgs = cache
+        return hook, hook._group_costs(vp, u8, npaths), log
+
+    # 1: frames as rendered, resident 'oursinception': resize on the device -> front end -> the inner translator's device cost entry
+    _, got, log = run(lambda log: NS(front=NS(features_dev=entry(log, "features_dev", "maps@dev")),
+                                     tr=NS(reward_costs_dev=entry(log, "reward_costs_dev", want))), True, True)
+    assert got is want and log == [("resize_dev", u8.tobytes()), ("features_dev", "f32@dev", npaths * bs),
+                                   ("reward_costs_dev", vp, "maps@dev", npaths, scale, "None")]
+    # 2: frames as rendered, a pixel translator with the device cost entry: resized into the encoder's own frame slot
+    for resident in (False, True):
+        _, got, log = run(lambda log: NS(dev_frames=entry(log, "dev_frames", ("slot", "slot2")),
+                                         reward_costs_dev=entry(log, "reward_costs_dev", want)), resident, True)
+        assert got is want and log == [("dev_frames", npaths * bs), ("resize_dev", u8.tobytes(), ("dst", "slot")),
+                                       ("reward_costs_dev", vp, "f32@dev", npaths, scale, "None")]
+    # 3: resident, frames at the translator's size -- and, as rendered without a device cost entry, behind the host resize
+    for render in (False, True):
+        _, got, log = run(lambda log: NS(reward_costs_u8=entry(log, "reward_costs_u8", want)), True, render)
+        assert got is want and log == [("resize", u8.tobytes())] * render + [("reward_costs_u8", vp, (small if render else u8).tobytes(), scale, "None")]
+    # 4: the host cache next to a device cost entry
+    for render in (False, True):
+        _, got, log = run(lambda log: NS(reward_costs=entry(log, "reward_costs", want)), False, render)
+        assert got is want and log == [("resize", u8.tobytes())] * render + [("reward_costs", vp, (small if render else u8).tobytes(), scale, "None")]
+    # 5: encode + the host formula, path by path (a non-resident 'oursinception' translator has a front end and lands here too)
+    rng = np.random.default_rng(0)
+    feats, x = rng.standard_normal((npaths * bs, 4)).astype(np.float32), rng.standard_normal((npaths * bs, 1, 1, 3)).astype(np.float32)
+    cache = [None, rng.standard_normal((bs, 4)).astype(np.float32)], [None, rng.standard_normal((bs, 1, 1, 3)).astype(np.float32)]
+    for render, front in ((False, False), (True, False), (True, True)):
+        hook, got, log = run(lambda log: NS(encode=entry(log, "encode", (feats, x)), **({"front": NS()} if front else {})), False, render,
+                             cache)
+        assert log == [("resize", u8.tobytes())] * render + [("encode", (small if render else u8).tobytes())]
+        assert got.shape == (npaths, bs) and got.dtype == np.float32
+        for k in range(npaths):
+            np.testing.assert_array_equal(got[k], hook._costs_from(feats[k * bs:(k + 1) * bs], x[k * bs:(k + 1) * bs], vp))
+
+
+def test_distributed_host_cache_shards_the_videos_and_all_reduces_one_flat_buffer_per_viewpoint():
+    """build_demo_cache(distributed=True) on a translator with its own group, rank 1 of 2: videos 1, 3, ... only are translated, and
+    per viewpoint ONE flat float64 buffer of bs * featsize + bs * H * W * 3 is all-reduced, feature sums first."""
+    bs, nvid, F, nvp = 4, 5, 6, 2
+
+    class Tr:
+        H, W, featsize, max_batch = 2, 3, F, 2 * bs
+
+        def __init__(self):
+            self.videos, self.reduced = [], []
+
+        def dp_world(self):
+            return 1, 2
+
+        def translate(self, src, ctx0):
+            assert src.dtype == np.uint8 and src.shape[0] % bs == 0 and (src.reshape(-1, bs, 18) == src.reshape(-1, bs, 18)[:, :1, :1]).all()
+            self.videos.append((int(ctx0[0, 0, 0]), [int(v) for v in src[::bs, 0, 0, 0]]))
+            one = src[:, 0, 0, 0].astype(np.float32)
+            return np.tile(one[:, None, None, None], (1, 2, 3, 3)), np.tile(-one[:, None], (1, F))
+
+        def dp_allreduce_host(self, x):
+            self.reduced.append((x.dtype, x.shape, x.copy()))
+            return x + 10.0                                       # the other rank's share
+
+    demos = np.tile(np.arange(nvid, dtype=np.uint8)[None, :, None, None, None], (bs, 1, 2, 3, 3))     # video i holds the value i
+    tr = Tr()
+    hook = TranslatorReward(tr, nvp, 1.0, batch_size=bs)
+    hook.build_demo_cache(demos, [np.full((2, 3, 3), vp, np.uint8) for vp in range(nvp)], distributed=True)
+    assert tr.videos == [(0, [1, 3]), (1, [1, 3])]
+    assert [(d, s) for d, s, _ in tr.reduced] == [(np.dtype(np.float64), (bs * F + bs * 2 * 3 * 3,))] * nvp
+    for vp in range(nvp):
+        flat = tr.reduced[vp][2]
+        assert (flat[:bs * F] == -4.0).all() and (flat[bs * F:] == 4.0).all()        # videos 1 + 3, features before frames
+        np.testing.assert_array_equal(hook.means[vp], np.full((bs, F), (-4.0 + 10.0) / nvid, np.float32))
+        np.testing.assert_array_equal(hook.imgs[vp], np.full((bs, 2, 3, 3), (4.0 + 10.0) / nvid, np.float32))
+
+
 def test_package_reward_module_does_not_import_torch():
     import subprocess
     import sys
