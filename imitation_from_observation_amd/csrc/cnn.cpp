@@ -331,7 +331,7 @@ int ctx_cnn_create(const ctx_cnn_buf* bufs, int nbufs, const ctx_cnn_op* ops, in
     if (!out) return cfail(nullptr, CTX_E_INVALID, "out is NULL");
     *out = nullptr;
     if (!bufs || !ops || nbufs <= 0 || nops <= 0 || weight_floats <= 0 || max_images <= 0) return cfail(nullptr, CTX_E_INVALID, "bad arguments");
-    if (precision != CTX_PREC_F32 && precision != CTX_PREC_BF16X3) return cfail(nullptr, CTX_E_INVALID, "unsupported precision %d", precision);
+    if (precision != CTX_PREC_F32 && precision != CTX_PREC_BF16X3 && precision != CTX_PREC_FP16X3) return cfail(nullptr, CTX_E_INVALID, "unsupported precision %d", precision);
     std::vector<ctx_cnn_buf> vb(bufs, bufs + nbufs);
     std::vector<ctx_cnn_op> vo(ops, ops + nops);
     if (validate(vb, vo, weight_floats, max_images) != CTX_OK) return CTX_E_INVALID;
@@ -374,7 +374,7 @@ int ctx_cnn_create(const ctx_cnn_buf* bufs, int nbufs, const ctx_cnn_op* ops, in
     }
     if (ok) ok = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) == hipSuccess;
     // measured at 192 images of 125x125: branch lanes -11 % in the split-bf16 mode, +2 % (and a slower chained train step) in f32
-    h->overlap = h->opt.v[OPT_CNN_LANES] < 0 ? precision == CTX_PREC_BF16X3 : h->opt.v[OPT_CNN_LANES] != 0;
+    h->overlap = h->opt.v[OPT_CNN_LANES] < 0 ? precision != CTX_PREC_F32 : h->opt.v[OPT_CNN_LANES] != 0;
     h->use_graphs = h->opt.v[OPT_GRAPHS] != 0;
     alloc((void**)&h->zeros, 256, true);
     if (!ok) { cfail(nullptr, CTX_E_NOMEM, "device allocation failed"); ctx_cnn_destroy(h); return CTX_E_NOMEM; }

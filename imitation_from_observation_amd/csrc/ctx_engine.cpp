@@ -96,11 +96,11 @@ int check_cfg(const ctx_config* c, ctx_handle* h) {
             if (hc % s || wc % s) return fail(h, CTX_E_INVALID, "feature grid %dx%d: a stride-2 layer meets an odd grid larger than 1x1", c->H, c->W);
             hc /= s; wc /= s;
         }
-        if (c->precision != CTX_PREC_F32 && c->precision != CTX_PREC_BF16X3) return fail(h, CTX_E_INVALID, "unsupported precision %d", c->precision);
+        if (c->precision != CTX_PREC_F32 && c->precision != CTX_PREC_BF16X3 && c->precision != CTX_PREC_FP16X3) return fail(h, CTX_E_INVALID, "unsupported precision %d", c->precision);
         return CTX_OK;
     }
     if (c->C != 3) return fail(h, CTX_E_INVALID, "C must be 3");
-    if (c->precision != CTX_PREC_F32 && c->precision != CTX_PREC_BF16X3) return fail(h, CTX_E_INVALID, "unsupported precision %d", c->precision);
+    if (c->precision != CTX_PREC_F32 && c->precision != CTX_PREC_BF16X3 && c->precision != CTX_PREC_FP16X3) return fail(h, CTX_E_INVALID, "unsupported precision %d", c->precision);
     if (c->variant == CTX_VARIANT_REAL) {   // ContextAEReal: two stride-2 layers, fixed filters 32/16/16/8
         if (c->H <= 0 || c->W <= 0 || c->H % 4 || c->W % 4) return fail(h, CTX_E_INVALID, "H, W must be positive multiples of 4 (got %dx%d)", c->H, c->W);
         if (c->featsize <= 0 || c->featsize % 4) return fail(h, CTX_E_INVALID, "featsize must be a multiple of 4");

@@ -16,11 +16,12 @@ namespace ctx {
 
 void splitk_reduce(hipStream_t s, const Epi& ep, int M, int N, int nprob, int nsplit);
 
-template <class LA, class LB, int MI, int NI, int WM, int WN>
-static void launch_tile_split(hipStream_t s, const LA& a, const LB& b, Epi ep, int M, int N, int nprob, int nsplit) {
+// one operand format of the split kernel (igemm_split.h: SPLIT_BF16 / SPLIT_FP16); the LDS image is the same for both
+template <int FMT, class LA, class LB, int MI, int NI, int WM, int WN>
+static void launch_tile_split_fmt(hipStream_t s, const LA& a, const LB& b, Epi ep, int M, int N, int nprob, int nsplit) {
     constexpr int NT = 64 * WM * WN, TM = 32 * MI * WM, TN = 32 * NI * WN;
     constexpr size_t lds = 2 * (size_t)(STile<LA::KM, TM, NT>::FLOATS + STile<LB::KM, TN, NT>::FLOATS) * sizeof(float);
-    if (lds > 65536) ensure_dyn_lds((const void*)igemm_split_kernel<LA, LB, MI, NI, WM, WN>, lds);
+    if (lds > 65536) ensure_dyn_lds((const void*)igemm_split_kernel<FMT, LA, LB, MI, NI, WM, WN>, lds);
     const int gm = (M + TM - 1) / TM, gn = (N + TN - 1) / TN;
     int64_t nblk = (int64_t)gm * gn * nprob * nsplit;
     if (nblk < 64) ep.xcd_swizzle = 0;
@@ -30,7 +31,15 @@ static void launch_tile_split(hipStream_t s, const LA& a, const LB& b, Epi ep, i
     }
     if (ep.xcd_swizzle && !ep.swz_group) nblk = (nblk + 7) / 8 * 8;
     dim3 grid((unsigned)nblk);
-    hipLaunchKernelGGL((igemm_split_kernel<LA, LB, MI, NI, WM, WN>), grid, dim3(NT), lds, s, a, b, ep, M, N, nprob, nsplit, gm, gn);
+    hipLaunchKernelGGL((igemm_split_kernel<FMT, LA, LB, MI, NI, WM, WN>), grid, dim3(NT), lds, s, a, b, ep, M, N, nprob, nsplit, gm, gn);
+}
+
+// prec = SplitWs::prec (CTX_PREC_BF16X3 or CTX_PREC_FP16X3): the one place a split launch picks its operand format
+template <class LA, class LB, int MI, int NI, int WM, int WN>
+static void launch_tile_split(hipStream_t s, const LA& a, const LB& b, const Epi& ep, int M, int N, int nprob, int nsplit, int prec) {
+    if (prec == SPLIT_FP16) launch_tile_split_fmt<SPLIT_FP16, LA, LB, MI, NI, WM, WN>(s, a, b, ep, M, N, nprob, nsplit);
+    else if (prec == SPLIT_BF16) launch_tile_split_fmt<SPLIT_BF16, LA, LB, MI, NI, WM, WN>(s, a, b, ep, M, N, nprob, nsplit);
+    else { fprintf(stderr, "ctxtrans: split launch with precision %d\n", prec); abort(); }
 }
 
 template <class LA, class LB, int MI, int NI, int WM, int WN>
@@ -54,7 +63,7 @@ static void launch_tile_f32(hipStream_t s, const LA& a, const LB& b, Epi ep, int
 // BIG = the 8-wave 256x256 tile is instantiated for this loader pair
 template <class LA, class LB, int MI, int NI, int WM, int WN>
 static void launch_tile(hipStream_t s, const LA& a, const LB& b, const Epi& ep, int M, int N, int nprob, int nsplit, int prec) {
-    if (prec) launch_tile_split<LA, LB, MI, NI, WM, WN>(s, a, b, ep, M, N, nprob, nsplit);
+    if (prec) launch_tile_split<LA, LB, MI, NI, WM, WN>(s, a, b, ep, M, N, nprob, nsplit, prec);
     else launch_tile_f32<LA, LB, MI, NI, WM, WN>(s, a, b, ep, M, N, nprob, nsplit);
 }
 
@@ -63,11 +72,11 @@ static void launch_tile(hipStream_t s, const LA& a, const LB& b, const Epi& ep, 
 // Eight waves (4 per SIMD at two blocks per CU) hide more of the load latency: measured per loader pair and precision at
 // B = 256 (f32: -6..-20 % everywhere; bf16x3: the conv gather prefers 4 waves), so each launcher names its pair's choice.
 template <class LA, class LB, int W, bool SPLIT>
-static void launch_128(hipStream_t s, const LA& a, const LB& b, const Epi& ep, int M, int N, int nprob, int nsplit) {
+static void launch_128(hipStream_t s, const LA& a, const LB& b, const Epi& ep, int M, int N, int nprob, int nsplit, int prec) {
     if constexpr (SPLIT) {
-        if constexpr (W == 1) launch_tile_split<LA, LB, 2, 1, 2, 4>(s, a, b, ep, M, N, nprob, nsplit);
-        else if constexpr (W == 2) launch_tile_split<LA, LB, 1, 2, 4, 2>(s, a, b, ep, M, N, nprob, nsplit);
-        else launch_tile_split<LA, LB, 2, 2, 2, 2>(s, a, b, ep, M, N, nprob, nsplit);
+        if constexpr (W == 1) launch_tile_split<LA, LB, 2, 1, 2, 4>(s, a, b, ep, M, N, nprob, nsplit, prec);
+        else if constexpr (W == 2) launch_tile_split<LA, LB, 1, 2, 4, 2>(s, a, b, ep, M, N, nprob, nsplit, prec);
+        else launch_tile_split<LA, LB, 2, 2, 2, 2>(s, a, b, ep, M, N, nprob, nsplit, prec);
     } else {
         if constexpr (W == 1) launch_tile_f32<LA, LB, 2, 1, 2, 4>(s, a, b, ep, M, N, nprob, nsplit);
         else if constexpr (W == 2) launch_tile_f32<LA, LB, 1, 2, 4, 2>(s, a, b, ep, M, N, nprob, nsplit);
@@ -166,8 +175,8 @@ static void launch_igemm(hipStream_t s, const LA& a, const LB& b, Epi ep, int M,
     else if (!ws.prec && N <= 32 && M <= 32) launch_tile_f32<LA, LB, 1, 1, 1, 1>(s, a, b, ep, M, N, nprob, nsplit);    //  32 x 32
     else if (!ws.prec && M <= 32 && N <= 64) launch_tile_f32<LA, LB, 1, 1, 1, 2>(s, a, b, ep, M, N, nprob, nsplit);    //  32 x 64
     else if (MI == 2 && NI == 2) {
-        if (ws.prec) launch_128<LA, LB, WSP, true>(s, a, b, ep, M, N, nprob, nsplit);
-        else launch_128<LA, LB, W32, false>(s, a, b, ep, M, N, nprob, nsplit);
+        if (ws.prec) launch_128<LA, LB, WSP, true>(s, a, b, ep, M, N, nprob, nsplit, ws.prec);
+        else launch_128<LA, LB, W32, false>(s, a, b, ep, M, N, nprob, nsplit, ws.prec);
     }
     // 128x64 / 64x128: eight 32x32 waves in f32 (-3 % of a step); the split tile needs >= 2 loads per thread, so 4 waves there
     else if (MI == 2 && !ws.prec) launch_tile_f32<LA, LB, 1, 1, 4, 2>(s, a, b, ep, M, N, nprob, nsplit);

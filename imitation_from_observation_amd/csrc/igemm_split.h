@@ -1,15 +1,25 @@
 // igemm_split.h -- the same implicit GEMM as igemm.h (same loaders, same epilogue, same grid and split-K
-// rules) on the bf16 matrix cores, with every f32 operand split on the fly into two bf16 terms:
+// rules) on the 16-bit matrix cores, with every f32 operand split on the fly into two 16-bit terms.  The
+// operand format FMT is a template parameter of the kernel, chosen per handle by ctx_config.precision:
+//   SPLIT_BF16 (CTX_PREC_BF16X3):
 //     x = hi + lo + O(2^-17 |x|),   hi = bf16(x),  lo = bf16(x - hi)          (both round-to-nearest-even)
 //     a*b ~= a_hi*b_hi + a_hi*b_lo + a_lo*b_hi                                  (a_lo*b_lo ~ 2^-16 |ab| dropped)
-// i.e. three v_mfma_f32_32x32x16_bf16 (16x the rate of the f32 MFMA each) with f32 accumulation replace eight
-// v_mfma_f32_32x32x2_f32: 5.3x fewer matrix-pipe cycles for a per-product relative error of ~2^-16 (1.5e-5),
-// against the 1e-3 budget the path is specified to (BASELINE.json north_star; SURVEY.md section 7 "hard parts").
-// Selected per handle by ctx_config.precision = CTX_PREC_BF16X3; the default stays exact f32.
+//   i.e. three v_mfma_f32_32x32x16_bf16 (16x the rate of the f32 MFMA each) with f32 accumulation replace eight
+//   v_mfma_f32_32x32x2_f32: 5.3x fewer matrix-pipe cycles for a per-product relative error of ~2^-16 (1.5e-5),
+//   against the 1e-3 budget the path is specified to (BASELINE.json north_star; SURVEY.md section 7 "hard parts").
+//   SPLIT_FP16 (CTX_PREC_FP16X3):
+//     y = x * 2^CTX_FP16_EXP,   hi = fp16(y),  lo = fp16(y - hi)              (both round-to-nearest-even)
+//   the same three terms on v_mfma_f32_32x32x16_f16 (same rate), the accumulators rescaled by 2^(-2 CTX_FP16_EXP) in
+//   front of the epilogue.  fp16's 11-bit significand (three bits more than bf16) leaves a_lo*b_lo ~ 2^-22 |ab|:
+//   f32-grade products -- inside fp16's exponent window.  The power-of-two operand scale keeps gradients and the lo
+//   terms above fp16's subnormals; |x| 2^CTX_FP16_EXP >= 65520 rounds hi to +-inf (a non-finite product, never a
+//   wrong finite one), and below |x| ~ 1e-3 the lo term runs into the absolute floor 2^-24 / 2^CTX_FP16_EXP
+//   (include/ctxtrans.h states the range contract; profiles/round6_e_fp16_split_errors.txt, profiles/precision_modes.txt).
+// The default stays exact f32.
 //
 // HBM holds f32 everywhere; only the LDS image changes.  Both operand kinds (KM: k-contiguous loads, NM:
-// row-contiguous loads) are written into ONE image
-//     tile[row][36 dwords] = 32 bf16 hi | 32 bf16 lo | 16 B pad          (same 144 B per row as the f32 KM tile)
+// row-contiguous loads) are written into ONE image, the same for both formats (2 bytes per term)
+//     tile[row][36 dwords] = 32 x 16-bit hi | 32 x 16-bit lo | 16 B pad      (same 144 B per row as the f32 KM tile)
 // so a lane's MFMA operand (8 consecutive k of its row) is one ds_read_b128 for hi and one for lo, conflict-free
 // (36 r mod 64 is a distinct multiple of 4 for the 16 rows of a ds_read_b128 lane group).  NM loaders transpose
 // in registers: a thread owns 4 rows x NPASS consecutive k, so each row's k-run is one packed store.
@@ -20,9 +30,6 @@ namespace ctx {
 
 // Measurement builds (never the shipped library; VERDICT r5 item 8, profiles/round6_e_fp16_split_errors.txt):
 //   make EXTRA="-DCTX_SPLIT_TERMS=n"   n = 3 (default): a_lo b_hi + a_hi b_lo + a_hi b_hi;  2: (a_hi + a_lo) b_hi;  1: a_hi b_hi
-//   make EXTRA="-DCTX_SPLIT_F16=k"     the two terms of an operand are fp16 (11-bit significand, three bits more than bf16, same MFMA rate:
-//                                      v_mfma_f32_32x32x16_f16) of x * 2^k; the power-of-two operand scale keeps gradients and the lo terms
-//                                      above fp16's subnormals (|x| 2^k < 65504 must hold) and leaves the accumulators as 2^-2k
 #ifndef CTX_SPLIT_TERMS
 #define CTX_SPLIT_TERMS 3
 #endif
@@ -32,33 +39,35 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// (x0, x1) -> packed bf16 pairs hi, lo  (element 0 in the low half)
+enum SplitFmt { SPLIT_BF16 = 1, SPLIT_FP16 = 2 };      // = CTX_PREC_BF16X3 / CTX_PREC_FP16X3 (SplitWs::prec)
+constexpr int CTX_FP16_EXP = 6;                        // SPLIT_FP16: operands are split as x * 2^6 (one constant, not a knob)
+
+// (x0, x1) -> packed 16-bit pairs hi, lo  (element 0 in the low half)
+template <int FMT>
 __device__ __forceinline__ void split2(float x0, float x1, uint32_t& hi, uint32_t& lo) {
 #ifdef CTX_ABL_SPLIT_NOCVT      // timing ablation only (WRONG numbers): the staging cost of operands that arrive pre-split -- same bytes, no conversion
     hi = __float_as_uint(x0); lo = __float_as_uint(x1);
     return;
 #endif
-#ifdef CTX_SPLIT_F16
-    {
-        const float sc = (float)(1 << CTX_SPLIT_F16);
+    if constexpr (FMT == SPLIT_FP16) {
+        const float sc = (float)(1 << CTX_FP16_EXP);
         const f32x2 v = {x0 * sc, x1 * sc};
         const f16x2 hv = __builtin_convertvector(v, f16x2);
         hi = __builtin_bit_cast(uint32_t, hv);
         const f32x2 r = {v.x - (float)hv.x, v.y - (float)hv.y};
         lo = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, f16x2));
-        return;
+    } else {
+        const f32x2 v = {x0, x1};
+        hi = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+        const f32x2 r = {x0 - __uint_as_float(hi << 16), x1 - __uint_as_float(hi & 0xffff0000u)};
+        lo = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, bf16x2));
     }
-#endif
-    const f32x2 v = {x0, x1};
-    hi = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-    const f32x2 r = {x0 - __uint_as_float(hi << 16), x1 - __uint_as_float(hi & 0xffff0000u)};
-    lo = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, bf16x2));
 }
 __device__ __forceinline__ float comp(const float4& v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
 
 constexpr int SLDR = 36;    // dwords per LDS row
 
-template <bool KMF, int TR, int NT>
+template <bool KMF, int TR, int NT, int FMT = SPLIT_BF16>
 struct STile {
     static constexpr int FLOATS = TR * SLDR;
     static constexpr int NPASS = TR * KC / 4 / NT;      // float4 per thread per chunk
@@ -77,15 +86,15 @@ struct STile {
     __device__ static void store(uint32_t* s, int tid, int j, const float4* v) {
         if (KMF) {
             uint32_t h0, l0, h1, l1;
-            split2(v[j].x, v[j].y, h0, l0);
-            split2(v[j].z, v[j].w, h1, l1);
+            split2<FMT>(v[j].x, v[j].y, h0, l0);
+            split2<FMT>(v[j].z, v[j].w, h1, l1);
             uint32_t* d = s + km_row(tid, j) * SLDR + (tid & 7) * 2;
             *reinterpret_cast<uint2*>(d) = make_uint2(h0, h1);
             *reinterpret_cast<uint2*>(d + 16) = make_uint2(l0, l1);
         } else if (NPASS == 4) {
             uint32_t h0, l0, h1, l1;
-            split2(comp(v[0], j), comp(v[1], j), h0, l0);
-            split2(comp(v[2], j), comp(v[3], j), h1, l1);
+            split2<FMT>(comp(v[0], j), comp(v[1], j), h0, l0);
+            split2<FMT>(comp(v[2], j), comp(v[3], j), h1, l1);
             uint32_t* d = s + (nm_r4(tid) + j) * SLDR + (tid % G) * 2;
             *reinterpret_cast<uint2*>(d) = make_uint2(h0, h1);
             *reinterpret_cast<uint2*>(d + 16) = make_uint2(l0, l1);
@@ -94,7 +103,7 @@ struct STile {
             for (int u = 0; u < 2; ++u) {
                 const int i = 2 * j + u;
                 uint32_t h0, l0;
-                split2(comp(v[0], i), comp(v[1], i), h0, l0);
+                split2<FMT>(comp(v[0], i), comp(v[1], i), h0, l0);
                 uint32_t* d = s + (nm_r4(tid) + i) * SLDR + (tid % G);
                 d[0] = h0;
                 d[16] = l0;
@@ -123,21 +132,21 @@ struct SFetch {
     __device__ float4 load1(const L& l, const typename L::Pos& q, int p) const { return l.load(c[p], q); }
 };
 
-__device__ __forceinline__ f32x16 mfma_bf16(const u32x4& a, const u32x4& b, const f32x16& c) {
-#ifdef CTX_SPLIT_F16
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-#else
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-#endif
+template <int FMT>
+__device__ __forceinline__ f32x16 mfma_split(const u32x4& a, const u32x4& b, const f32x16& c) {
+    if constexpr (FMT == SPLIT_FP16)
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
-template <class LA, class LB, int MI, int NI, int WM, int WN>
+template <int FMT, class LA, class LB, int MI, int NI, int WM, int WN>
 __global__ __launch_bounds__(64 * WM * WN) void igemm_split_kernel(const LA la, const LB lb, const Epi ep, int M, int N,
                                                                    int nprob, int nsplit, int gm, int gn) {
     constexpr int NT = 64 * WM * WN;
     constexpr int TM = 32 * MI * WM, TN = 32 * NI * WN;
-    using TA = STile<LA::KM, TM, NT>;
-    using TB = STile<LB::KM, TN, NT>;
+    using TA = STile<LA::KM, TM, NT, FMT>;
+    using TB = STile<LB::KM, TN, NT, FMT>;
     constexpr int NA = TA::NPASS, NB = TB::NPASS, NLS = NA + NB;
     constexpr int STAGE = TA::FLOATS + TB::FLOATS;
     constexpr int NT_ = CTX_SPLIT_TERMS, NGAP = 2 * NT_;    // MFMA groups per chunk: 2 k-steps x 3 terms
@@ -242,7 +251,7 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm_split_kernel(const LA la, 
                 for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
                     for (int ni = 0; ni < NI; ++ni)
-                        acc[mi][ni] = mfma_bf16(term == 0 ? al[ks][mi] : ah[ks][mi], term == 1 ? bl[ks][ni] : bh[ks][ni], acc[mi][ni]);
+                        acc[mi][ni] = mfma_split<FMT>(term == 0 ? al[ks][mi] : ah[ks][mi], term == 1 ? bl[ks][ni] : bh[ks][ni], acc[mi][ni]);
                 const int gl = TWO_SETS ? g : g - NGAP / 2;
 #pragma unroll
                 for (int u = 0; u < PER; ++u) {
@@ -271,14 +280,14 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm_split_kernel(const LA la, 
         }
     }
 
-#ifdef CTX_SPLIT_F16
+    if constexpr (FMT == SPLIT_FP16) {                  // the operands were x * 2^CTX_FP16_EXP: an exact power-of-two rescale
 #pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
+        for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
+            for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mi][ni][r] *= 1.0f / (float)(1ll << (2 * CTX_SPLIT_F16));
-#endif
+                for (int r = 0; r < 16; ++r) acc[mi][ni][r] *= 1.0f / (float)(1ll << (2 * CTX_FP16_EXP));
+    }
     // position-major launches (rowmode 4 / 5): the destination pixel is LINEAR in the row (= image) index; the
     // block-uniform part is resolved once here, outside the unrolled loops
     const RowMap rmap = epi_rowmap(ep, prob);

@@ -47,7 +47,7 @@ int balance_bits();
 struct SplitWs {
     float* slab;
     int64_t slab_floats;
-    int prec = 0;   // CTX_PREC_*: 0 exact-f32 MFMA, 1 split-bf16 (igemm_split.h)
+    int prec = 0;   // CTX_PREC_*: 0 exact-f32 MFMA, 1 split-bf16, 2 split-fp16 (igemm_split.h); every heuristic reads nonzero as "split mode"
     int swz = 0;    // XCD-swizzle bits the caller allows (gemm_conv.hip: xcd_swz()); measured to pay only on ContextSkipNew's launches
 };
 

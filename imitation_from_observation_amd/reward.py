@@ -94,16 +94,17 @@ class TranslatorReward:
 
     @classmethod
     def for_sampler(cls, name, imsize, nvp, scale, modelname=None, ablation_type="None", batch_size=25,
-                    paths_per_launch=10, device=0, mode="ours", inception_ckpt=None, resident=False, render_size=None):
+                    paths_per_launch=10, device=0, mode="ours", inception_ckpt=None, resident=False, render_size=None, precision=None):
         """What BaseSampler.initialize() sets up for mode 'ours' (base.py:113-145): the model class follows the
         experiment name -- ContextAEReal for 'real'/'sweep', ContextSkipNew otherwise (:134-137) -- on the
         sampler's imsize, restored from `modelname` when given (:138).  mode 'oursinception' (:121-132): frames go
         through the frozen Inception-v3 (variables from `inception_ckpt`, an .npz keyed by the TF names) and
-        ContextAEInception2 runs on the Mixed_7c feature maps."""
+        ContextAEInception2 runs on the Mixed_7c feature maps.  precision: "f32" | "bf16x3" | "fp16x3" for the Translator /
+        InceptionTranslator built here (Translator.__init__ states each mode's error and range); None = their default."""
         from .translator import Translator
         if mode == "oursinception":
             from .oursinception import InceptionTranslator
-            it = InceptionTranslator(imsize, max_batch=batch_size * paths_per_launch, device=device, train=False)
+            it = InceptionTranslator(imsize, max_batch=batch_size * paths_per_launch, device=device, train=False, precision=precision)
             if inception_ckpt is not None:
                 it.front.load(inception_ckpt)
             if modelname is not None:
@@ -112,7 +113,7 @@ class TranslatorReward:
                        render_size=render_size)
         real = name in ("real", "sweep")
         tr = Translator(imsize[0], imsize[1], featsize=100 if real else 1024, max_batch=batch_size * paths_per_launch,
-                        device=device, variant="real" if real else "skipnew")
+                        device=device, variant="real" if real else "skipnew", precision=precision)
         if modelname is not None:
             tr.load(modelname)
         return cls(tr, nvp, scale, name=name, ablation_type=ablation_type, batch_size=batch_size, resident=resident, render_size=render_size)

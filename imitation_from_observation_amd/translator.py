@@ -87,7 +87,7 @@ class Translator:
     """
 
     VARIANTS = {"skipnew": _lib.CTX_VARIANT_SKIPNEW, "real": _lib.CTX_VARIANT_REAL, "inception2": _lib.CTX_VARIANT_INCEPTION2}
-    PRECISIONS = {"f32": _lib.CTX_PREC_F32, "bf16x3": _lib.CTX_PREC_BF16X3}
+    PRECISIONS = {"f32": _lib.CTX_PREC_F32, "bf16x3": _lib.CTX_PREC_BF16X3, "fp16x3": _lib.CTX_PREC_FP16X3}
 
     def __init__(self, H=64, W=64, df_dim=64, featsize=1024, max_batch=256, device=0, stream=None, arena_ptr=None,
                  variant="skipnew", precision=None, C=3, strides=None, kernels=None, filters=None, keep_prob=None, ablation_type="None"):
@@ -99,8 +99,16 @@ class Translator:
         [16d,16d,8d,8d]).
         keep_prob (variant "real" only): tf.nn.dropout keep probability of the training graph (arm_shaping.py:1637-1661;
         ablations_code/ablations.py:544 feeds 0.5); None / 1: none.  ablation_type: which terms Adam minimises
-        (ablations.py:175-182): "None" = recon1 + recon2 + simloss, "L2" = recon1 + recon2, "L2L3" = recon1, "L1" = recon2 + simloss."""
-        precision = precision or os.environ.get("CTX_PRECISION", "f32")     # "f32" (exact) | "bf16x3" (split-bf16 products)
+        (ablations.py:175-182): "None" = recon1 + recon2 + simloss, "L2" = recon1 + recon2, "L2L3" = recon1, "L1" = recon2 + simloss.
+        precision (None = $CTX_PRECISION, else "f32"): arithmetic of the convolutions and linear layers; everything else is f32.
+          "f32"     exact f32 matrix cores.
+          "bf16x3"  operands split into bf16 hi + lo, three products: ~1e-5 on outputs and gradients, the fastest mode.
+          "fp16x3"  operands split into fp16 hi + lo of x * 2^6, three products: outputs and gradients level with "f32" (1e-6) at
+                    about the speed of "bf16x3" -- for operand magnitudes (activations, weights, gradients) from about 1e-3 up to
+                    1023.  Smaller operands degrade gradually (absolute floor per operand ~2^-24 / 64: relative 3e-6 at 1e-4,
+                    3e-4 at 1e-6).  An operand with |x| * 64 >= 65520 becomes +-inf: that call's scalars / features come back
+                    non-finite, never as a wrong finite number."""
+        precision = precision or os.environ.get("CTX_PRECISION", "f32")     # "f32" (exact) | "bf16x3" | "fp16x3" (split products)
         self._lib = _lib.load()
         self.variant, self.precision = variant, precision
         self.cfg = self.make_config(variant, H, W, C, df_dim, featsize, max_batch, precision, strides, kernels, filters, keep_prob, ablation_type)

@@ -75,12 +75,25 @@ enum {
 };
 
 /* Arithmetic of the convolutions / linear layers (everything else -- epilogues, losses, reductions, Adam,
- * parameters, activations in HBM -- is f32 in both modes):
+ * parameters, activations in HBM -- is f32 in every mode):
  *   CTX_PREC_F32     v_mfma_f32_32x32x2_f32: bitwise an fmaf chain.
  *   CTX_PREC_BF16X3  every f32 operand is split on the fly into bf16 hi + bf16 lo and a*b is evaluated as
  *                    hi*hi + hi*lo + lo*hi on the bf16 matrix cores with f32 accumulation: ~2^-16 relative error
- *                    per product, inside the 1e-3 budget of the path, at 16/3 the f32 matrix rate. */
-enum { CTX_PREC_F32 = 0, CTX_PREC_BF16X3 = 1 };
+ *                    per product, inside the 1e-3 budget of the path, at 16/3 the f32 matrix rate.
+ *   CTX_PREC_FP16X3  the same three terms with fp16 hi + fp16 lo of x * 2^6 on the fp16 matrix cores (same rate), the
+ *                    f32 accumulators rescaled by 2^-12: fp16's 11-bit significand makes the dropped lo*lo term
+ *                    ~2^-22, so outputs and gradients are level with CTX_PREC_F32 (1e-6) -- inside a window of
+ *                    operand magnitudes (operands = activations, weights, gradients: whatever a convolution or
+ *                    linear layer multiplies).  Range contract:
+ *                      small  f32-grade for |x| from about 1e-3 up to 1023.  Below, the error degrades gradually:
+ *                             the absolute floor per operand is about 2^-24 / 64 (fp16's smallest subnormal over
+ *                             the operand scale), e.g. relative 3e-6 for operands ~1e-4, 3e-4 for ~1e-6.
+ *                      large  an operand with |x| * 64 >= 65520 (|x| >= 1023.75) becomes +-inf in its hi term: the
+ *                             product is non-finite and the inf / NaN reaches the scalars or features of that
+ *                             call.  A large operand never yields a wrong finite number.
+ *                    The scale 2^6 is fixed (no dynamic or per-operand scaling).
+ * An addition to the enum only: CTX_ABI_VERSION and the ctx_config layout are those of ABI 4. */
+enum { CTX_PREC_F32 = 0, CTX_PREC_BF16X3 = 1, CTX_PREC_FP16X3 = 2 };
 
 typedef struct ctx_config {
     int32_t variant;    /* CTX_VARIANT_* */

@@ -1,8 +1,9 @@
-"""Error table of the split-precision mode (ctx_config.precision = bf16x3: whatever operand format / term count libctxtrans.so was BUILT
-with -- igemm_split.h: CTX_SPLIT_F16, CTX_SPLIT_TERMS) against the B = 256 float64 fixture of BASELINE configs[1]
+"""Error table of the split-precision modes (ctx_config.precision = bf16x3 and fp16x3; the term count is what libctxtrans.so was BUILT
+with -- igemm_split.h: CTX_SPLIT_TERMS) against the B = 256 float64 fixture of BASELINE configs[1]
 (tests/golden/b256_skipnew_*.npz): outputs, scalars, per-tensor gradient deviations (4096 samples + 16 projections), and ms/step.
    python tools/split_errors_b256.py [label]
-Measurement tool of VERDICT r5 item 8 (profiles/round6_e_fp16_split_errors.txt); the exact-f32 row is printed first as the yardstick."""
+Measurement tool of VERDICT r5 item 8 (profiles/round6_e_fp16_split_errors.txt, whose fp16 rows came from the compile-time switch that
+precision="fp16x3" replaced); the exact-f32 row is printed first as the yardstick."""
 import os
 import sys
 import time
@@ -31,7 +32,7 @@ def relmax(a, b):
     return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-300))
 
 
-for prec in ("f32", "bf16x3"):
+for prec in ("f32", "bf16x3", "fp16x3"):
     with Translator(cfg.H, cfg.W, cfg.df_dim, cfg.featsize, max_batch=B, precision=prec) as tr:
         tr.set_params(p)
         ev = tr.evaluate(src, ctx, tgt)
@@ -59,7 +60,7 @@ for prec in ("f32", "bf16x3"):
             tr.dev_adam(0.0)
         tr.sync()
         ms = (time.perf_counter() - t0) / 15 * 1e3
-    tag = "exact f32" if prec == "f32" else label
+    tag = "exact f32" if prec == "f32" else f"{label} {prec}"
     wn = max(samp, key=samp.get)
     d4 = max(samp[n] for n in names if n.startswith("deconv/d_h4"))       # upstream of every lrelu' mask: pure product error, no branch flips
     print(f"{tag:34s} {ms:6.2f} ms/step | out {outs['out']:.1e} out2 {outs['out2']:.1e} translated_z {outs['translated_z']:.1e} input_z {outs['input_z']:.1e} | "
