@@ -13,6 +13,7 @@ CTX_VARIANT_INCEPTION2 = 2
 CTX_PREC_F32 = 0
 CTX_PREC_BF16X3 = 1
 CTX_PREC_FP16X3 = 2
+CTX_PREC_FP16X3D = 3
 CTX_DP_UNIQUE_ID_BYTES = 128
 CTX_DISC_TPIL, CTX_DISC_GAIL = 0, 1
 CTX_REWARD_STATS = ("d2h_bytes", "cost_calls", "split_launches", "plain_launches")      # ctx_reward_stats, in index order

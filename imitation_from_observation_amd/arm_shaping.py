@@ -139,7 +139,7 @@ class ContextAEInception2(ContextSkipNew):
             setattr(self, f, f)
 
     def build(self, image, device=0, seed=None, precision=None):
-        """precision: "f32" | "bf16x3" | "fp16x3" (Translator.__init__); None = the translator's default."""
+        """precision: "f32" | "bf16x3" | "fp16x3" | "fp16x3d" (Translator.__init__); None = the translator's default."""
         shape = tuple(getattr(image, "shape", image))
         if len(shape) != 5 or shape[0] != 3:
             raise ValueError(f"expected (3, batch, h, w, C) feature maps, got {shape}")

@@ -42,6 +42,7 @@ struct ctx_cnn {
     static constexpr int NLANE = 4;                   // branch lanes: lane 0 is `stream`
     hipStream_t lane[NLANE] = {};
     float* slab[NLANE] = {};                          // one split-K workspace per lane
+    SplitSlots slots[NLANE];                          // CTX_PREC_FP16X3D: one ring of scale slots per lane (launch.h)
     float* wpack[NLANE] = {};                         // dconv's re-packed filter, per lane
     int64_t slab_floats = 0;
     std::vector<hipEvent_t> done;                     // done[i]: op i finished (recorded on its lane)
@@ -178,7 +179,7 @@ int run(ctx_cnn* h, int n, std::vector<hipEvent_t>* ev = nullptr) {
         hipStream_t st = h->lane[L];
         if (ev) (void)hipEventRecord((*ev)[oi], st);
         if (par) for (int j : h->deps[oi]) (void)hipStreamWaitEvent(st, h->done[j], 0);
-        const SplitWs ws{h->slab[L], h->slab_floats, h->precision};
+        const SplitWs ws{h->slab[L], h->slab_floats, h->precision, 0, &h->slots[L]};
         const ctx_cnn_buf &in = h->bufs[op.src], &out = h->bufs[op.dst];
         const float* x = h->dbuf[op.src] + (is_conv(op.kind) ? op.src_ch0 : 0);
         const int cin = is_conv(op.kind) && op.src_c ? op.src_c : in.c;      // channels the conv reads (row stride stays in.c)
@@ -331,7 +332,7 @@ int ctx_cnn_create(const ctx_cnn_buf* bufs, int nbufs, const ctx_cnn_op* ops, in
     if (!out) return cfail(nullptr, CTX_E_INVALID, "out is NULL");
     *out = nullptr;
     if (!bufs || !ops || nbufs <= 0 || nops <= 0 || weight_floats <= 0 || max_images <= 0) return cfail(nullptr, CTX_E_INVALID, "bad arguments");
-    if (precision != CTX_PREC_F32 && precision != CTX_PREC_BF16X3 && precision != CTX_PREC_FP16X3) return cfail(nullptr, CTX_E_INVALID, "unsupported precision %d", precision);
+    if (precision < CTX_PREC_F32 || precision > CTX_PREC_FP16X3D) return cfail(nullptr, CTX_E_INVALID, "unsupported precision %d", precision);
     std::vector<ctx_cnn_buf> vb(bufs, bufs + nbufs);
     std::vector<ctx_cnn_op> vo(ops, ops + nops);
     if (validate(vb, vo, weight_floats, max_images) != CTX_OK) return CTX_E_INVALID;
@@ -365,6 +366,11 @@ int ctx_cnn_create(const ctx_cnn_buf* bufs, int nbufs, const ctx_cnn_op* ops, in
         alloc((void**)&h->wpack[l], (size_t)DC_WPACK_FLOATS * sizeof(float), false);
         if (l && ok) ok = hipStreamCreateWithFlags(&h->lane[l], hipStreamNonBlocking) == hipSuccess;
     }
+    if (precision == CTX_PREC_FP16X3D) {              // zeroed once: the slots keep themselves clean
+        SplitSlot* sl = nullptr;
+        alloc((void**)&sl, sizeof(SplitSlot) * SPLIT_RING * ctx_cnn::NLANE, true);
+        for (int l = 0; l < ctx_cnn::NLANE && sl; ++l) h->slots[l] = SplitSlots{sl + l * SPLIT_RING, 0};
+    }
     h->done.assign(nops, nullptr);
     h->deps.assign(nops, {});
     for (int i = 0; i < nops && ok; ++i) {
@@ -388,6 +394,7 @@ void ctx_cnn_destroy(ctx_cnn* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (float* p : h->dbuf) if (p) (void)hipFree(p);
     for (void* p : {(void*)h->weights, (void*)h->u8, (void*)h->f32in, (void*)h->zeros}) if (p) (void)hipFree(p);
+    if (h->slots[0].dev) (void)hipFree(h->slots[0].dev);
     for (int l = 0; l < ctx_cnn::NLANE; ++l) {
         if (h->slab[l]) (void)hipFree(h->slab[l]);
         if (h->wpack[l]) (void)hipFree(h->wpack[l]);

@@ -96,11 +96,11 @@ int check_cfg(const ctx_config* c, ctx_handle* h) {
             if (hc % s || wc % s) return fail(h, CTX_E_INVALID, "feature grid %dx%d: a stride-2 layer meets an odd grid larger than 1x1", c->H, c->W);
             hc /= s; wc /= s;
         }
-        if (c->precision != CTX_PREC_F32 && c->precision != CTX_PREC_BF16X3 && c->precision != CTX_PREC_FP16X3) return fail(h, CTX_E_INVALID, "unsupported precision %d", c->precision);
+        if (c->precision < CTX_PREC_F32 || c->precision > CTX_PREC_FP16X3D) return fail(h, CTX_E_INVALID, "unsupported precision %d", c->precision);
         return CTX_OK;
     }
     if (c->C != 3) return fail(h, CTX_E_INVALID, "C must be 3");
-    if (c->precision != CTX_PREC_F32 && c->precision != CTX_PREC_BF16X3 && c->precision != CTX_PREC_FP16X3) return fail(h, CTX_E_INVALID, "unsupported precision %d", c->precision);
+    if (c->precision < CTX_PREC_F32 || c->precision > CTX_PREC_FP16X3D) return fail(h, CTX_E_INVALID, "unsupported precision %d", c->precision);
     if (c->variant == CTX_VARIANT_REAL) {   // ContextAEReal: two stride-2 layers, fixed filters 32/16/16/8
         if (c->H <= 0 || c->W <= 0 || c->H % 4 || c->W % 4) return fail(h, CTX_E_INVALID, "H, W must be positive multiples of 4 (got %dx%d)", c->H, c->W);
         if (c->featsize <= 0 || c->featsize % 4) return fail(h, CTX_E_INVALID, "featsize must be a multiple of 4");
@@ -180,6 +180,13 @@ int alloc_tail(ctx_handle* h, int64_t slab_floats, int64_t maxc) {
         TRY(dev_alloc(h, &h->scratchL[l], scratch));
         TRY(dev_alloc(h, &h->wpackL[l], DC_WPACK_FLOATS));
     }
+    if (h->cfg.precision == CTX_PREC_FP16X3D) {       // one ring of scale slots per lane, zeroed once: the slots keep themselves clean (launch.h)
+        SplitSlot* sl = nullptr;
+        const int64_t n = (int64_t)(ctx_handle::NLANE + 1) * SPLIT_RING;
+        TRY(dev_alloc(h, &sl, n));
+        if (hipMemset(sl, 0, n * sizeof(SplitSlot)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(h, CTX_E_DEVICE, "hipMemset(scale slots)");
+        for (int l = 0; l <= ctx_handle::NLANE; ++l) h->slots[l] = SplitSlots{sl + l * SPLIT_RING, 0};
+    }
     TRY(dev_alloc(h, &h->scalars, 4));
     TRY(dev_alloc(h, &h->zeros, 64));
     if (hipMemset(h->zeros, 0, 64 * sizeof(float)) != hipSuccess) return fail(h, CTX_E_DEVICE, "hipMemset(zeros)");
@@ -243,7 +250,11 @@ void pack_c4(ctx_handle* h, const float* p3, int64_t npix) { pack3to4(h->stream,
 // terms of `loss` (ctx_config.loss_terms; 0 = all)
 int loss_terms_of(const ctx_handle* h) { return h->cfg.loss_terms ? h->cfg.loss_terms : 7; }
 
-SplitWs ws_of(ctx_handle* h) { return SplitWs{h->slab, h->slab_floats, h->cfg.precision, h->rt.swz}; }
+SplitWs ws_of(ctx_handle* h) {
+    SplitSlots* sl = &h->slots[0];                    // the ring of the lane whose slab is current (LaneSwap / Side below)
+    for (int l = 0; l < ctx_handle::NLANE; ++l) if (h->slab == h->slabL[l]) sl = &h->slots[1 + l];
+    return SplitWs{h->slab, h->slab_floats, h->cfg.precision, h->rt.swz, sl};
+}
 
 // Everything below enqueues on h->stream with h->slab / h->scratch; LaneSwap points those at the second lane
 // for the lifetime of a scope.  fork(): the second lane starts after everything enqueued so far on the

@@ -147,6 +147,7 @@ struct ctx_handle {
     hipStream_t aux[NLANE] = {};
     hipEvent_t ev_fork[NLANE] = {}, ev_join[NLANE] = {};
     float *slabL[NLANE] = {}, *scratchL[NLANE] = {};
+    SplitSlots slots[NLANE + 1];   // CTX_PREC_FP16X3D: the scale-slot rings (launch.h) that go with slab ([0]) and slabL[l] ([1 + l])
     float *wpack = nullptr, *wpackL[NLANE] = {};   // dconv's re-packed filters, one buffer per stream lane (concurrent launches)
     bool overlap = true;
     // hipGraph cache of the two inference forwards (reward hook: batch-25 calls are launch-bound): key = mode * 2^20 + B

@@ -16,9 +16,10 @@ namespace ctx {
 
 void splitk_reduce(hipStream_t s, const Epi& ep, int M, int N, int nprob, int nsplit);
 
-// one operand format of the split kernel (igemm_split.h: SPLIT_BF16 / SPLIT_FP16); the LDS image is the same for both
+// one operand format of the split kernel (igemm_split.h: SPLIT_BF16 / SPLIT_FP16 / SPLIT_FP16D); the LDS image is the same for all.
+// dyn (SPLIT_FP16D only): the launch's device-resident scales, SplitSlot::scale
 template <int FMT, class LA, class LB, int MI, int NI, int WM, int WN>
-static void launch_tile_split_fmt(hipStream_t s, const LA& a, const LB& b, Epi ep, int M, int N, int nprob, int nsplit) {
+static void launch_tile_split_fmt(hipStream_t s, const LA& a, const LB& b, Epi ep, int M, int N, int nprob, int nsplit, const float* dyn = nullptr) {
     constexpr int NT = 64 * WM * WN, TM = 32 * MI * WM, TN = 32 * NI * WN;
     constexpr size_t lds = 2 * (size_t)(STile<LA::KM, TM, NT>::FLOATS + STile<LB::KM, TN, NT>::FLOATS) * sizeof(float);
     if (lds > 65536) ensure_dyn_lds((const void*)igemm_split_kernel<FMT, LA, LB, MI, NI, WM, WN>, lds);
@@ -31,13 +32,24 @@ static void launch_tile_split_fmt(hipStream_t s, const LA& a, const LB& b, Epi e
     }
     if (ep.xcd_swizzle && !ep.swz_group) nblk = (nblk + 7) / 8 * 8;
     dim3 grid((unsigned)nblk);
-    hipLaunchKernelGGL((igemm_split_kernel<FMT, LA, LB, MI, NI, WM, WN>), grid, dim3(NT), lds, s, a, b, ep, M, N, nprob, nsplit, gm, gn);
+    hipLaunchKernelGGL((igemm_split_kernel<FMT, LA, LB, MI, NI, WM, WN>), grid, dim3(NT), lds, s, a, b, ep, M, N, nprob, nsplit, gm, gn, dyn);
 }
 
-// prec = SplitWs::prec (CTX_PREC_BF16X3 or CTX_PREC_FP16X3): the one place a split launch picks its operand format
+// ws.prec (CTX_PREC_BF16X3, CTX_PREC_FP16X3 or CTX_PREC_FP16X3D): the one place a split launch picks its operand format -- and, having
+// both loaders in hand, the one place the per-operand scales of CTX_PREC_FP16X3D are taken: the loaders state the floats the product
+// reads (igemm.h: ranges), split_absmax turns their largest magnitudes into the next slot of the lane's ring, the product reads it.
 template <class LA, class LB, int MI, int NI, int WM, int WN>
-static void launch_tile_split(hipStream_t s, const LA& a, const LB& b, const Epi& ep, int M, int N, int nprob, int nsplit, int prec) {
-    if (prec == SPLIT_FP16) launch_tile_split_fmt<SPLIT_FP16, LA, LB, MI, NI, WM, WN>(s, a, b, ep, M, N, nprob, nsplit);
+static void launch_tile_split(hipStream_t s, const LA& a, const LB& b, const Epi& ep, int M, int N, int nprob, int nsplit, const SplitWs& ws) {
+    const int prec = ws.prec;
+    if (prec == SPLIT_FP16D) {
+        if (!ws.slots || !ws.slots->dev) { set_launch_error("fp16x3d launch without scale slots"); return; }
+        SplitSlot* slot = ws.slots->next();
+        AmaxOp ra, rb;
+        a.ranges(ra, b); b.ranges(rb, a);
+        split_absmax(s, ra, rb, slot);
+        launch_tile_split_fmt<SPLIT_FP16D, LA, LB, MI, NI, WM, WN>(s, a, b, ep, M, N, nprob, nsplit, slot->scale);
+    }
+    else if (prec == SPLIT_FP16) launch_tile_split_fmt<SPLIT_FP16, LA, LB, MI, NI, WM, WN>(s, a, b, ep, M, N, nprob, nsplit);
     else if (prec == SPLIT_BF16) launch_tile_split_fmt<SPLIT_BF16, LA, LB, MI, NI, WM, WN>(s, a, b, ep, M, N, nprob, nsplit);
     else { fprintf(stderr, "ctxtrans: split launch with precision %d\n", prec); abort(); }
 }
@@ -62,8 +74,8 @@ static void launch_tile_f32(hipStream_t s, const LA& a, const LB& b, Epi ep, int
 
 // BIG = the 8-wave 256x256 tile is instantiated for this loader pair
 template <class LA, class LB, int MI, int NI, int WM, int WN>
-static void launch_tile(hipStream_t s, const LA& a, const LB& b, const Epi& ep, int M, int N, int nprob, int nsplit, int prec) {
-    if (prec) launch_tile_split<LA, LB, MI, NI, WM, WN>(s, a, b, ep, M, N, nprob, nsplit, prec);
+static void launch_tile(hipStream_t s, const LA& a, const LB& b, const Epi& ep, int M, int N, int nprob, int nsplit, const SplitWs& ws) {
+    if (ws.prec) launch_tile_split<LA, LB, MI, NI, WM, WN>(s, a, b, ep, M, N, nprob, nsplit, ws);
     else launch_tile_f32<LA, LB, MI, NI, WM, WN>(s, a, b, ep, M, N, nprob, nsplit);
 }
 
@@ -72,11 +84,11 @@ static void launch_tile(hipStream_t s, const LA& a, const LB& b, const Epi& ep, 
 // Eight waves (4 per SIMD at two blocks per CU) hide more of the load latency: measured per loader pair and precision at
 // B = 256 (f32: -6..-20 % everywhere; bf16x3: the conv gather prefers 4 waves), so each launcher names its pair's choice.
 template <class LA, class LB, int W, bool SPLIT>
-static void launch_128(hipStream_t s, const LA& a, const LB& b, const Epi& ep, int M, int N, int nprob, int nsplit, int prec) {
+static void launch_128(hipStream_t s, const LA& a, const LB& b, const Epi& ep, int M, int N, int nprob, int nsplit, const SplitWs& ws) {
     if constexpr (SPLIT) {
-        if constexpr (W == 1) launch_tile_split<LA, LB, 2, 1, 2, 4>(s, a, b, ep, M, N, nprob, nsplit, prec);
-        else if constexpr (W == 2) launch_tile_split<LA, LB, 1, 2, 4, 2>(s, a, b, ep, M, N, nprob, nsplit, prec);
-        else launch_tile_split<LA, LB, 2, 2, 2, 2>(s, a, b, ep, M, N, nprob, nsplit, prec);
+        if constexpr (W == 1) launch_tile_split<LA, LB, 2, 1, 2, 4>(s, a, b, ep, M, N, nprob, nsplit, ws);
+        else if constexpr (W == 2) launch_tile_split<LA, LB, 1, 2, 4, 2>(s, a, b, ep, M, N, nprob, nsplit, ws);
+        else launch_tile_split<LA, LB, 2, 2, 2, 2>(s, a, b, ep, M, N, nprob, nsplit, ws);
     } else {
         if constexpr (W == 1) launch_tile_f32<LA, LB, 2, 1, 2, 4>(s, a, b, ep, M, N, nprob, nsplit);
         else if constexpr (W == 2) launch_tile_f32<LA, LB, 1, 2, 4, 2>(s, a, b, ep, M, N, nprob, nsplit);
@@ -95,7 +107,7 @@ static void launch_igemm(hipStream_t s, const LA& a, const LB& b, Epi ep, int M,
         // (since the 128x128 tile runs eight waves the 256x256 tile only pays in the split-bf16 mode: f32 conv gather -2.4 % without it)
         if (M >= 256 && N >= 256 && big_tiles >= 192 && ws.prec) {
             ep.slab = nullptr;
-            launch_tile<LA, LB, 2, 4, 4, 2>(s, a, b, ep, M, N, nprob, 1, ws.prec);
+            launch_tile<LA, LB, 2, 4, 4, 2>(s, a, b, ep, M, N, nprob, 1, ws);
             return;
         }
     }
@@ -175,15 +187,15 @@ static void launch_igemm(hipStream_t s, const LA& a, const LB& b, Epi ep, int M,
     else if (!ws.prec && N <= 32 && M <= 32) launch_tile_f32<LA, LB, 1, 1, 1, 1>(s, a, b, ep, M, N, nprob, nsplit);    //  32 x 32
     else if (!ws.prec && M <= 32 && N <= 64) launch_tile_f32<LA, LB, 1, 1, 1, 2>(s, a, b, ep, M, N, nprob, nsplit);    //  32 x 64
     else if (MI == 2 && NI == 2) {
-        if (ws.prec) launch_128<LA, LB, WSP, true>(s, a, b, ep, M, N, nprob, nsplit, ws.prec);
-        else launch_128<LA, LB, W32, false>(s, a, b, ep, M, N, nprob, nsplit, ws.prec);
+        if (ws.prec) launch_128<LA, LB, WSP, true>(s, a, b, ep, M, N, nprob, nsplit, ws);
+        else launch_128<LA, LB, W32, false>(s, a, b, ep, M, N, nprob, nsplit, ws);
     }
     // 128x64 / 64x128: eight 32x32 waves in f32 (-3 % of a step); the split tile needs >= 2 loads per thread, so 4 waves there
     else if (MI == 2 && !ws.prec) launch_tile_f32<LA, LB, 1, 1, 4, 2>(s, a, b, ep, M, N, nprob, nsplit);
     else if (NI == 2 && !ws.prec) launch_tile_f32<LA, LB, 1, 1, 2, 4>(s, a, b, ep, M, N, nprob, nsplit);
-    else if (MI == 2) launch_tile<LA, LB, 2, 1, 2, 2>(s, a, b, ep, M, N, nprob, nsplit, ws.prec);
-    else if (NI == 2) launch_tile<LA, LB, 1, 2, 2, 2>(s, a, b, ep, M, N, nprob, nsplit, ws.prec);
-    else launch_tile<LA, LB, 1, 1, 2, 2>(s, a, b, ep, M, N, nprob, nsplit, ws.prec);
+    else if (MI == 2) launch_tile<LA, LB, 2, 1, 2, 2>(s, a, b, ep, M, N, nprob, nsplit, ws);
+    else if (NI == 2) launch_tile<LA, LB, 1, 2, 2, 2>(s, a, b, ep, M, N, nprob, nsplit, ws);
+    else launch_tile<LA, LB, 1, 1, 2, 2>(s, a, b, ep, M, N, nprob, nsplit, ws);
     if (nsplit > 1) splitk_reduce(s, ep, M, N, nprob, nsplit);
 }
 

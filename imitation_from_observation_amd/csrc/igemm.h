@@ -190,10 +190,50 @@ __device__ __forceinline__ float4 bload4(rsrc_t r, uint32_t voff) {
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }
 
+// What CTX_PREC_FP16X3D needs from a loader besides its loads: a HOST-side statement of the floats the product reads through it
+// (`ranges`), so that the launch funnel (gemm_launch.h) can take the operand's largest magnitude first.  An operand has up to two
+// sources ([decoder | skip], the ...2 filter-gradient operands, KmCat2): one exponent from the maximum over both.  A range is
+//   p[i0 * s0 + i1 * s1 + c]   for i0 < n0, i1 < n1, c < cols
+// and covers more than the product reads only where the rest is written and finite: pixels of the same activation tensor that a
+// VALID or strided window skips (its producer wrote them), the zero channel of a 4-channel copy.  Filters are stated tap-exactly
+// where a launch skips taps (the position-major loaders): a parameter is written, but nobody promises it is finite.
+// `ranges(o, other)` receives the launch's other loader because some filter loaders take their geometry from the activation side.
+struct AmaxRange { const float* p; int64_t n0, s0, n1, s1, cols; };
+struct AmaxOp {
+    AmaxRange r[2];
+    int n = 0;
+    void add3(const float* p, int64_t n0, int64_t s0, int64_t n1, int64_t s1, int64_t cols) {
+        if (p && n0 > 0 && n1 > 0 && cols > 0) r[n++] = AmaxRange{p, n0, s0, n1, s1, cols};
+    }
+    void add(const float* p, int64_t rows, int64_t cols, int64_t ld) { add3(p, 1, 0, rows, ld, cols); }
+};
+
+// taps k in [lo, hi) of a K-tap axis that land inside the big grid at some of the nsmall output positions (PosGeo::range over all i)
+inline void tap_span(int s, int pad, int K, int nbig, int nsmall, int& lo, int& hi) {
+    lo = pad - s * (nsmall - 1) > 0 ? pad - s * (nsmall - 1) : 0;
+    hi = nbig + pad < K ? nbig + pad : K;
+}
+// the same for a stride-2 transposed conv over an n-position axis (TPosGeo::where over both parity classes and all positions)
+inline void ttap_span(int n, int K, int pb, int& lo, int& hi) {
+    lo = K; hi = 0;
+    for (int p = 0; p < 2; ++p) {
+        const int par = (p + pb) & 1, nt = (K - par + 1) >> 1, off = (p + pb - par) >> 1;
+        for (int i = 0; i < n; ++i) {
+            const int sy0 = i + off - n + 1 > 0 ? i + off - n + 1 : 0, sy1 = i + off + 1 < nt ? i + off + 1 : nt;
+            for (int sy = sy0; sy < sy1; ++sy) { const int k = par + 2 * sy; if (k < lo) lo = k; if (k + 1 > hi) hi = k + 1; }
+        }
+    }
+    if (hi < lo) lo = hi = 0;
+}
+
 // Plain row-major matrix V[row][k], optionally split along k into two buffers (the translate MLP's
 // concat([src_z, ctx_z]), arm_shaping.py:1310).
 struct KmPlain {
     static constexpr bool KM = true;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        const int64_t K = (int64_t)nchunks * KC, k0 = K < ksplit ? K : ksplit;
+        o.add(p0, R, k0, ld0); o.add(p1, R, K - k0, ld1);
+    }
     const float* p0; int64_t ld0;
     const float* p1; int64_t ld1;
     int ksplit;      // k < ksplit -> p0, else p1[k - ksplit]; a multiple of KC
@@ -224,6 +264,11 @@ struct KmPlain {
 // K order: 32-channel slice outer, the 25 taps inner.
 struct KmConvGather {
     static constexpr bool KM = true;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        const int64_t nimg = R / (hs * ws), C = (int64_t)cps * KC, n2 = nimg < nmod2 ? nimg : nmod2;     // every pixel of the nimg input images
+        o.add(x, nimg * hb * wb, x2 ? c1 : C, ldx);
+        if (x2) o.add(x2, n2 * hb * wb, C - c1, ldx2);
+    }
     const float* x; int64_t ldx;   // NHWC input, channel stride ldx
     int hb, wb, hs, ws;            // input (big) and output (small) grids
     int cps;                       // chunks per tap = (c1 + c2) / 32
@@ -276,6 +321,10 @@ struct KmConvGather {
 // passes, so its image index is img % nmod2 (arm_shaping.py:1323 and :1336 use the same tgtctx_h*).
 struct KmConvTGather {
     static constexpr bool KM = true;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        const int64_t nimg = R / (hs * ws), C = (int64_t)cps * KC, n2 = nimg < nmod2 ? nimg : nmod2;
+        o.add(s1, R, c1 < C ? c1 : C, ld1); o.add(s2, n2 * hs * ws, C - c1, ld2);
+    }
     const float* s1; int64_t ld1; int c1;   // c1 a multiple of KC
     const float* s2; int64_t ld2; int nmod2;
     int hs, ws;
@@ -332,6 +381,9 @@ struct KmConvTGather {
 // conv2d_transpose filter as the B operand: w[ky][kx][a][b] (a = output channel = tile row, b = k).
 struct KmConvTWeights {
     static constexpr bool KM = true;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        o.add(w, (int64_t)K * K * ca, (int64_t)cps * KC, cb);          // all K*K taps: the four parity classes, or flip25
+    }
     const float* w; int ca, cb;    // cb = c1 + c2
     int cps;
     const float* zeros;
@@ -362,6 +414,10 @@ struct KmConvTWeights {
 // channel; s2 is the ctx skip (image index img % nmod2).  Used by the d_h4 scatter product.
 struct KmCat2 {
     static constexpr bool KM = true;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        const int64_t nimg = R / hsws, C = (int64_t)cps * KC, n2 = nimg < nmod2 ? nimg : nmod2;
+        o.add(s1, R, c1 < C ? c1 : C, ld1); o.add(s2, n2 * hsws, C - c1, ld2);
+    }
     const float* s1; int64_t ld1; int c1;
     const float* s2; int64_t ld2; int nmod2;
     int hsws;        // pixels per image
@@ -390,6 +446,9 @@ struct KmCat2 {
 // 16-byte load.  K order: k = tap * 4 + ch with the 25 taps padded to 32: 4 chunks of 8 taps, tap = 8 * chunk + k4 / 4.
 struct KmC3Gather {
     static constexpr bool KM = true;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        o.add(x4, 1, (int64_t)(R / (hs * ws)) * hb * wb * 4, 0);       // the 4-channel copy, channel 3 = 0
+    }
     const float* x4;
     int hb, wb, hs, ws;
     int R;
@@ -418,6 +477,9 @@ struct KmC3Gather {
 // [25][cin][cout] read in KmConvGather's K order (slice outer, tap inner).
 struct NmPlain {
     static constexpr bool KM = false;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        o.add(p0, K, R, ld0);
+    }
     const float* p0; int64_t ld0;
     const float* p1; int64_t ld1;   // unused here (see NmPlain2)
     int rsplit;
@@ -449,6 +511,9 @@ struct NmPlain {
 // one returns zeros.
 struct NmPlain2 {
     static constexpr bool KM = false;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        o.add(p0, K, rsplit, ld0); o.add(p1, K, R - rsplit, ld1);
+    }
     const float* p0; int64_t ld0;
     const float* p1; int64_t ld1;
     int rsplit;
@@ -477,6 +542,9 @@ struct NmPlain2 {
 // cin == 3 conv filter w[5][5][3][cb] as the B operand of KmC3Gather: k = tap * 4 + ch -> filter row tap * 3 + ch (ch < 3).
 struct NmC3Weights {
     static constexpr bool KM = false;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        o.add3(w, ntap, (int64_t)cs * cb, 3, cb, cb);                  // rows tap * cs + ch, ch < 3
+    }
     const float* w; int cb;
     const float* zeros;
     int ntap = 25, cs = 3;         // cs = filter rows per tap (32 where the blob keeps cin padded: the CNN executor's stem)
@@ -495,6 +563,9 @@ struct NmC3Weights {
 // pixel shifted by tap prob = ky*5+kx:  dw[ky,kx,a,b] = sum big[img,2i+ky-1,2j+kx-1,a] * small[img,i,j,b].
 struct NmWgradBig {
     static constexpr bool KM = false;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        o.add(big, (int64_t)(npix / (pd.hs * pd.ws)) * hb * wb, ca, ldb);
+    }
     const float* big; int64_t ldb; int ca;
     int hb, wb;
     PixDiv pd;
@@ -523,6 +594,9 @@ struct NmWgradBig {
 // Filter-gradient operand, small side, single tensor: k = pixel, rows = channels.
 struct NmWgradSmall {
     static constexpr bool KM = false;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        o.add(s1, npix, cb, ld1);
+    }
     const float* s1; int64_t ld1; int c1;
     const float* s2; int64_t ld2; int nmod2;      // unused here (see NmWgradSmall2)
     int cb;
@@ -544,6 +618,10 @@ struct NmWgradSmall {
 // img % nmod2 (img < 2 * nmod2: the two decoder passes).  Both loads are issued; a lane's other one is OOB.
 struct NmWgradSmall2 {
     static constexpr bool KM = false;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        const int64_t wrap = (int64_t)nmod2 * hsws;
+        o.add(s1, npix, c1, ld1); o.add(s2, npix < wrap ? npix : wrap, cb - c1, ld2);
+    }
     const float* s1; int64_t ld1; int c1;
     const float* s2; int64_t ld2; int nmod2;
     int cb;          // c1 + c2
@@ -594,6 +672,9 @@ inline PatchGeo make_patch(int nimg, int hs, int ws) {
 
 struct NmWgradBigP {
     static constexpr bool KM = false;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        o.add(big, (int64_t)2 * g.rows_total * wb, ca, ldb);           // hb = 2 hs: 2 rows_total stacked rows of wb pixels
+    }
     const float* big; int64_t ldb; int ca;
     int wb;
     PatchGeo g;
@@ -623,6 +704,9 @@ struct NmWgradBigP {
 
 struct NmWgradSmallP {
     static constexpr bool KM = false;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        o.add(s1, (int64_t)g.rows_total * g.ws, cb, ld1);
+    }
     const float* s1; int64_t ld1; int cb;
     PatchGeo g;
     const float* zeros;
@@ -643,6 +727,10 @@ struct NmWgradSmallP {
 
 struct NmWgradSmall2P {
     static constexpr bool KM = false;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        const int64_t wrap = (int64_t)nmod2 * g.hs, rows2 = g.rows_total < wrap ? g.rows_total : wrap;
+        o.add(s1, (int64_t)g.rows_total * g.ws, c1, ld1); o.add(s2, rows2 * g.ws, cb - c1, ld2);
+    }
     const float* s1; int64_t ld1; int c1;
     const float* s2; int64_t ld2; int nmod2;     // s2 = ctx skip, stacked rows wrap at nmod2 * hs
     int cb;
@@ -724,6 +812,9 @@ inline RectGeo make_rect(int nimg, int hs, int ws, int hb, int wb, int s, int pa
 
 struct NmWgradBigR {
     static constexpr bool KM = false;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        o.add(big, (int64_t)g.nimg * g.hb * g.wb, ca, ldb);
+    }
     const float* big; int64_t ldb; int ca;
     RectGeo g;
     const float* zeros;
@@ -741,6 +832,9 @@ struct NmWgradBigR {
 
 struct NmWgradSmallR {
     static constexpr bool KM = false;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        o.add(s1, (int64_t)g.nimg * g.hs * g.ws, cb, ld1);
+    }
     const float* s1; int64_t ld1; int cb;
     RectGeo g;
     const float* zeros;
@@ -758,6 +852,10 @@ struct NmWgradSmallR {
 // small side = channels of [s1 | s2]; s2 is the ctx skip shared by both decoder passes (image n % nmod2, nmod2 % 32 == 0)
 struct NmWgradSmall2R {
     static constexpr bool KM = false;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        const int64_t n2 = g.nimg < nmod2 ? g.nimg : nmod2;
+        o.add(s1, (int64_t)g.nimg * g.hs * g.ws, c1, ld1); o.add(s2, n2 * g.hs * g.ws, cb - c1, ld2);
+    }
     const float* s1; int64_t ld1; int c1;
     const float* s2; int64_t ld2; int nmod2;
     int cb;
@@ -785,6 +883,9 @@ struct NmWgradSmall2R {
 // used), k = output-grid pixel; a lane's float4 is the 4 channels of ONE tap at one pixel.
 struct NmC3WgradBig {
     static constexpr bool KM = false;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        o.add(big4, 1, (int64_t)(npix / (pd.hs * pd.ws)) * hb * wb * 4, 0);
+    }
     const float* big4;
     int hb, wb;
     PixDiv pd;
@@ -888,6 +989,9 @@ inline int posgeo_min_chunks(const PosGeo& g) {                  // the corner p
 // conv2d operand: problem = output position (i,j), row = image.  Epilogue rowmode 4.
 struct KmConvGatherQ {
     static constexpr bool KM = true;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        o.add(x, (int64_t)nimg * g.hb * g.wb, (int64_t)g.cps * KC, ldx);
+    }
     const float* x; int64_t ldx;
     PosGeo g;
     int nimg;
@@ -912,6 +1016,13 @@ struct KmConvGatherQ {
 // its filter [K][K][cin][cout] as the B operand (rows = cout)
 struct NmConvWeightsQ {
     static constexpr bool KM = false;
+    template <class O> void ranges(AmaxOp& o, const O& a) const {
+        // only the taps that land inside the grid at SOME position are read (on a 1x1 grid: 1 of K*K)
+        int y0, y1, x0, x1;
+        tap_span(a.g.s, a.g.pad, a.g.K, a.g.hb, a.g.hs, y0, y1); tap_span(a.g.s, a.g.px(), a.g.kw(), a.g.wb, a.g.ws, x0, x1);
+        const int64_t tap = (int64_t)cin * cout;
+        o.add3(w + (y0 * K + x0) * tap, y1 - y0, K * tap, x1 - x0, tap, (int64_t)a.g.cps * KC * cout);
+    }
     const float* w; int cin, cout, K;     // K = kernel WIDTH (row index = ky * K + kx)
     const float* zeros;
     struct Pos { rsrc_t rs; };
@@ -963,6 +1074,10 @@ inline TPosGeo make_tposgeo(int hs, int ws, int K, int pb, int cps) {
 }
 struct KmConvTGatherQ {
     static constexpr bool KM = true;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        const int64_t hw = (int64_t)g.hs * g.ws, C = (int64_t)g.cps * KC, n2 = nimg < nmod2 ? nimg : nmod2;
+        o.add(s1, nimg * hw, c1 < C ? c1 : C, ld1); o.add(s2, n2 * hw, C - c1, ld2);
+    }
     const float* s1; int64_t ld1; int c1;   // c1 a multiple of KC
     const float* s2; int64_t ld2; int nmod2;
     TPosGeo g;
@@ -992,6 +1107,12 @@ struct KmConvTGatherQ {
 // its filter w[ky][kx][a][b] (a = output channel = tile row, b = k) as the B operand
 struct KmConvTWeightsQ {
     static constexpr bool KM = true;
+    template <class O> void ranges(AmaxOp& o, const O& a) const {
+        int y0, y1, x0, x1;                                            // the taps some (class, position) reaches
+        ttap_span(a.g.hs, K, a.g.pb, y0, y1); ttap_span(a.g.ws, K, a.g.pb, x0, x1);
+        const int64_t tap = (int64_t)ca * cb;
+        o.add3(w + (y0 * K + x0) * tap, y1 - y0, K * tap, x1 - x0, tap, tap);
+    }
     const float* w; int ca, cb, K;
     const float* zeros;
     struct Pos { rsrc_t rs; };
@@ -1010,6 +1131,10 @@ struct KmConvTWeightsQ {
 // Two sources as in KmConvTGatherQ (the decoder's concat([d, skip]), the skip indexed by image % nmod2).  Epilogue rowmode 4.
 struct KmConvT1GatherQ {
     static constexpr bool KM = true;
+    template <class O> void ranges(AmaxOp& o, const O&) const {
+        const int64_t hw = (int64_t)g.hb * g.wb, C = (int64_t)g.cps * KC, n2 = nimg < nmod2 ? nimg : nmod2;
+        o.add(s1, nimg * hw, c1 < C ? c1 : C, ld1); o.add(s2, n2 * hw, C - c1, ld2);
+    }
     const float* s1; int64_t ld1; int c1;   // c1 a multiple of KC
     const float* s2; int64_t ld2; int nmod2;
     PosGeo g;                               // make_posgeo(hs, ws, hs, ws, 1, K - 1 - pad, K, cps)
@@ -1040,6 +1165,12 @@ struct KmConvT1GatherQ {
 // its filter w[ky][kx][a][b] (a = output channel = tile row, b = k) as the B operand
 struct KmConvT1WeightsQ {
     static constexpr bool KM = true;
+    template <class O> void ranges(AmaxOp& o, const O& a) const {
+        int y0, y1, x0, x1;                                            // mirrored taps ky' in [y0, y1) -> filter rows K-y1 .. K-1-y0
+        tap_span(1, a.g.pad, K, a.g.hb, a.g.hs, y0, y1); tap_span(1, a.g.pad, K, a.g.wb, a.g.ws, x0, x1);
+        const int64_t tap = (int64_t)ca * cb;
+        o.add3(w + ((K - y1) * K + (K - x1)) * tap, y1 - y0, K * tap, x1 - x0, tap, tap);
+    }
     const float* w; int ca, cb, K;
     const float* zeros;
     struct Pos { rsrc_t rs; };

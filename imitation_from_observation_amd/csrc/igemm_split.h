@@ -15,6 +15,14 @@
 //   terms above fp16's subnormals; |x| 2^CTX_FP16_EXP >= 65520 rounds hi to +-inf (a non-finite product, never a
 //   wrong finite one), and below |x| ~ 1e-3 the lo term runs into the absolute floor 2^-24 / 2^CTX_FP16_EXP
 //   (include/ctxtrans.h states the range contract; profiles/round6_e_fp16_split_errors.txt, profiles/precision_modes.txt).
+//   SPLIT_FP16D (CTX_PREC_FP16X3D):
+//     y = x * 2^e,   e = 14 - (exponent of the operand's largest |x|), one e per operand and launch, taken ON THE DEVICE by
+//   split_absmax (kernels.hip) right in front of the product; the kernel reads {2^e_a, 2^e_b, f1, f2} from device memory (`dyn`,
+//   launch.h: SplitSlot), so a captured graph follows the data at every replay.  The largest entry of either operand lands in
+//   [2^14, 2^15): no window to audit.  The accumulators are rescaled as (acc * f1) * f2 with {f1, f2} = {2^-e_a, 2^-e_b}, the
+//   smaller factor first: each multiply is exact, and the intermediate cannot overflow where the result does not.  An inf / NaN
+//   entry makes its operand's scale NaN: a non-finite product, never a wrong finite one.  Everything else -- LDS image, thread
+//   maps, gap schedule, split-K (partials are written after the rescale, at true magnitude), epilogue -- is SPLIT_FP16's.
 // The default stays exact f32.
 //
 // HBM holds f32 everywhere; only the LDS image changes.  Both operand kinds (KM: k-contiguous loads, NM:
@@ -39,17 +47,23 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-enum SplitFmt { SPLIT_BF16 = 1, SPLIT_FP16 = 2 };      // = CTX_PREC_BF16X3 / CTX_PREC_FP16X3 (SplitWs::prec)
+enum SplitFmt { SPLIT_BF16 = 1, SPLIT_FP16 = 2, SPLIT_FP16D = 3 };      // = CTX_PREC_BF16X3 / CTX_PREC_FP16X3 / CTX_PREC_FP16X3D (SplitWs::prec)
 constexpr int CTX_FP16_EXP = 6;                        // SPLIT_FP16: operands are split as x * 2^6 (one constant, not a knob)
 
-// (x0, x1) -> packed 16-bit pairs hi, lo  (element 0 in the low half)
+// (x0, x1) -> packed 16-bit pairs hi, lo  (element 0 in the low half); dsc = the operand's run-time scale (SPLIT_FP16D only)
 template <int FMT>
-__device__ __forceinline__ void split2(float x0, float x1, uint32_t& hi, uint32_t& lo) {
+__device__ __forceinline__ void split2(float x0, float x1, uint32_t& hi, uint32_t& lo, float dsc = 0.f) {
 #ifdef CTX_ABL_SPLIT_NOCVT      // timing ablation only (WRONG numbers): the staging cost of operands that arrive pre-split -- same bytes, no conversion
     hi = __float_as_uint(x0); lo = __float_as_uint(x1);
     return;
 #endif
-    if constexpr (FMT == SPLIT_FP16) {
+    if constexpr (FMT == SPLIT_FP16D) {
+        const f32x2 v = {x0 * dsc, x1 * dsc};
+        const f16x2 hv = __builtin_convertvector(v, f16x2);
+        hi = __builtin_bit_cast(uint32_t, hv);
+        const f32x2 r = {v.x - (float)hv.x, v.y - (float)hv.y};
+        lo = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, f16x2));
+    } else if constexpr (FMT == SPLIT_FP16) {
         const float sc = (float)(1 << CTX_FP16_EXP);
         const f32x2 v = {x0 * sc, x1 * sc};
         const f16x2 hv = __builtin_convertvector(v, f16x2);
@@ -83,18 +97,18 @@ struct STile {
     __device__ static int nm_kk(int tid, int p) { return (tid % G) * NPASS + p; }
     __device__ static int nm_r4(int tid) { return (tid / G) * 4; }
     // store step j (0 .. NPASS-1) of this thread's NPASS float4
-    __device__ static void store(uint32_t* s, int tid, int j, const float4* v) {
+    __device__ static void store(uint32_t* s, int tid, int j, const float4* v, float dsc = 0.f) {
         if (KMF) {
             uint32_t h0, l0, h1, l1;
-            split2<FMT>(v[j].x, v[j].y, h0, l0);
-            split2<FMT>(v[j].z, v[j].w, h1, l1);
+            split2<FMT>(v[j].x, v[j].y, h0, l0, dsc);
+            split2<FMT>(v[j].z, v[j].w, h1, l1, dsc);
             uint32_t* d = s + km_row(tid, j) * SLDR + (tid & 7) * 2;
             *reinterpret_cast<uint2*>(d) = make_uint2(h0, h1);
             *reinterpret_cast<uint2*>(d + 16) = make_uint2(l0, l1);
         } else if (NPASS == 4) {
             uint32_t h0, l0, h1, l1;
-            split2<FMT>(comp(v[0], j), comp(v[1], j), h0, l0);
-            split2<FMT>(comp(v[2], j), comp(v[3], j), h1, l1);
+            split2<FMT>(comp(v[0], j), comp(v[1], j), h0, l0, dsc);
+            split2<FMT>(comp(v[2], j), comp(v[3], j), h1, l1, dsc);
             uint32_t* d = s + (nm_r4(tid) + j) * SLDR + (tid % G) * 2;
             *reinterpret_cast<uint2*>(d) = make_uint2(h0, h1);
             *reinterpret_cast<uint2*>(d + 16) = make_uint2(l0, l1);
@@ -103,7 +117,7 @@ struct STile {
             for (int u = 0; u < 2; ++u) {
                 const int i = 2 * j + u;
                 uint32_t h0, l0;
-                split2<FMT>(comp(v[0], i), comp(v[1], i), h0, l0);
+                split2<FMT>(comp(v[0], i), comp(v[1], i), h0, l0, dsc);
                 uint32_t* d = s + (nm_r4(tid) + i) * SLDR + (tid % G);
                 d[0] = h0;
                 d[16] = l0;
@@ -134,7 +148,7 @@ struct SFetch {
 
 template <int FMT>
 __device__ __forceinline__ f32x16 mfma_split(const u32x4& a, const u32x4& b, const f32x16& c) {
-    if constexpr (FMT == SPLIT_FP16)
+    if constexpr (FMT == SPLIT_FP16 || FMT == SPLIT_FP16D)
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
     else
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
@@ -142,7 +156,7 @@ __device__ __forceinline__ f32x16 mfma_split(const u32x4& a, const u32x4& b, con
 
 template <int FMT, class LA, class LB, int MI, int NI, int WM, int WN>
 __global__ __launch_bounds__(64 * WM * WN) void igemm_split_kernel(const LA la, const LB lb, const Epi ep, int M, int N,
-                                                                   int nprob, int nsplit, int gm, int gn) {
+                                                                   int nprob, int nsplit, int gm, int gn, const float* dyn) {
     constexpr int NT = 64 * WM * WN;
     constexpr int TM = 32 * MI * WM, TN = 32 * NI * WN;
     using TA = STile<LA::KM, TM, NT, FMT>;
@@ -156,6 +170,8 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm_split_kernel(const LA la, 
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int wm = wv / WN, wn = wv % WN, l31 = lane & 31, h = lane >> 5;
+    float dsa = 0.f, dsb = 0.f;                         // SPLIT_FP16D: this launch's operand scales 2^e_a, 2^e_b (wave-uniform loads)
+    if constexpr (FMT == SPLIT_FP16D) { dsa = dyn[0]; dsb = dyn[1]; }
 
     int rest = blockIdx.x;
     if (ep.xcd_swizzle) {                               // workgroups are dealt round-robin to the 8 XCDs: give each XCD a contiguous run of work
@@ -210,9 +226,9 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm_split_kernel(const LA la, 
             for (int p = 0; p < NB; ++p) xb[p] = fb.load1(lb, qb, p);
         }
 #pragma unroll
-        for (int p = 0; p < NA; ++p) TA::store(smem_u, tid, p, xa);
+        for (int p = 0; p < NA; ++p) TA::store(smem_u, tid, p, xa, dsa);
 #pragma unroll
-        for (int p = 0; p < NB; ++p) TB::store(smem_u + TA::FLOATS, tid, p, xb);
+        for (int p = 0; p < NB; ++p) TB::store(smem_u + TA::FLOATS, tid, p, xb, dsb);
         {
             typename LA::Pos qa;
             typename LB::Pos qb;
@@ -261,8 +277,8 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm_split_kernel(const LA la, 
                         else lb_[ld - NA] = fb.load1(lb, qb, ld - NA);
                     }
                     if (st_ < NLS) {
-                        if (st_ < NA) TA::store(nA, tid, st_, sa_);
-                        else TB::store(nB, tid, st_ - NA, sb_);
+                        if (st_ < NA) TA::store(nA, tid, st_, sa_, dsa);
+                        else TB::store(nB, tid, st_ - NA, sb_, dsb);
                     }
                 }
             }
@@ -280,6 +296,15 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm_split_kernel(const LA la, 
         }
     }
 
+    if constexpr (FMT == SPLIT_FP16D) {                 // the operands were x * 2^e_a, x * 2^e_b: two exact power-of-two rescales, the smaller first
+        const float f1 = dyn[2], f2 = dyn[3];
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[mi][ni][r] = (acc[mi][ni][r] * f1) * f2;
+    }
     if constexpr (FMT == SPLIT_FP16) {                  // the operands were x * 2^CTX_FP16_EXP: an exact power-of-two rescale
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)

@@ -268,6 +268,128 @@ void splitk_reduce(hipStream_t s, const Epi& ep, int M, int N, int nprob, int ns
 }
 
 // ------------------------------------------------------------------------------------------------
+// CTX_PREC_FP16X3D: the per-operand scales of one split launch (launch.h: SplitSlot; igemm_split.h: SPLIT_FP16D).
+// One launch for both operands: every block reduces max(bits & 0x7fffffff) over its share of the stated ranges -- as UNSIGNED
+// integers, so inf / NaN win by construction and the result depends neither on the order nor on the grid --, leaves its two maxima
+// in the slot's `part` and draws a ticket (ONE integer atomic per block: with an atomicMax per operand on top, the 2048 blocks of
+// the first version queued 6144 same-address atomics and a launch took 100 us whatever it read).  The block that draws the last
+// ticket reduces `part`, writes the scales and leaves the ticket at zero for the slot's next use: no clearing launch, no host round
+// trip, replayable in a captured graph.
+//   e = 14 - (exponent field of absmax - 127), clamped to [-126, 126] so that 2^e and 2^-e are normal: the largest entry lands in
+//   [2^14, 2^15) (fp16 tops out at 65504); the clamp only binds for absmax < 2^-112, where e stays 126.  absmax == 0: e = 0.
+//   A non-finite absmax makes all four factors NaN.
+// HBM-bound: one extra read of each operand, float4 loads where the range allows.
+// ------------------------------------------------------------------------------------------------
+struct AmaxArgs {
+    AmaxRange r[4];
+    uint32_t cw[4];         // units per innermost run: cols / 4 (vec) or cols
+    uint8_t op[4], vec[4];  // operand (0 = A, 1 = B) / float4 loads
+    int n;
+};
+
+__global__ __launch_bounds__(NTHREADS) void split_absmax_kernel(const AmaxArgs A, SplitSlot* slot) {
+    constexpr uint32_t ABS = 0x7fffffffu;
+    uint32_t m0 = 0, m1 = 0;
+    const int64_t gt = (int64_t)blockIdx.x * NTHREADS + threadIdx.x, gs = (int64_t)gridDim.x * NTHREADS;
+    for (int q = 0; q < A.n; ++q) {
+        const AmaxRange r = A.r[q];
+        const uint32_t cw = A.cw[q], n1 = (uint32_t)r.n1;
+        const bool flat = r.n0 * r.n1 == 1;
+        const int64_t total = r.n0 * r.n1 * (int64_t)cw;           // < 2^32 (checked by the launcher)
+        const int w = A.vec[q] ? 4 : 1;
+        uint32_t m = 0;
+        auto offset = [&](int64_t i) {
+            if (flat) return i * w;
+            const uint32_t u = (uint32_t)i, t = u / cw, c = u - t * cw, i0 = t / n1, i1 = t - i0 * n1;
+            return (int64_t)i0 * r.s0 + (int64_t)i1 * r.s1 + (int64_t)c * w;
+        };
+        if (A.vec[q]) {
+#pragma unroll 8
+            for (int64_t i = gt; i < total; i += gs) {
+                const float4 v = ldg4(r.p + offset(i));
+                const uint32_t a = max(__float_as_uint(v.x) & ABS, __float_as_uint(v.y) & ABS), b = max(__float_as_uint(v.z) & ABS, __float_as_uint(v.w) & ABS);
+                m = max(m, max(a, b));
+            }
+        } else {
+            for (int64_t i = gt; i < total; i += gs) m = max(m, __float_as_uint(r.p[offset(i)]) & ABS);
+        }
+        if (A.op[q]) m1 = max(m1, m); else m0 = max(m0, m);
+    }
+    __shared__ uint32_t red[2][NTHREADS / 64];
+    __shared__ bool last;
+    auto block_max = [&]() {                                       // -> m0, m1 of thread 0
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            m0 = max(m0, (uint32_t)__shfl_xor((int)m0, o));
+            m1 = max(m1, (uint32_t)__shfl_xor((int)m1, o));
+        }
+        if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = m0; red[1][threadIdx.x >> 6] = m1; }
+        __syncthreads();
+        for (int wv = 0; wv < NTHREADS / 64; ++wv) { m0 = max(m0, red[0][wv]); m1 = max(m1, red[1][wv]); }
+    };
+    block_max();
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(&slot->part[0][blockIdx.x], m0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&slot->part[1][blockIdx.x], m1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __threadfence();
+        last = atomicAdd(&slot->ticket, 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();                                               // last block: every other block's maxima are in
+    m0 = m1 = 0;
+    for (int b = threadIdx.x; b < (int)gridDim.x; b += NTHREADS) {
+        m0 = max(m0, __hip_atomic_load(&slot->part[0][b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        m1 = max(m1, __hip_atomic_load(&slot->part[1][b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    }
+    __syncthreads();                                               // (red is reused)
+    block_max();
+    if (threadIdx.x != 0) return;
+    const uint32_t am[2] = {m0, m1};
+    atomicExch(&slot->ticket, 0u);
+    float sc[2], inv[2];
+    bool finite = true;
+    for (int k = 0; k < 2; ++k) {
+        const int E = (int)(am[k] >> 23);
+        int e = am[k] ? 14 - (E - 127) : 0;
+        e = e > 126 ? 126 : e < -126 ? -126 : e;
+        finite = finite && E != 255;
+        sc[k] = __uint_as_float((uint32_t)(127 + e) << 23);
+        inv[k] = __uint_as_float((uint32_t)(127 - e) << 23);
+    }
+    const float nan = __uint_as_float(0x7fc00000u);
+    slot->scale[0] = finite ? sc[0] : nan;
+    slot->scale[1] = finite ? sc[1] : nan;
+    slot->scale[2] = finite ? fminf(inv[0], inv[1]) : nan;         // the smaller factor first: (acc * f1) * f2 cannot overflow on the way
+    slot->scale[3] = finite ? fmaxf(inv[0], inv[1]) : nan;
+}
+
+void split_absmax(hipStream_t s, const AmaxOp& a, const AmaxOp& b, SplitSlot* slot) {
+    AmaxArgs A{};
+    int64_t work = 0;
+    auto al = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+    for (int k = 0; k < 2; ++k) {
+        const AmaxOp& o = k ? b : a;
+        for (int j = 0; j < o.n; ++j) {
+            AmaxRange r = o.r[j];
+            if (r.n1 == 1 || r.s1 == r.cols) { r.cols *= r.n1; r.n1 = 1; r.s1 = 0; }                       // contiguous runs collapse
+            if (r.n1 == 1 && (r.n0 == 1 || r.s0 == r.cols)) { r.cols *= r.n0; r.n0 = 1; r.s0 = 0; }
+            const bool vec = al(r.p) && r.cols % 4 == 0 && (r.n0 == 1 || r.s0 % 4 == 0) && (r.n1 == 1 || r.s1 % 4 == 0);
+            const int64_t cw = vec ? r.cols / 4 : r.cols, units = r.n0 * r.n1 * cw;
+            if (units >= (1ll << 32)) { set_launch_error("split_absmax: a range of %lld units", (long long)units); return; }
+            A.r[A.n] = r; A.cw[A.n] = (uint32_t)cw; A.op[A.n] = (uint8_t)k; A.vec[A.n] = vec;
+            ++A.n;
+            work += units;
+        }
+    }
+    // (an operand without a range -- nothing the product reads -- keeps absmax 0: scale 1)
+    int64_t blocks = (work + 8 * NTHREADS - 1) / (8 * NTHREADS);
+    const int64_t cap = std::min<int64_t>(2ll * dev_info().cus, SPLIT_ABSMAX_BLOCKS);
+    blocks = blocks < 1 ? 1 : blocks > cap ? cap : blocks;
+    hipLaunchKernelGGL(split_absmax_kernel, dim3((unsigned)blocks), dim3(NTHREADS), 0, s, A, slot);
+}
+
+// ------------------------------------------------------------------------------------------------
 // conv2d_transpose 5x5 s2 to 3 output channels (d_h4, arm_shaping.py:1329-1330, :1342-1343), step 2:
 //   out[n, y, x, c] = b[c] + sum over taps with y = 2i+ky-1, x = 2j+kx-1 of P[(n,i,j)][(ky*5+kx)*3+c]
 // One thread per output pixel; taps are added in a fixed order.  HBM/L2-bound: 4-9 x 12 B gathers.

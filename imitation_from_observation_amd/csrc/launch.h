@@ -43,13 +43,38 @@ const uint16_t* morton_order(int gh, int gw, hipStream_t stream);      // Z-orde
 // Default 9.
 int balance_bits();
 
+// CTX_PREC_FP16X3D: the per-operand scales of one split launch live in a device SLOT.  Every block of split_absmax (kernels.hip) leaves
+// the largest |x| bit pattern it saw of either operand in `part` and draws a `ticket`; the block that draws the last one reduces `part`,
+// writes the scales the product kernel reads and puts the ticket back to zero -- so a slot needs no clearing launch and a captured
+// graph may replay it.  Slots are zeroed once where they are allocated (also under CTX_DEBUG_POISON).
+constexpr int SPLIT_ABSMAX_BLOCKS = 512;    // largest grid of split_absmax (two blocks per CU on MI355X)
+struct SplitSlot {
+    float scale[4];         // {2^e_a, 2^e_b, f1, f2}: operands are split as x * 2^e; the accumulators are rescaled as (acc * f1) * f2,
+                            // {f1, f2} = {2^-e_a, 2^-e_b} with the smaller factor first (igemm_split.h)
+    uint32_t ticket;        // blocks of the running split_absmax launch that have finished
+    uint32_t pad[3];
+    uint32_t part[2][SPLIT_ABSMAX_BLOCKS];   // per block: max of (bits & 0x7fffffff) over its share of operand A / B
+};
+constexpr int SPLIT_RING = 4;
+// One ring per stream lane (it travels with the lane's split-K slab): a slot is written by a split_absmax launch and read by the
+// product launch enqueued right behind it on the same stream (or graph branch); the next launch of the lane takes the next slot.
+struct SplitSlots {
+    SplitSlot* dev = nullptr;   // SPLIT_RING slots
+    int cursor = 0;
+    SplitSlot* next() { SplitSlot* p = dev + cursor; cursor = (cursor + 1) % SPLIT_RING; return p; }
+};
+
 // Split-K policy shared by all launchers: `slab` is scratch of `slab_floats` floats.
 struct SplitWs {
     float* slab;
     int64_t slab_floats;
-    int prec = 0;   // CTX_PREC_*: 0 exact-f32 MFMA, 1 split-bf16, 2 split-fp16 (igemm_split.h); every heuristic reads nonzero as "split mode"
+    int prec = 0;   // CTX_PREC_*: 0 exact-f32 MFMA, 1 split-bf16, 2 split-fp16, 3 split-fp16 with per-operand scales (igemm_split.h); every heuristic reads nonzero as "split mode"
     int swz = 0;    // XCD-swizzle bits the caller allows (gemm_conv.hip: xcd_swz()); measured to pay only on ContextSkipNew's launches
+    SplitSlots* slots = nullptr;   // prec 3 only: this lane's slot ring
 };
+
+// slot->scale from the largest magnitude of each operand (one launch for both, no host synchronisation, capturable)
+void split_absmax(hipStream_t s, const AmaxOp& a, const AmaxOp& b, SplitSlot* slot);
 
 // Each launcher computes D = A*B through igemm_kernel with the given loader pair; nprob problems
 // share M, N (transposed-conv parity classes, filter-gradient taps).  min_chunks = smallest K-chunk

@@ -36,7 +36,7 @@ class HipEngine:
     torch.distributed are stream-ordered with them."""
 
     def __init__(self, H, W, df_dim, featsize, max_batch, device, seed, precision=None):
-        """precision: "f32" | "bf16x3" | "fp16x3" (Translator.__init__); None = the translator's default."""
+        """precision: "f32" | "bf16x3" | "fp16x3" | "fp16x3d" (Translator.__init__); None = the translator's default."""
         self.dev = torch.device("cuda", device)
         n = Translator.arena_floats(H, W, df_dim, featsize)
         self.arena = torch.zeros(n, device=self.dev, dtype=torch.float32)
@@ -160,7 +160,7 @@ class RcclTrainer:
 
     def __init__(self, H=64, W=64, df_dim=64, featsize=1024, max_batch=256, device=0, seed=1234, rank=None, world=None,
                  unique_id=None, precision=None):
-        """precision: "f32" | "bf16x3" | "fp16x3" (Translator.__init__); None = the translator's default."""
+        """precision: "f32" | "bf16x3" | "fp16x3" | "fp16x3d" (Translator.__init__); None = the translator's default."""
         if rank is None:
             rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
         if world is None:

@@ -264,7 +264,7 @@ class InceptionFrontend:
     final: the last end point computed (ENDPOINTS; 'PreLogits' / 'Logits' append the classifier head)."""
 
     def __init__(self, H=125, W=125, max_images=75, device=0, precision="f32", stream=None, merge_heads=None, final="Mixed_7c"):
-        """precision: "f32" | "bf16x3" | "fp16x3", the arithmetic of the convolutions (Translator.__init__ states each mode's error and
+        """precision: "f32" | "bf16x3" | "fp16x3" | "fp16x3d", the arithmetic of the convolutions (Translator.__init__ states each mode's error and
         range; the 3-channel stem and the direct kernels stay exact f32 in every mode)."""
         self._lib = _lib.load()
         self.H, self.W, self.device = H, W, device

@@ -23,7 +23,7 @@ from .translator import Translator
 class InceptionTranslator:
     def __init__(self, imsize=(125, 125), max_batch=25, device=0, precision=None, df_dim=64, featsize=1024, stream=None,
                  strides=None, kernels=None, filters=None, train=True):
-        """precision: "f32" | "bf16x3" | "fp16x3" for BOTH handles (Translator.__init__); None = f32 front end, the translator's default."""
+        """precision: "f32" | "bf16x3" | "fp16x3" | "fp16x3d" for BOTH handles (Translator.__init__); None = f32 front end, the translator's default."""
         # the front end sees src + ctx (+ tgt when training) frames of one batch in a single pass: 3 * max_batch images for the
         # trainer, 2 * max_batch for the reward hook (train=False: translate = B + B, encode = B), which sizes every activation buffer
         self.train = bool(train)

@@ -99,7 +99,7 @@ class TranslatorReward:
         experiment name -- ContextAEReal for 'real'/'sweep', ContextSkipNew otherwise (:134-137) -- on the
         sampler's imsize, restored from `modelname` when given (:138).  mode 'oursinception' (:121-132): frames go
         through the frozen Inception-v3 (variables from `inception_ckpt`, an .npz keyed by the TF names) and
-        ContextAEInception2 runs on the Mixed_7c feature maps.  precision: "f32" | "bf16x3" | "fp16x3" for the Translator /
+        ContextAEInception2 runs on the Mixed_7c feature maps.  precision: "f32" | "bf16x3" | "fp16x3" | "fp16x3d" for the Translator /
         InceptionTranslator built here (Translator.__init__ states each mode's error and range); None = their default."""
         from .translator import Translator
         if mode == "oursinception":

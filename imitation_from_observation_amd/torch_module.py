@@ -91,7 +91,7 @@ class _TranslatorFn(torch.autograd.Function):
 
 class TranslatorModule(torch.nn.Module):
     def __init__(self, H=64, W=64, df_dim=64, featsize=1024, max_batch=256, device=0, seed=0, **translator_kw):
-        """translator_kw: Translator's variant / precision ("f32" | "bf16x3" | "fp16x3") / C / strides / kernels / filters / keep_prob / ablation_type."""
+        """translator_kw: Translator's variant / precision ("f32" | "bf16x3" | "fp16x3" | "fp16x3d") / C / strides / kernels / filters / keep_prob / ablation_type."""
         super().__init__()
         self.device = torch.device("cuda", device)
         kw = {k: translator_kw[k] for k in ("variant", "C", "strides", "kernels", "filters") if k in translator_kw}

@@ -104,7 +104,7 @@ class ModelTrainer:
                  precision=None, log=print, rank=0, world=1, dp_unique_id=None, videos=None, device_resize=False):
         """The reference's 14 positional arguments (train_script.py:29-30; the launchers omit the last five, SURVEY.md 3.4-b,
         hence the defaults), then: vdata (array or .npy path of the demo tensor), basedir (logger._snapshot_dir), device,
-        seed of the parameter initialiser, an optional ready-made translator (tests), the arithmetic (precision: "f32" | "bf16x3" | "fp16x3",
+        seed of the parameter initialiser, an optional ready-made translator (tests), the arithmetic (precision: "f32" | "bf16x3" | "fp16x3" | "fp16x3d",
         Translator.__init__; None = its default), the log sink.
         rank / world: one trainer per GPU process (module docstring); `batch_size` stays the GLOBAL batch (a multiple of world).
         dp_unique_id: the 128-byte blob of Translator.dp_unique_id() made on rank 0 and shipped to every rank by the launcher (omitted:

@@ -87,7 +87,8 @@ class Translator:
     """
 
     VARIANTS = {"skipnew": _lib.CTX_VARIANT_SKIPNEW, "real": _lib.CTX_VARIANT_REAL, "inception2": _lib.CTX_VARIANT_INCEPTION2}
-    PRECISIONS = {"f32": _lib.CTX_PREC_F32, "bf16x3": _lib.CTX_PREC_BF16X3, "fp16x3": _lib.CTX_PREC_FP16X3}
+    PRECISIONS = {"f32": _lib.CTX_PREC_F32, "bf16x3": _lib.CTX_PREC_BF16X3, "fp16x3": _lib.CTX_PREC_FP16X3,
+                  "fp16x3d": _lib.CTX_PREC_FP16X3D}
 
     def __init__(self, H=64, W=64, df_dim=64, featsize=1024, max_batch=256, device=0, stream=None, arena_ptr=None,
                  variant="skipnew", precision=None, C=3, strides=None, kernels=None, filters=None, keep_prob=None, ablation_type="None"):
@@ -107,8 +108,13 @@ class Translator:
                     about the speed of "bf16x3" -- for operand magnitudes (activations, weights, gradients) from about 1e-3 up to
                     1023.  Smaller operands degrade gradually (absolute floor per operand ~2^-24 / 64: relative 3e-6 at 1e-4,
                     3e-4 at 1e-6).  An operand with |x| * 64 >= 65520 becomes +-inf: that call's scalars / features come back
-                    non-finite, never as a wrong finite number."""
-        precision = precision or os.environ.get("CTX_PRECISION", "f32")     # "f32" (exact) | "bf16x3" | "fp16x3" (split products)
+                    non-finite, never as a wrong finite number.
+          "fp16x3d" the three fp16 products of "fp16x3" with a power-of-two scale per operand of each product, taken on the device
+                    from that operand's largest magnitude (one extra read of the operands and one small launch per product): level
+                    with "f32" for operands of ANY finite magnitude -- no window to audit.  An all-zero operand gives an exactly
+                    zero product; an inf / NaN operand makes that call's scalars / features non-finite, never a wrong finite
+                    number (include/ctxtrans.h: range contract)."""
+        precision = precision or os.environ.get("CTX_PRECISION", "f32")     # "f32" (exact) | "bf16x3" | "fp16x3" | "fp16x3d" (split products)
         self._lib = _lib.load()
         self.variant, self.precision = variant, precision
         self.cfg = self.make_config(variant, H, W, C, df_dim, featsize, max_batch, precision, strides, kernels, filters, keep_prob, ablation_type)

@@ -91,9 +91,26 @@ enum {
  *                      large  an operand with |x| * 64 >= 65520 (|x| >= 1023.75) becomes +-inf in its hi term: the
  *                             product is non-finite and the inf / NaN reaches the scalars or features of that
  *                             call.  A large operand never yields a wrong finite number.
- *                    The scale 2^6 is fixed (no dynamic or per-operand scaling).
- * An addition to the enum only: CTX_ABI_VERSION and the ctx_config layout are those of ABI 4. */
-enum { CTX_PREC_F32 = 0, CTX_PREC_BF16X3 = 1, CTX_PREC_FP16X3 = 2 };
+ *                    The scale 2^6 is fixed (CTX_PREC_FP16X3D is the form with per-operand scales).
+ *   CTX_PREC_FP16X3D the three fp16 terms of CTX_PREC_FP16X3 with a power-of-two scale PER OPERAND of each product launch:
+ *                    x * 2^e with e = 14 - floor(log2(largest |x| of that operand)), taken on the device in front of
+ *                    the product (one extra read of both operands, one small launch; no host synchronisation, and a
+ *                    replayed graph follows the data); the accumulators are rescaled by 2^-e_a and 2^-e_b, each an
+ *                    exact multiply.  The largest entry of every operand lands in [2^14, 2^15).  Range contract:
+ *                      f32-grade (level with CTX_PREC_F32, 1e-6) for operands of ANY finite magnitude: there is no
+ *                             window to audit.  e is clamped to [-126, 126] so that 2^e and 2^-e are normal f32
+ *                             values; the clamp binds only below a largest magnitude of 2^-112 (1.9e-34), where e
+ *                             stays 126 and entries lose accuracy gradually as they approach the f32 subnormals.
+ *                      inside one operand, entries below 2^-25 of its largest magnitude meet the fp16 subnormal floor
+ *                             (absolute error 2^-39 of the largest entry per term: far below the f32 rounding of the
+ *                             entries that dominate the sum).  One exponent per operand tensor; [decoder | skip]
+ *                             operands share one.
+ *                      zero   an all-zero operand takes e = 0: the product is exactly zero.
+ *                      inf / NaN in an operand makes its scale NaN: every output of that launch is non-finite --
+ *                             never a wrong finite number.
+ *                    The 3-channel and narrow direct kernels the split modes fall back to stay exact f32.
+ * Additions to the enum only: CTX_ABI_VERSION and the ctx_config layout are those of ABI 4. */
+enum { CTX_PREC_F32 = 0, CTX_PREC_BF16X3 = 1, CTX_PREC_FP16X3 = 2, CTX_PREC_FP16X3D = 3 };
 
 typedef struct ctx_config {
     int32_t variant;    /* CTX_VARIANT_* */

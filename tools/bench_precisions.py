@@ -1,5 +1,5 @@
-"""Step and call times of the three precision modes (f32 | bf16x3 | fp16x3) in ONE process, the modes alternating round by round so
-that drift of the box hits all three alike; medians over the rounds and the ratios fp16x3 / f32, fp16x3 / bf16x3.
+"""Step and call times of the four precision modes (f32 | bf16x3 | fp16x3 | fp16x3d) in ONE process, the modes alternating round by round
+so that drift of the box hits all alike; medians over the rounds and the ratios fp16x3 / f32, fp16x3 / bf16x3, fp16x3d / f32, fp16x3d / fp16x3.
    python tools/bench_precisions.py [--rounds 9] [--out profiles/precision_modes.txt]
 Cases:
    ContextSkipNew 64x64, B = 256:  dev_forward_backward + dev_adam, 15 steps behind one sync (as tools/split_errors_b256.py times them)
@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from imitation_from_observation_amd import Translator  # noqa: E402
 
-MODES = ("f32", "bf16x3", "fp16x3")
+MODES = ("f32", "bf16x3", "fp16x3", "fp16x3d")
 
 
 def frames(B, H, W, seed):
@@ -105,11 +105,11 @@ def main():
     rows.append(("encode, 25 frames 64x64, ms/call", inf["encode"]))
 
     lines = [f"precision modes, one process, modes alternating, median of {a.rounds} rounds (min .. max); device: {torch.cuda.get_device_name(0)}",
-             f"{'case':62s} {'f32':>22s} {'bf16x3':>22s} {'fp16x3':>22s}  fp16x3/f32  fp16x3/bf16x3"]
+             f"{'case':62s} {'f32':>22s} {'bf16x3':>22s} {'fp16x3':>22s} {'fp16x3d':>22s}  fp16x3/f32  fp16x3/bf16x3  fp16x3d/f32  fp16x3d/fp16x3"]
     for lab, r in rows:
         med = {m: statistics.median(r[m]) for m in MODES}
         cells = " ".join(f"{med[m]:8.3f} ({min(r[m]):.3f}..{max(r[m]):.3f})".rjust(22) for m in MODES)
-        lines.append(f"{lab:62s} {cells}  {med['fp16x3'] / med['f32']:10.3f}  {med['fp16x3'] / med['bf16x3']:13.3f}")
+        lines.append(f"{lab:62s} {cells}  {med['fp16x3'] / med['f32']:10.3f}  {med['fp16x3'] / med['bf16x3']:13.3f}  {med['fp16x3d'] / med['f32']:11.3f}  {med['fp16x3d'] / med['fp16x3']:14.3f}")
     text = "\n".join(lines) + "\n"
     print(text, end="")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
