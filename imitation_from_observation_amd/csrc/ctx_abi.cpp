@@ -47,6 +47,14 @@ int ctx_create_ex(const ctx_config* cfg, int device, void* stream, void* arena, 
     ctx_handle* h = new ctx_handle();
     h->cfg = *cfg;
     h->opt = options_from_env();             // CTX_<NAME> in the environment = this handle's defaults; ctx_set_option changes them
+    // dconv bit 32 (part of the built-in default only) = "bit 16 by mode": ContextAEReal's forward-type direct launches take the handle's
+    // split arithmetic where that was measured to win in every row -- bf16x3 and fp16x3 -- and not in fp16x3d, whose split_absmax launch in
+    // front of every product costs more than the split product saves at 36x64 and at 25 frames (profiles/precision_modes.txt).  Resolved
+    // here and read back without bit 32; a stated value without it (CTX_DCONV=27) holds in every mode.
+    if (h->opt.v[OPT_DCONV] > 0 && (h->opt.v[OPT_DCONV] & 32)) {
+        h->opt.v[OPT_DCONV] &= ~32;
+        if (cfg->precision == CTX_PREC_FP16X3D) h->opt.v[OPT_DCONV] &= ~16;
+    }
     OptScope os(&h->opt);
     h->device = device;
     h->H = cfg->H; h->W = cfg->W; h->d = cfg->df_dim; h->F = cfg->featsize; h->Bm = cfg->max_batch;

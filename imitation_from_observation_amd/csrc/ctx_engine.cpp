@@ -446,8 +446,12 @@ void set_routing(ctx_handle* h) {
     // smallest grid whose stride-2 transposed conv runs position-major: in f32 ContextSkipNew's 4x4 grids keep the class-major launch
     // (64 problems of 1 .. 9 taps leave a tail)
     rt.q_minpos = skipnew && f32 ? 64 : 0;
-    rt.h4_direct_bf16 = skipnew;       // exact f32 arithmetic either way; measured faster in ContextSkipNew's split-bf16 step only
-    rt.direct3 = skipnew ? use_dc3(h) : h->gen->narrow;   // ContextAEReal's narrow f32 path runs every layer on the direct kernels
+    // exact f32 arithmetic either way; measured faster in ContextSkipNew's split-bf16 step only.  ContextAEReal's narrow path keeps the
+    // f32 handle's d_h4 kernel in every mode (its 3-channel family is exact f32 throughout).
+    rt.h4_direct_bf16 = skipnew || h->gen->narrow;
+    rt.direct3 = skipnew ? use_dc3(h) : h->gen->narrow;   // ContextAEReal's narrow path runs every layer on the direct kernels
+    // ... whose forward-type launches with >= 8 input channels take the handle's split arithmetic under option dconv bit 16
+    rt.dc_split = !skipnew && !f32 && h->gen->narrow && (h->opt.v[OPT_DCONV] & 16) != 0;
 }
 
 // d_h4 (conv2d_transpose to the 3 image channels) in one pass on the vector ALUs (convt3.hip) instead of scatter product + gather.
@@ -508,6 +512,14 @@ double useful_frac(const Geo& g) { return tap_frac_p(g.hb, g.wb, g.hs, g.ws, g.K
 // small-grid operand [x1 | x2] of c1 + c2 channels, x2 (a decoder layer's ctx skip) read at image index img % nmod2; c2 = 0: x1 alone
 struct Cat { const float* x1; int c1; const float* x2 = nullptr; int c2 = 0; int nmod2 = 1; };
 
+// operand format of a direct forward-type launch (dconv.h: DcFwd::fmt): the handle's split mode where the routing record says so; the
+// launcher keeps the channel counts without a split form (3, 64) on the exact-f32 kernel
+void dc_format(ctx_handle* h, DcFwd& P) {
+    if (!h->rt.dc_split) return;
+    P.fmt = h->cfg.precision;
+    P.slots = ws_of(h).slots;
+}
+
 // y = conv2d(x, w) into ep: x [nimg, hb, wb, ca] -> [nimg, hs, ws, cb], w read as [K, K, ca, cb].  The encoders' layers and the input
 // gradient of every decoder layer.
 void conv(ctx_handle* h, const std::string& label, const Geo& g, const float* x, int ca, int nimg, const float* w, int cb, const Epi& ep,
@@ -520,6 +532,7 @@ void conv(ctx_handle* h, const std::string& label, const Geo& g, const float* x,
         DcFwd P{};
         P.x1 = x; P.ld1 = ca; P.c1 = ca; P.CI = ca; P.hin = g.hb; P.win = g.wb; P.nimg = nimg;
         P.w = w; P.wmode = 0; P.N = cb; P.ep = ep; P.wp = h->wpack; P.pc = &h->pack;
+        dc_format(h, P);
         dconv_conv(h->stream, P, g.s, g.pad);
     } else if (ca == 3) {
         KmC3Gather a{c4of(h, x), g.hb, g.wb, g.hs, g.ws, R, g_zeros};
@@ -555,6 +568,7 @@ void convt(ctx_handle* h, const std::string& label, const Geo& g, const Cat& in,
         P.x1 = in.x1; P.ld1 = in.c1; P.c1 = in.c1; P.CI = cb;
         if (in.x2) { P.x2 = in.x2; P.ld2 = in.c2; P.nmod2 = in.nmod2; }
         P.hin = hs; P.win = ws; P.nimg = nimg; P.w = w; P.wmode = 1; P.N = ca; P.ep = ep; P.wp = h->wpack; P.pc = &h->pack;
+        dc_format(h, P);
         if (g.s == 2) dconv_convt2(h->stream, P); else dconv_convt1(h->stream, P);
     } else if (prod) {
         convt_product(h->stream, KmCat2{in.x1, in.c1, in.c1, in.x2, in.c2, in.nmod2, hs * ws, R, cb / KC, g_zeros}, w, cb, ca, h->PP, R, ws_of(h));

@@ -57,8 +57,9 @@ struct GenState {
     int C0 = 3;                  // frame channels: 3 (cin = 3 kernels) or a multiple of 32
     int nset = 1;                // 1: one encoder for src, tgt, ctx; 2: `conv` (set 0) + `conv_context` (set 1)
     bool residual = false;       // out = decode(.) + ctx frame
-    bool narrow = false;         // ContextAEReal in f32: activations and filters at their REAL widths (32/16/16/8), every conv / deconv and
-                                 // filter gradient on the direct kernels of dconv.h (no zero padding to 32 channels anywhere but the codes)
+    bool narrow = false;         // ContextAEReal (f32; the split modes under option dconv bit 8): activations and filters at their REAL widths
+                                 // (32/16/16/8), every conv / deconv and filter gradient on the direct kernels of dconv.h (no zero padding to 32
+                                 // channels anywhere but the codes)
     // ---- derived geometry
     int Fp = 0;                  // padded featsize
     int gh[4], gw[4];            // grid after encoder layer k
@@ -96,6 +97,8 @@ struct Routing {
     int q_minpos = 0;            // smallest grid (positions) of a stride-2 position-major transposed conv
     bool h4_direct_bf16 = false; // d_h4 on its direct kernel (convt3.hip) in split-bf16 mode too
     bool direct3 = false;        // 3-channel layers on the direct kernels of dconv.h (the frames / d out read as [pixel][3], no 4-channel copies)
+    bool dc_split = false;       // ContextAEReal's narrow path in a split mode: forward-type direct launches with 8 .. 32 input channels use the
+                                 // handle's split arithmetic (dconv.h: FMT; option dconv bit 16); false: the exact-f32 direct kernel
 };
 
 }  // namespace ctxi

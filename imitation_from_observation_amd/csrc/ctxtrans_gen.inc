@@ -46,10 +46,11 @@ int gen_spec(const ctx_config& c, GenState& r) {
     }
     r.C0 = c.C;
     {
-        const bool dc = opt(OPT_DCONV) != 0;
+        // f32: any bit of the option; a split mode: bit 8 (cleared = the channel-padded implicit-GEMM route)
+        const bool dc = c.precision == CTX_PREC_F32 ? opt(OPT_DCONV) != 0 : (opt(OPT_DCONV) & 8) != 0;
         int hh = c.H, ww = c.W;
         for (int k = 0; k < 4; ++k) { if (r.S[k] == 2) { hh /= 2; ww /= 2; } }
-        r.narrow = dc && c.variant == CTX_VARIANT_REAL && c.precision == CTX_PREC_F32 && c.W % 64 == 0 &&      // grids 64 / 32 / 16 wide: whole 16-pixel row blocks
+        r.narrow = dc && c.variant == CTX_VARIANT_REAL && c.W % 64 == 0 &&      // grids 64 / 32 / 16 wide: whole 16-pixel row blocks
                    ((int64_t)hh * ww * r.nf[3]) % 32 == 0;                                                      // the flatten feeds the FC GEMMs in 32-wide K chunks
         // every (input channels, filter columns) pair the direct kernels would meet must be one they are instantiated for
         for (int k = 0; k < 4 && r.narrow; ++k) {

@@ -25,7 +25,7 @@
 
 #include <type_traits>
 
-#include "igemm.h"
+#include "igemm_split.h"
 
 namespace ctx {
 
@@ -44,6 +44,7 @@ struct DcClass {
 };
 
 struct DcPackCache;
+struct SplitSlots;                                 // launch.h
 
 struct DcFwd {
     const float* x1; int ld1; int c1;              // input channels [0, c1)
@@ -68,6 +69,9 @@ struct DcFwd {
     Epi ep;
     unsigned long long* trace = nullptr;           // -DDC_TRACE builds of tools/dconv_bench.hip: s_memtime stamps [block][wave][tile][8] (never set by the product)
     DcPackCache* pc = nullptr;                     // host side only: where packed filters are kept between launches (null: pack into wp every time)
+    int fmt = 0;                                   // operand format of the products: 0 exact f32, or a SplitFmt (launches with 8 .. 32 input channels only)
+    const float* dyn = nullptr;                    // SPLIT_FP16D: this launch's SplitSlot::scale {2^e_x, 2^e_w, f1, f2}, x = [x1 | x2] (one exponent), w = the filter
+    SplitSlots* slots = nullptr;                   // host side only, SPLIT_FP16D: the lane's slot ring the launcher draws `dyn` from
 };
 
 // Packed-filter cache of one handle.  The LDS image of a layer's filter (dconv_pack_kernel) depends on the parameters and on the layer's
@@ -131,9 +135,47 @@ constexpr int DC_PF = 12;           // prefetch slots per thread: the big-tile k
 constexpr int DC_PF_SMALL = 4;      // ... and the kernels built for TWO blocks per CU (<= 128 registers): tiles of <= 2048 elements, so that one
                                     // block's landing / epilogue / barriers run under the other's MFMA loop
 typedef unsigned dc_u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned dc_u32x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 dc_f16x4 __attribute__((ext_vector_type(4)));
+typedef short dc_s16x4 __attribute__((ext_vector_type(4)));
 
-template <int CIK, int MI, int NB, int PF = DC_PF>
+// THE SPLIT FORM (FMT = SPLIT_BF16 | SPLIT_FP16 | SPLIT_FP16D; 8 .. 32 input channels): the same kernel -- same tiles, same LDS
+// footprint, CIP, tab[] offsets and bank analysis, same epilogue -- with the products on the 16-bit matrix cores.  Each 16-byte LDS
+// item [4 x f32] (four consecutive k of one row) holds [4 x hi | 4 x lo] 16-bit terms instead: split2<FMT> of igemm_split.h (the one
+// statement of the split arithmetic) is applied where data enters LDS -- land() on the prefetch registers, the staging loop on the
+// packed f32 filter (dconv_pack_kernel and DcPackCache stay f32: no format key, and under SPLIT_FP16D the filter's scale is this
+// launch's) -- once per element, which up to 25 taps then read.  One ds_read_b128 per fragment still feeds the lane's whole k-group:
+// its low half is the hi operand, its high half the lo operand of v_mfma_f32_16x16x16_{f16,bf16}, whose lane layout (lane (l15, kg)
+// supplies k = 4 kg + j) IS the kernel's K order.  Per chunk the four v_mfma_f32_16x16x4_f32 become the three terms
+// w_lo x_hi + w_hi x_lo + w_hi x_hi (small terms first, as in igemm_split.h); the accumulators are rescaled in front of the epilogue
+// (SPLIT_FP16: 2^(-2 CTX_FP16_EXP); SPLIT_FP16D: (acc * f1) * f2 from the launch's SplitSlot; SPLIT_BF16: not at all).
+// 16x16x16 per chunk, not 16x16x32 per chunk pair: the 32-deep instruction wants a lane's hi terms of BOTH chunks in four consecutive
+// registers, and a ds_read_b128 of one item delivers [hi | lo] of ONE chunk -- so either eight v_mov per fragment pair on the vector
+// issue port that the MFMAs share, or four b64 reads per fragment pair and a four-buffer pipeline (twice the fragment registers of
+// the 3 x 2 / 2 x 4 tiles, which are at the register limit).  The per-chunk form drops into the existing two-buffer pipeline
+// unchanged.  This was decided from the instruction counts; the pair form was not built and measured.
+// CIK == 4 (3-channel input, scalar LDS writes) has no split form: exact f32, like the whole 3-channel family.  Neither has
+// dconv_wgrad_kernel below: its K is the pixel index and its fragments are scalar LDS reads, so nothing of the above carries over;
+// filter gradients are exact f32 in every mode (include/ctxtrans.h states both next to the modes' range contract).
+template <int FMT>
+__device__ __forceinline__ dc_u32x4 dc_split4(const dc_u32x4 v, float dsc) {         // [4 x f32] -> [4 x hi | 4 x lo]
+    uint32_t h0, l0, h1, l1;
+    split2<FMT>(__uint_as_float(v.x), __uint_as_float(v.y), h0, l0, dsc);
+    split2<FMT>(__uint_as_float(v.z), __uint_as_float(v.w), h1, l1, dsc);
+    return dc_u32x4{h0, h1, l0, l1};
+}
+template <int FMT>
+__device__ __forceinline__ f32x4 dc_mfma16(float a0, float a1, float b0, float b1, const f32x4& c) {      // 16x16x16 on two packed 16-bit pairs per operand
+    const dc_u32x2 a = {__float_as_uint(a0), __float_as_uint(a1)}, b = {__float_as_uint(b0), __float_as_uint(b1)};
+    if constexpr (FMT == SPLIT_BF16)
+        return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(dc_s16x4, a), __builtin_bit_cast(dc_s16x4, b), c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(dc_f16x4, a), __builtin_bit_cast(dc_f16x4, b), c, 0, 0, 0);
+}
+
+template <int CIK, int MI, int NB, int PF = DC_PF, int FMT = 0>
 __global__ __launch_bounds__(DC_THREADS, (PF <= DC_PF_SMALL ? 4 : 2)) void dconv_fwd_kernel(const DcFwd P, int ntiles, int nslots) {
+    static_assert(FMT == 0 || (CIK >= 8 && CIK <= 32), "the split form exists for 8 .. 32 input channels");
     const int CIP = P.CIP;                                 // (only in address set-up: the MFMA loop reads through abase[] + tab[])
     constexpr int NP = NB * 16;
     constexpr int TPC = CIK >= 16 ? 1 : 16 / CIK;          // taps per 16-k chunk
@@ -144,6 +186,8 @@ __global__ __launch_bounds__(DC_THREADS, (PF <= DC_PF_SMALL ? 4 : 2)) void dconv
     float* tile = smem;
     const int tile_floats = (P.IH * P.IW * CIP + 3) & ~3;
     float* W4 = smem + tile_floats;
+    float dsx = 0.f, dsw = 0.f, rf1 = 1.f, rf2 = 1.f;      // SPLIT_FP16D: operand scales 2^e_x, 2^e_w and the two rescale factors (wave-uniform loads)
+    if constexpr (FMT == SPLIT_FP16D) { dsx = P.dyn[0]; dsw = P.dyn[1]; rf1 = P.dyn[2]; rf2 = P.dyn[3]; }
 
     // ---- resident filter: columns [n0, n0 + NP) of the packed image wp[slot * CIK / 4 + kq][NPT][4]
     {
@@ -158,7 +202,13 @@ __global__ __launch_bounds__(DC_THREADS, (PF <= DC_PF_SMALL ? 4 : 2)) void dconv
                 v[u] = i < total ? src[(int64_t)row * P.NPT + P.n0 + n] : zero4();
             }
 #pragma unroll
-            for (int u = 0; u < 4; ++u) if (i0 + u * DC_THREADS < total) dst[i0 + u * DC_THREADS] = v[u];
+            for (int u = 0; u < 4; ++u) {
+                if constexpr (FMT != 0) {                    // the packed image is f32: split here, with this launch's filter scale
+                    const dc_u32x4 sv = dc_split4<FMT>(dc_u32x4{__float_as_uint(v[u].x), __float_as_uint(v[u].y), __float_as_uint(v[u].z), __float_as_uint(v[u].w)}, dsw);
+                    v[u] = make_float4(__uint_as_float(sv.x), __uint_as_float(sv.y), __uint_as_float(sv.z), __uint_as_float(sv.w));
+                }
+                if (i0 + u * DC_THREADS < total) dst[i0 + u * DC_THREADS] = v[u];
+            }
         }
     }
     if constexpr (CIK == 4) for (int i = tid; i < P.IH * P.IW; i += DC_THREADS) tile[i * 4 + 3] = 0.f;   // the 4th channel is never loaded
@@ -273,7 +323,9 @@ __global__ __launch_bounds__(DC_THREADS, (PF <= DC_PF_SMALL ? 4 : 2)) void dconv
             for (int j = 0; j < PF; ++j) {
                 // (two-source tiles: halo lanes outside the image were loaded from a pixel that exists and become zeros here)
                 const bool halo = P.x2 && !((unsigned)(iy0 + iy) < (unsigned)P.hin && (unsigned)(ix0 + ix) < (unsigned)P.win);
-                if (iy < P.IH) *reinterpret_cast<dc_u32x4*>(&tile[lds0 + j * (SPX * CIP)]) = halo ? dc_u32x4{0u, 0u, 0u, 0u} : pf[j];
+                dc_u32x4 pv = pf[j];
+                if constexpr (FMT != 0) pv = dc_split4<FMT>(pv, dsx);
+                if (iy < P.IH) *reinterpret_cast<dc_u32x4*>(&tile[lds0 + j * (SPX * CIP)]) = halo ? dc_u32x4{0u, 0u, 0u, 0u} : pv;
                 ix += rx; iy += qy;
                 if (ix >= roww) { ix -= roww; ++iy; }
             }
@@ -353,6 +405,17 @@ __global__ __launch_bounds__(DC_THREADS, (PF <= DC_PF_SMALL ? 4 : 2)) void dconv
                     bp += 64 * NP;
                 };
                 auto mma = [&](int buf) {
+                    if constexpr (FMT != 0) {                // items are [hi.x hi.y | lo.z lo.w]: w_lo x_hi, w_hi x_lo, w_hi x_hi
+#pragma unroll
+                        for (int term = 0; term < 3; ++term)
+#pragma unroll
+                            for (int mi = 0; mi < NMI; ++mi)
+#pragma unroll
+                                for (int nb = 0; nb < NB; ++nb) {
+                                    const float4 &w = b4[buf][nb], &x = a4[buf][mi];
+                                    acc[mi][nb] = dc_mfma16<FMT>(term == 0 ? w.z : w.x, term == 0 ? w.w : w.y, term == 1 ? x.z : x.x, term == 1 ? x.w : x.y, acc[mi][nb]);
+                                }
+                    } else {
 #pragma unroll
                     for (int tt = 0; tt < 4; ++tt) {
 #pragma unroll
@@ -368,6 +431,7 @@ __global__ __launch_bounds__(DC_THREADS, (PF <= DC_PF_SMALL ? 4 : 2)) void dconv
 #endif
                             }
                         }
+                    }
                     }
                 };
                 // software pipeline: the fragments of chunk g + 1 are read before the MFMAs of chunk g, and the table entry of chunk
@@ -431,6 +495,15 @@ __global__ __launch_bounds__(DC_THREADS, (PF <= DC_PF_SMALL ? 4 : 2)) void dconv
             if (wv + DC_NW * (MI - 1) < nrb) run(std::integral_constant<int, MI>{});
             else if constexpr (MI > 1) { if (active) run(std::integral_constant<int, MI - 1>{}); }
 #endif
+            if constexpr (FMT == SPLIT_FP16 || FMT == SPLIT_FP16D) {      // the operands were x 2^e_x, w 2^e_w: exact power-of-two rescales (FP16D: the smaller factor first)
+#pragma unroll
+                for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+                    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            acc[mi][nb][r] = FMT == SPLIT_FP16 ? acc[mi][nb][r] * (1.0f / (float)(1ll << (2 * CTX_FP16_EXP))) : (acc[mi][nb][r] * rf1) * rf2;
+            }
             if (ci == P.ncls - 1) {                          // the tile's last MFMA loop is done: every wave has read its last fragment
                 DC_STAMP(2);
                 __syncthreads();

@@ -21,34 +21,44 @@ int cik_of(int CI) { return CI == 3 ? 4 : CI <= 8 ? 8 : CI <= 16 ? 16 : CI <= 32
 // (4 x 2, 4 x 4, 3 x 4 and anything x 8 spill)
 bool fwd_cfg_ok(int mi, int nb) { return nb == 1 ? mi <= 4 : nb == 2 ? mi <= 3 : nb == 4 ? mi <= 2 : false; }
 
-template <int CIK, int MI, int NB>
+template <int CIK, int MI, int NB, int FMT>
 void launch_fwd_one(hipStream_t s, const DcFwd& P, int occ, dim3 grid, size_t lds, int ntiles, int nslots) {
     if constexpr ((NB == 1 && MI <= 4) || (NB == 2 && MI <= 3) || (NB == 4 && MI <= 2)) {
         if constexpr (MI * NB <= 2) {          // (MI x NB = 4 spills at 128 registers)
             if (occ == 2) {                                   // the two-blocks-per-CU build (<= 128 registers, 4 prefetch slots)
-                ensure_dyn_lds((const void*)dconv_fwd_kernel<CIK, MI, NB, DC_PF_SMALL>, (size_t)LDS_TOTAL / 2);
-                hipLaunchKernelGGL((dconv_fwd_kernel<CIK, MI, NB, DC_PF_SMALL>), grid, dim3(DC_THREADS), lds, s, P, ntiles, nslots);
+                ensure_dyn_lds((const void*)dconv_fwd_kernel<CIK, MI, NB, DC_PF_SMALL, FMT>, (size_t)LDS_TOTAL / 2);
+                hipLaunchKernelGGL((dconv_fwd_kernel<CIK, MI, NB, DC_PF_SMALL, FMT>), grid, dim3(DC_THREADS), lds, s, P, ntiles, nslots);
                 return;
             }
         }
-        ensure_dyn_lds((const void*)dconv_fwd_kernel<CIK, MI, NB>, (size_t)LDS_TOTAL);
-        hipLaunchKernelGGL((dconv_fwd_kernel<CIK, MI, NB>), grid, dim3(DC_THREADS), lds, s, P, ntiles, nslots);
+        ensure_dyn_lds((const void*)dconv_fwd_kernel<CIK, MI, NB, DC_PF, FMT>, (size_t)LDS_TOTAL);
+        hipLaunchKernelGGL((dconv_fwd_kernel<CIK, MI, NB, DC_PF, FMT>), grid, dim3(DC_THREADS), lds, s, P, ntiles, nslots);
     }
 }
 
-template <int CIK, int MI>
+template <int CIK, int MI, int FMT>
 void launch_fwd_nb(hipStream_t s, const DcFwd& P, int NB, int occ, dim3 grid, size_t lds, int ntiles, int nslots) {
-    if (NB == 4) launch_fwd_one<CIK, MI, 4>(s, P, occ, grid, lds, ntiles, nslots);
-    else if (NB == 2) launch_fwd_one<CIK, MI, 2>(s, P, occ, grid, lds, ntiles, nslots);
-    else launch_fwd_one<CIK, MI, 1>(s, P, occ, grid, lds, ntiles, nslots);
+    if (NB == 4) launch_fwd_one<CIK, MI, 4, FMT>(s, P, occ, grid, lds, ntiles, nslots);
+    else if (NB == 2) launch_fwd_one<CIK, MI, 2, FMT>(s, P, occ, grid, lds, ntiles, nslots);
+    else launch_fwd_one<CIK, MI, 1, FMT>(s, P, occ, grid, lds, ntiles, nslots);
 }
 
-template <int CIK>
+template <int CIK, int FMT = 0>
 void launch_fwd_mi(hipStream_t s, const DcFwd& P, int MI, int NB, int occ, dim3 grid, size_t lds, int ntiles, int nslots) {
-    if (MI == 4) launch_fwd_nb<CIK, 4>(s, P, NB, occ, grid, lds, ntiles, nslots);
-    else if (MI == 3) launch_fwd_nb<CIK, 3>(s, P, NB, occ, grid, lds, ntiles, nslots);
-    else if (MI == 2) launch_fwd_nb<CIK, 2>(s, P, NB, occ, grid, lds, ntiles, nslots);
-    else launch_fwd_nb<CIK, 1>(s, P, NB, occ, grid, lds, ntiles, nslots);
+    if (MI == 4) launch_fwd_nb<CIK, 4, FMT>(s, P, NB, occ, grid, lds, ntiles, nslots);
+    else if (MI == 3) launch_fwd_nb<CIK, 3, FMT>(s, P, NB, occ, grid, lds, ntiles, nslots);
+    else if (MI == 2) launch_fwd_nb<CIK, 2, FMT>(s, P, NB, occ, grid, lds, ntiles, nslots);
+    else launch_fwd_nb<CIK, 1, FMT>(s, P, NB, occ, grid, lds, ntiles, nslots);
+}
+
+// the split form (dconv.h: FMT) exists for 8 .. 32 input channels
+template <int FMT>
+void launch_fwd_split(hipStream_t s, const DcFwd& P, int CIK, int MI, int NB, int occ, dim3 grid, size_t lds, int ntiles, int nslots) {
+    switch (CIK) {
+        case 8: launch_fwd_mi<8, FMT>(s, P, MI, NB, occ, grid, lds, ntiles, nslots); break;
+        case 16: launch_fwd_mi<16, FMT>(s, P, MI, NB, occ, grid, lds, ntiles, nslots); break;
+        default: launch_fwd_mi<32, FMT>(s, P, MI, NB, occ, grid, lds, ntiles, nslots); break;
+    }
 }
 }  // namespace
 
@@ -242,8 +252,25 @@ static bool dconv_launch2(hipStream_t s, DcFwd P, int span) {
 
 static void dconv_launch(hipStream_t s, DcFwd P, int span) {
     g_dc2_last[0] = 0;
-    if (dconv_launch2(s, P, span)) return;
     const int CIK = cik_of(P.CI), CIP = dc_cip(CIK, P.S);
+    // The split form: 8 .. 32 input channels.  A 3-channel input (scalar LDS writes) and the 64-channel instantiations run the exact-f32
+    // kernel in every mode (include/ctxtrans.h: inside every mode's contract); the LDS-DMA kernel of dconv2.h cannot convert on landing.
+    if (P.fmt && (CIK < 8 || CIK > 32)) P.fmt = 0;
+    if (!P.fmt && dconv_launch2(s, P, span)) return;
+    if (P.fmt == SPLIT_FP16D) {                               // this launch's operand scales: x = [x1 | x2] under ONE exponent, w = the whole filter
+        if (!P.slots || !P.slots->dev) { set_launch_error("dconv: fp16x3d launch without scale slots"); return; }
+        SplitSlot* slot = P.slots->next();
+        AmaxOp rx, rw;
+        const int64_t hw = (int64_t)P.hin * P.win;
+        rx.add(P.x1, P.nimg * hw, P.c1, P.ld1);
+        if (P.x2) rx.add(P.x2, (P.nimg < P.nmod2 ? P.nimg : P.nmod2) * hw, P.CI - P.c1, P.ld2);
+        int ntaps = 0;
+        for (int c = 0; c < P.ncls; ++c) ntaps += P.cls[c].ntaps;
+        if (ntaps != 25) { set_launch_error("dconv: fp16x3d states the whole 25-tap filter, launch has %d taps", ntaps); return; }
+        rw.add(P.w, 1, (int64_t)25 * P.CI * P.N, 0);
+        split_absmax(s, rx, rw, slot);
+        P.dyn = slot->scale;
+    }
     P.CIP = CIP;
     int NBT = (P.N + 15) / 16;
     NBT = NBT <= 1 ? 1 : NBT <= 2 ? 2 : NBT <= 4 ? 4 : 8;
@@ -280,7 +307,7 @@ static void dconv_launch(hipStream_t s, DcFwd P, int span) {
                                      (int64_t)ih * iw * (CIK == 4 ? 3 : CIK / 4) <= (int64_t)DC_THREADS * DC_PF_SMALL) ? 2 : 1;
                     const int tiles_y = (P.hlog + th - 1) / th, tiles_x = (P.wlog + tw - 1) / tw;
                     const double rows = (double)P.hlog * P.wlog / ((double)tiles_y * tiles_x);          // real output pixels per tile
-                    const double compute = (double)busiest * nb * 4.0 * nchunks * 32.0;
+                    const double compute = (double)busiest * nb * nchunks * (P.fmt ? 3 * 16.0 : 4 * 32.0);      // per chunk: four f32 MFMAs | three 16-bit ones
                     const double loadc = (double)tile / 16.0, land = (double)tile / 79.0, fixed = 3000.0 + 40.0 * mi * nb * P.ncls;   // (barriers, prefetch issue, epilogue: calibrated on the tile sweeps of tools/dconv_bench.hip)
                     const double T = (compute > loadc ? compute : loadc) + (land + fixed) / occ;
                     const double score = rows / (T * (NBT / nb));
@@ -317,6 +344,9 @@ static void dconv_launch(hipStream_t s, DcFwd P, int span) {
     if (!pack_cached(P, CIK, nslots, s)) launch_pack(s, P, CIK, nslots);
     for (int n0 = 0; n0 < P.N; n0 += NB * 16) {
         P.n0 = n0;
+        if (P.fmt == SPLIT_BF16) { launch_fwd_split<SPLIT_BF16>(s, P, CIK, MI, NB, best_occ, grid, lds, ntiles, nslots); continue; }
+        if (P.fmt == SPLIT_FP16) { launch_fwd_split<SPLIT_FP16>(s, P, CIK, MI, NB, best_occ, grid, lds, ntiles, nslots); continue; }
+        if (P.fmt == SPLIT_FP16D) { launch_fwd_split<SPLIT_FP16D>(s, P, CIK, MI, NB, best_occ, grid, lds, ntiles, nslots); continue; }
         switch (CIK) {
             case 4: launch_fwd_mi<4>(s, P, MI, NB, best_occ, grid, lds, ntiles, nslots); break;
             case 8: launch_fwd_mi<8>(s, P, MI, NB, best_occ, grid, lds, ntiles, nslots); break;

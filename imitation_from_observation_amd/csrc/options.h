@@ -19,7 +19,10 @@ enum Opt {
                        // 16 inference launches of <= 32 images as one product + a gather (launch.h: convt_product)
     OPT_DIRECT3,       // bits: 1 3-channel layers on the direct kernels, 2 c3conv, 4 c3wgrad, 8 d_h4 forward in one pass (convt3), 16 ... on the matrix cores at >= 128 images (convt3m)
     OPT_DCONV,         // bits: 1 ContextAEReal in f32 on the narrow-channel direct kernels (dconv.h), 2 their forward-type launches on the K-sliced
-                       // double-buffered LDS-DMA kernel (dconv2.h) where it applies
+                       // double-buffered LDS-DMA kernel (dconv2.h) where it applies (4: its four-class launches too), 8 ContextAEReal in a split
+                       // mode takes the narrow path (cleared: the channel-padded implicit GEMM), 16 its forward-type launches with >= 8 input
+                       // channels use the handle's split arithmetic (dconv.h: FMT; cleared: the exact-f32 direct kernel), 32 (in the default,
+                       // 59, only) bit 16 by mode: resolved at ctx_create -- cleared for fp16x3d handles -- and read back without bit 32
     OPT_RCHAIN,        // 1: ContextAEReal's FC middle in three launches (rchain.hip)
     OPT_EARLY_ADAM,    // 1: Adam's slices beside the remaining backward in the fused ContextSkipNew steps (bit-identical; -0.06 ms, round 4)
     OPT_CNN_LANES,     // Inception front end: -1 = by precision (lanes in the split modes only), 0 / 1 = off / on

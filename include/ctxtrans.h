@@ -108,7 +108,19 @@ enum {
  *                      zero   an all-zero operand takes e = 0: the product is exactly zero.
  *                      inf / NaN in an operand makes its scale NaN: every output of that launch is non-finite --
  *                             never a wrong finite number.
- *                    The 3-channel and narrow direct kernels the split modes fall back to stay exact f32.
+ *                    Exact f32 in every mode (inside every mode's contract; they are no operands of a split product): the 3-channel
+ *                    family (c3conv, c3wgrad, convt3, convt3m: every layer that reads or writes the 3-channel frames) and the
+ *                    filter gradients of the narrow direct path (dconv_wgrad_kernel / c3wgrad: their K is the pixel index and
+ *                    their fragments are scalar LDS reads, so the split form of the forward kernel does not carry over).
+ *                    ContextAEReal (CTX_VARIANT_REAL, W a multiple of 64) in a split mode, per launch:
+ *                      split   h1..h3_conv forward, d_h1..d_h3 forward and the input gradients of all six (8 .. 32 input
+ *                              channels): the split form of dconv_fwd_kernel (option dconv bit 16; fp16x3d: the scale of
+ *                              [decoder | skip] is one exponent over both tensors, the filter's is taken per launch), and
+ *                              every fully connected layer (implicit GEMM).
+ *                      exact   h0_conv forward, d_h4 forward, d_h4's input gradient, the frame gradients of a VJP, and all
+ *                              eight filter gradients.  With bit 16 cleared also the six layers above (the f32 direct kernel).
+ *                      Option dconv bit 8 cleared (or W not a multiple of 64): every launch but the 3-channel ones is a
+ *                      split implicit GEMM on channel-padded tensors, as before the narrow path existed for these modes.
  * Additions to the enum only: CTX_ABI_VERSION and the ctx_config layout are those of ABI 4. */
 enum { CTX_PREC_F32 = 0, CTX_PREC_BF16X3 = 1, CTX_PREC_FP16X3 = 2, CTX_PREC_FP16X3D = 3 };
 
@@ -167,7 +179,12 @@ const char* ctx_last_error(const ctx_handle* h);
  *                    16 inference launches of <= 32 images as one product + a gather
  *   direct3     31   bits: 1 3-channel layers on the direct kernels, 2 c3conv, 4 c3wgrad, 8 d_h4 forward in one pass, 16 d_h4 forward on the
  *                    matrix cores at >= 128 images (convt3m.hip)  [fixed at create]
- *   dconv        3   bits: 1 ContextAEReal in f32 on the narrow-channel direct kernels, 2 the K-sliced LDS-DMA forward kernel     [fixed at create]
+ *   dconv       59   bits: 1 ContextAEReal in f32 on the narrow-channel direct kernels, 2 the K-sliced LDS-DMA forward kernel (4: its four-class
+ *                    launches too), 8 ContextAEReal in a split mode takes the narrow path (cleared: channel-padded implicit GEMM, 3 x the step),
+ *                    16 its forward-type launches with >= 8 input channels use the split arithmetic (cleared: the exact-f32 direct kernel).
+ *                    32 (in the default only) = bit 16 by mode: at create it is dropped, and with it bit 16 for CTX_PREC_FP16X3D handles
+ *                    (measured slower there: profiles/precision_modes.txt), so a handle reads back 27 or 11; a stated value without bit 32
+ *                    (CTX_DCONV=27) holds in every mode     [fixed at create]
  *   rchain       1   ContextAEReal's FC middle in three launches
  *   early_adam   1   Adam's slices beside the remaining backward in the fused ContextSkipNew steps (bit-identical; -0.06 ms)
  *   cnn_lanes   -1   Inception front end: branch lanes; -1 = in the split-bf16 mode only      (ctx_cnn handles: environment at create) [fixed at create]
@@ -183,7 +200,8 @@ const char* ctx_last_error(const ctx_handle* h);
  *   ContextSkipNew 64x64 B = 256:  overlap 0 | posmajor 0 | xcd_swizzle 0 1 2 3 4 5 6 | balance 0 1 2 3 4 5 8 13 | wconvt 0 1 3 5 7 15 23 29 |
  *                                  direct3 0 1 3 5 7 9 15 23 | early_adam 0 | adam_prio -1 0 1;  graph_lanes 0 1 and early_adam 0 1 also in
  *                                  tests/test_gpu_parity.py against the oracle
- *   ContextAEReal 36x64 B = 64:    overlap 0 1 | dconv 0 1 5 7 | rchain 0 | direct3 0 15 | posmajor 0
+ *   ContextAEReal 36x64 B = 64:    overlap 0 1 | dconv 0 1 5 7 | rchain 0 | direct3 0 15 | posmajor 0;  dconv 3 11 27 in the three split modes against
+ *                                  the oracle (tests/test_gpu_real_split.py: bits 8 and 16 choose kernels with different ARITHMETIC, each within its mode's bars)
  * Combinations of two non-default switches are not enumerated; cnn_* (front end) and graphs 0 run in their own suites' defaults only.
  * Not options: CTX_DEBUG_POISON=1 (debugging aid: every device
  * buffer a handle allocates is filled with 0xFF bytes -- float NaN -- so that a read of never-written memory shows on every run),
