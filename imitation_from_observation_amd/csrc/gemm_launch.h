@@ -16,13 +16,9 @@ namespace ctx {
 
 void splitk_reduce(hipStream_t s, const Epi& ep, int M, int N, int nprob, int nsplit);
 
-// one operand format of the split kernel (igemm_split.h: SPLIT_BF16 / SPLIT_FP16 / SPLIT_FP16D); the LDS image is the same for all.
-// dyn (SPLIT_FP16D only): the launch's device-resident scales, SplitSlot::scale
-template <int FMT, class LA, class LB, int MI, int NI, int WM, int WN>
-static void launch_tile_split_fmt(hipStream_t s, const LA& a, const LB& b, Epi ep, int M, int N, int nprob, int nsplit, const float* dyn = nullptr) {
-    constexpr int NT = 64 * WM * WN, TM = 32 * MI * WM, TN = 32 * NI * WN;
-    constexpr size_t lds = 2 * (size_t)(STile<LA::KM, TM, NT>::FLOATS + STile<LB::KM, TN, NT>::FLOATS) * sizeof(float);
-    if (lds > 65536) ensure_dyn_lds((const void*)igemm_split_kernel<FMT, LA, LB, MI, NI, WM, WN>, lds);
+// Grid of one tile launch: gm x gn tiles per (problem, split), the block count, and ep's XCD swizzle settled for that count.
+struct TileGrid { int gm, gn; unsigned nblk; };
+inline TileGrid tile_grid(Epi& ep, int M, int N, int TM, int TN, int nprob, int nsplit) {
     const int gm = (M + TM - 1) / TM, gn = (N + TN - 1) / TN;
     int64_t nblk = (int64_t)gm * gn * nprob * nsplit;
     if (nblk < 64) ep.xcd_swizzle = 0;
@@ -31,8 +27,18 @@ static void launch_tile_split_fmt(hipStream_t s, const LA& a, const LB& b, Epi e
         if (grp % 8 == 0) ep.swz_group = (int)grp; else ep.xcd_swizzle = 0;
     }
     if (ep.xcd_swizzle && !ep.swz_group) nblk = (nblk + 7) / 8 * 8;
-    dim3 grid((unsigned)nblk);
-    hipLaunchKernelGGL((igemm_split_kernel<FMT, LA, LB, MI, NI, WM, WN>), grid, dim3(NT), lds, s, a, b, ep, M, N, nprob, nsplit, gm, gn, dyn);
+    return TileGrid{gm, gn, (unsigned)nblk};
+}
+
+// one operand format of the split kernel (igemm_split.h: SPLIT_BF16 / SPLIT_FP16 / SPLIT_FP16D); the LDS image is the same for all.
+// dyn (SPLIT_FP16D only): the launch's device-resident scales, SplitSlot::scale
+template <int FMT, class LA, class LB, int MI, int NI, int WM, int WN>
+static void launch_tile_split_fmt(hipStream_t s, const LA& a, const LB& b, Epi ep, int M, int N, int nprob, int nsplit, const float* dyn = nullptr) {
+    constexpr int NT = 64 * WM * WN, TM = 32 * MI * WM, TN = 32 * NI * WN;
+    constexpr size_t lds = 2 * (size_t)(STile<LA::KM, TM, NT, FMT>::FLOATS + STile<LB::KM, TN, NT, FMT>::FLOATS) * sizeof(float);
+    if (lds > 65536) ensure_dyn_lds((const void*)igemm_split_kernel<FMT, LA, LB, MI, NI, WM, WN>, lds);
+    const TileGrid g = tile_grid(ep, M, N, TM, TN, nprob, nsplit);
+    hipLaunchKernelGGL((igemm_split_kernel<FMT, LA, LB, MI, NI, WM, WN>), dim3(g.nblk), dim3(NT), lds, s, a, b, ep, M, N, nprob, nsplit, g.gm, g.gn, dyn);
 }
 
 // ws.prec (CTX_PREC_BF16X3, CTX_PREC_FP16X3 or CTX_PREC_FP16X3D): the one place a split launch picks its operand format -- and, having
@@ -60,16 +66,8 @@ static void launch_tile_f32(hipStream_t s, const LA& a, const LB& b, Epi ep, int
     // two LDS stages of [A tile | B tile]; above the 64 KiB default the limit is raised once per kernel
     constexpr size_t lds = 2 * (size_t)(Tile<LA::KM, TM, NT>::FLOATS + Tile<LB::KM, TN, NT>::FLOATS) * sizeof(float);
     if (lds > 65536) ensure_dyn_lds((const void*)igemm_kernel<LA, LB, MI, NI, WM, WN>, lds);
-    const int gm = (M + TM - 1) / TM, gn = (N + TN - 1) / TN;
-    int64_t nblk = (int64_t)gm * gn * nprob * nsplit;
-    if (nblk < 64) ep.xcd_swizzle = 0;
-    if (ep.xcd_swizzle && ep.swz_group) {                 // grouped: one group = one (split, parity class); needs whole groups of 8
-        const int64_t grp = (int64_t)gm * gn * (nprob / 4);
-        if (grp % 8 == 0) ep.swz_group = (int)grp; else ep.xcd_swizzle = 0;
-    }
-    if (ep.xcd_swizzle && !ep.swz_group) nblk = (nblk + 7) / 8 * 8;
-    dim3 grid((unsigned)nblk);
-    hipLaunchKernelGGL((igemm_kernel<LA, LB, MI, NI, WM, WN>), grid, dim3(NT), lds, s, a, b, ep, M, N, nprob, nsplit, gm, gn);
+    const TileGrid g = tile_grid(ep, M, N, TM, TN, nprob, nsplit);
+    hipLaunchKernelGGL((igemm_kernel<LA, LB, MI, NI, WM, WN>), dim3(g.nblk), dim3(NT), lds, s, a, b, ep, M, N, nprob, nsplit, g.gm, g.gn);
 }
 
 // BIG = the 8-wave 256x256 tile is instantiated for this loader pair
@@ -85,15 +83,11 @@ static void launch_tile(hipStream_t s, const LA& a, const LB& b, const Epi& ep, 
 // B = 256 (f32: -6..-20 % everywhere; bf16x3: the conv gather prefers 4 waves), so each launcher names its pair's choice.
 template <class LA, class LB, int W, bool SPLIT>
 static void launch_128(hipStream_t s, const LA& a, const LB& b, const Epi& ep, int M, int N, int nprob, int nsplit, const SplitWs& ws) {
-    if constexpr (SPLIT) {
-        if constexpr (W == 1) launch_tile_split<LA, LB, 2, 1, 2, 4>(s, a, b, ep, M, N, nprob, nsplit, ws);
-        else if constexpr (W == 2) launch_tile_split<LA, LB, 1, 2, 4, 2>(s, a, b, ep, M, N, nprob, nsplit, ws);
-        else launch_tile_split<LA, LB, 2, 2, 2, 2>(s, a, b, ep, M, N, nprob, nsplit, ws);
-    } else {
-        if constexpr (W == 1) launch_tile_f32<LA, LB, 2, 1, 2, 4>(s, a, b, ep, M, N, nprob, nsplit);
-        else if constexpr (W == 2) launch_tile_f32<LA, LB, 1, 2, 4, 2>(s, a, b, ep, M, N, nprob, nsplit);
-        else launch_tile_f32<LA, LB, 2, 2, 2, 2>(s, a, b, ep, M, N, nprob, nsplit);
-    }
+    constexpr int L[3][4] = {{2, 2, 2, 2},      // W = 0: MI, NI, WM, WN
+                             {2, 1, 2, 4},      // W = 1
+                             {1, 2, 4, 2}};     // W = 2
+    if constexpr (SPLIT) launch_tile_split<LA, LB, L[W][0], L[W][1], L[W][2], L[W][3]>(s, a, b, ep, M, N, nprob, nsplit, ws);
+    else launch_tile_f32<LA, LB, L[W][0], L[W][1], L[W][2], L[W][3]>(s, a, b, ep, M, N, nprob, nsplit);
 }
 
 template <class L> struct is_plain_loader : std::integral_constant<bool, std::is_same<L, KmPlain>::value || std::is_same<L, NmPlain>::value || std::is_same<L, NmPlain2>::value> {};
@@ -166,7 +160,7 @@ static void launch_igemm(hipStream_t s, const LA& a, const LB& b, Epi ep, int M,
             static std::mutex mu;
             static std::set<std::string> seen;
             char buf[256];
-            snprintf(buf, sizeof buf, "igemm %s | M %d N %d nprob %d chunks %d..%d tile %dx%d tiles %lld nsplit %d swz %d/%d", __PRETTY_FUNCTION__ + 0 ? "" : "", M, N, nprob, min_chunks, max_chunks, 64 * MI, 64 * NI,
+            snprintf(buf, sizeof buf, "igemm | M %d N %d nprob %d chunks %d..%d tile %dx%d tiles %lld nsplit %d swz %d/%d", M, N, nprob, min_chunks, max_chunks, 64 * MI, 64 * NI,
                      (long long)tiles, nsplit, ep.xcd_swizzle, ep.swz_group);
             std::lock_guard<std::mutex> g(mu);
             if (seen.insert(std::string(buf) + typeid(LA).name()).second) fprintf(stderr, "%s  [%s x %s]\n", buf, typeid(LA).name(), typeid(LB).name());

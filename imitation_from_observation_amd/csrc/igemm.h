@@ -88,8 +88,6 @@ __device__ __forceinline__ void tap_slice(int chunk, int ntap, int& seg, int& sl
 
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ __forceinline__ float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-// branch-free guarded load: `zeros` is >= 16 bytes of device zeros
-__device__ __forceinline__ float4 ldg4_or0(const float* p, bool ok, const float* zeros) { return ldg4(ok ? p : zeros); }
 
 // ------------------------------------------------------------------------------------------------
 // Epilogue: what happens to D.  One struct serves forward (bias + lrelu), backward (skip-gradient
@@ -1212,9 +1210,9 @@ struct Tile {
 };
 
 // per-thread view of a loader: the loop-invariant state of the float4 this thread fetches in pass p
-template <class L, int TR, int NT>
+// (T = the operand's LDS tile: Tile<...> here, STile<..., FMT> in igemm_split.h -- its thread map decides which float4s are this thread's)
+template <class L, class T>
 struct Fetch {
-    using T = Tile<L::KM, TR, NT>;
     typename L::Ctx c[T::NPASS];
     __device__ void init(const L& l, int prob, int row0, int tid) {
 #pragma unroll
@@ -1225,6 +1223,53 @@ struct Fetch {
     }
     __device__ float4 load1(const L& l, const typename L::Pos& q, int p) const { return l.load(c[p], q); }
 };
+
+// ------------------------------------------------------------------------------------------------
+// What igemm_kernel and igemm_split_kernel (igemm_split.h) share: block order, tile / problem / split decode, the K range
+// of a split.  None of it depends on the operand format.  The accumulator clear, the D-layout row formula and the split-K
+// partial store stay written out in both kernels.  As __forceinline__ helpers each changed some instantiation (compile only,
+// same counts of every other instruction class): a clear_acc(acc) over MI x NI x 16, s_waitcnt 169 -> 171 in
+// igemm_kernel<KmPlain, NmPlain, 2,2,2,2>; d_row(r, h), 81 -> 82 in <KmC3Gather, NmC3Weights, 1,1,1,1>; a store_partials with
+// the kernel's own index expressions, SGPRs 104 -> 106 in <KmConvGather, NmPlain, 2,4,4,2> (with regrouped ones also VGPRs
+// 88 -> 90 in <KmCat2, KmPlain, 2,1,2,4>); and the split kernel can only call it by leaving its per-row `if (ep.slab)`
+// for an early return, which is another epilogue (s_waitcnt -15 .. -35).  A per-row helper was worse (SGPRs +2 .. +4).
+// ------------------------------------------------------------------------------------------------
+// Block b -> work item under ep.xcd_swizzle: workgroups are dealt round-robin to the 8 XCDs, so this gives each XCD a contiguous
+// run of work.  Padding blocks of the grid map past the last item: the KERNEL returns on those (a helper that reports "no work"
+// cost every instantiation 4-14 SGPRs and 4.5 % more instructions -- compile-only finding, do not fold the check in here).
+__device__ __forceinline__ int swizzled_item(const Epi& ep, int b) {
+    if (ep.swz_group) {
+        const int per = ep.swz_group >> 3, l = b >> 3, grp = l / per;
+        return grp * ep.swz_group + (b & 7) * per + (l - grp * per);
+    }
+    const int per = (int)gridDim.x >> 3;                // the launcher pads the grid to a multiple of 8
+    return (b & 7) * per + (b >> 3);
+}
+
+// Work item -> block tile.  1-D order, m-tile fastest, then n-tile, then problem, then K-split.  Problems go last-first: the
+// (1,1) parity class of a transposed conv has 9 taps against 4 for (0,0), and the longest blocks
+// must not form the tail.  (XCD-contiguous and n-tile-fastest orders were measured: -8..-20 %.)
+struct WorkItem { int prob, split, m0, n0; };
+template <int TM, int TN>
+__device__ __forceinline__ WorkItem decode_item(const Epi& ep, int rest, int gm, int gn, int nprob) {
+    const int bx = rest % gm; rest /= gm;
+    const int by = rest % gn; rest /= gn;
+    // transposed conv (nprob == 4): parity classes have 4/6/6/9 taps.  Dispatching 9,6,4,6 makes the two
+    // blocks that share a CU (one from each half of a 2-per-CU round) sum to 13 and 12 taps, not 15 and 10.
+    const int pr = rest % nprob;
+    const int prob = ep.perm ? (int)ep.perm[pr] : nprob == 4 ? ((0x3201 >> (4 * (3 - pr))) & 15) : nprob - 1 - pr;
+    return WorkItem{prob, rest / nprob, bx * TM, by * TN};
+}
+
+// chunks [cb, ce) of problem prob that K-split `split` of nsplit multiplies
+struct KRange { int cb, ce; };
+template <class LA>
+__device__ __forceinline__ KRange k_range(const LA& la, int prob, int split, int nsplit) {
+    const int nch = la.nchunks_of(prob);
+    const int per = (nch + nsplit - 1) / nsplit;
+    const int cb = split * per;
+    return KRange{cb, (cb + per < nch) ? cb + per : nch};
+}
 
 // ------------------------------------------------------------------------------------------------
 // The kernel.  1-D grid of gm * gn * nprob * nsplit blocks; a block is WM x WN waves, each wave owns
@@ -1250,39 +1295,20 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm_kernel(const LA la, const 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int wm = wv / WN, wn = wv % WN, l31 = lane & 31, h = lane >> 5;
 
-    // 1-D grid, m-tile fastest, then n-tile, then problem, then K-split.  Problems go last-first: the
-    // (1,1) parity class of a transposed conv has 9 taps against 4 for (0,0), and the longest blocks
-    // must not form the tail.  (XCD-contiguous and n-tile-fastest orders were measured: -8..-20 %.)
-    int rest = blockIdx.x;
-    if (ep.xcd_swizzle) {                               // workgroups are dealt round-robin to the 8 XCDs: give each XCD a contiguous run of work
-        int item;
-        if (ep.swz_group) {
-            const int per = ep.swz_group >> 3, l = rest >> 3, grp = l / per;
-            item = grp * ep.swz_group + (rest & 7) * per + (l - grp * per);
-        } else {
-            const int per = (int)gridDim.x >> 3;            // the launcher pads the grid to a multiple of 8
-            item = (rest & 7) * per + (rest >> 3);
-        }
+    int item = blockIdx.x;
+    if (ep.xcd_swizzle) {
+        item = swizzled_item(ep, item);
         if (item >= gm * gn * nprob * nsplit) return;
-        rest = item;
     }
-    const int bx = rest % gm; rest /= gm;
-    const int by = rest % gn; rest /= gn;
-    // transposed conv (nprob == 4): parity classes have 4/6/6/9 taps.  Dispatching 9,6,4,6 makes the two
-    // blocks that share a CU (one from each half of a 2-per-CU round) sum to 13 and 12 taps, not 15 and 10.
-    const int pr = rest % nprob;
-    const int prob = ep.perm ? (int)ep.perm[pr] : nprob == 4 ? ((0x3201 >> (4 * (3 - pr))) & 15) : nprob - 1 - pr;
-    const int split = rest / nprob;
-    const int m0 = bx * TM, n0 = by * TN;
+    const WorkItem w = decode_item<TM, TN>(ep, item, gm, gn, nprob);
+    const int prob = w.prob, split = w.split, m0 = w.m0, n0 = w.n0;
 
     const auto kblk = make_kblock(la, prob);
-    const int nch = la.nchunks_of(prob);
-    const int per = (nch + nsplit - 1) / nsplit;
-    const int cb = split * per;
-    const int ce = (cb + per < nch) ? cb + per : nch;
+    const KRange kr = k_range(la, prob, split, nsplit);
+    const int cb = kr.cb, ce = kr.ce;
 
-    Fetch<LA, TM, NT> fa;      // per-lane invariants of this thread's float4s
-    Fetch<LB, TN, NT> fb;
+    Fetch<LA, TA> fa;      // per-lane invariants of this thread's float4s
+    Fetch<LB, TB> fb;
     fa.init(la, prob, m0, tid);
     fb.init(lb, prob, n0, tid);
 

@@ -132,20 +132,6 @@ struct STile {
     }
 };
 
-template <class L, int TR, int NT>
-struct SFetch {
-    using T = STile<L::KM, TR, NT>;
-    typename L::Ctx c[T::NPASS];
-    __device__ void init(const L& l, int prob, int row0, int tid) {
-#pragma unroll
-        for (int p = 0; p < T::NPASS; ++p) {
-            if (L::KM) l.prep(prob, row0 + T::km_row(tid, p), T::km_k4(tid), c[p]);
-            else l.prep(prob, T::nm_kk(tid, p), row0 + T::nm_r4(tid), c[p]);
-        }
-    }
-    __device__ float4 load1(const L& l, const typename L::Pos& q, int p) const { return l.load(c[p], q); }
-};
-
 template <int FMT>
 __device__ __forceinline__ f32x16 mfma_split(const u32x4& a, const u32x4& b, const f32x16& c) {
     if constexpr (FMT == SPLIT_FP16 || FMT == SPLIT_FP16D)
@@ -173,34 +159,20 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm_split_kernel(const LA la, 
     float dsa = 0.f, dsb = 0.f;                         // SPLIT_FP16D: this launch's operand scales 2^e_a, 2^e_b (wave-uniform loads)
     if constexpr (FMT == SPLIT_FP16D) { dsa = dyn[0]; dsb = dyn[1]; }
 
-    int rest = blockIdx.x;
-    if (ep.xcd_swizzle) {                               // workgroups are dealt round-robin to the 8 XCDs: give each XCD a contiguous run of work
-        int item;
-        if (ep.swz_group) {
-            const int per = ep.swz_group >> 3, l = rest >> 3, grp = l / per;
-            item = grp * ep.swz_group + (rest & 7) * per + (l - grp * per);
-        } else {
-            const int per = (int)gridDim.x >> 3;            // the launcher pads the grid to a multiple of 8
-            item = (rest & 7) * per + (rest >> 3);
-        }
+    int item = blockIdx.x;
+    if (ep.xcd_swizzle) {
+        item = swizzled_item(ep, item);
         if (item >= gm * gn * nprob * nsplit) return;
-        rest = item;
-    }                              // same block order as igemm_kernel
-    const int bx = rest % gm; rest /= gm;
-    const int by = rest % gn; rest /= gn;
-    const int pr = rest % nprob;
-    const int prob = ep.perm ? (int)ep.perm[pr] : nprob == 4 ? ((0x3201 >> (4 * (3 - pr))) & 15) : nprob - 1 - pr;
-    const int split = rest / nprob;
-    const int m0 = bx * TM, n0 = by * TN;
+    }
+    const WorkItem w = decode_item<TM, TN>(ep, item, gm, gn, nprob);
+    const int prob = w.prob, split = w.split, m0 = w.m0, n0 = w.n0;
 
     const auto kblk = make_kblock(la, prob);
-    const int nch = la.nchunks_of(prob);
-    const int per = (nch + nsplit - 1) / nsplit;
-    const int cb = split * per;
-    const int ce = (cb + per < nch) ? cb + per : nch;
+    const KRange kr = k_range(la, prob, split, nsplit);
+    const int cb = kr.cb, ce = kr.ce;
 
-    SFetch<LA, TM, NT> fa;
-    SFetch<LB, TN, NT> fb;
+    Fetch<LA, TA> fa;
+    Fetch<LB, TB> fb;
     fa.init(la, prob, m0, tid);
     fb.init(lb, prob, n0, tid);
 
