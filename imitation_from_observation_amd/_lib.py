@@ -103,6 +103,11 @@ SIGNATURES = {
     "ctx_reward_set_cache": (_c.c_int, [_P, _c.c_int, _F, _F, _c.c_int]),
     "ctx_reward_costs": (_c.c_int, [_P, _c.c_int, _U8, _c.c_int, _c.c_float, _c.c_int, _F]),
     "ctx_reward_costs_dev": (_c.c_int, [_P, _c.c_int, _P, _c.c_int, _c.c_float, _c.c_int, _F]),
+    "ctx_reconstruct": (_c.c_int, [_P, _U8, _U8, _c.c_int, _c.c_int, _F, _F]),
+    "ctx_reconstruct_f32": (_c.c_int, [_P, _F, _F, _c.c_int, _c.c_int, _F, _F]),
+    "ctx_reconstruct_dev": (_c.c_int, [_P, _P, _P, _c.c_int, _c.c_int, _F, _F]),
+    "ctx_reward_costs_recon": (_c.c_int, [_P, _c.c_int, _U8, _c.c_int, _c.c_float, _F]),
+    "ctx_reward_costs_recon_dev": (_c.c_int, [_P, _c.c_int, _P, _c.c_int, _c.c_float, _F]),
     "ctx_reward_cache_begin": (_c.c_int, [_P, _c.c_int, _c.c_int]),
     "ctx_reward_cache_add_dev": (_c.c_int, [_P, _c.c_int, _P, _P, _c.c_int]),
     "ctx_reward_cache_add": (_c.c_int, [_P, _c.c_int, _U8, _U8, _c.c_int]),

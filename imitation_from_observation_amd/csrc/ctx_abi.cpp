@@ -452,6 +452,157 @@ int ctx_reward_costs_dev(ctx_handle* h, int vp, const float* d_frames, int npath
     return reward_costs_tail(h, rc, d_frames, B, scale, ablation, costs);
 }
 
+// ---- out2 / input_z of the feed [frames, ctx, frames] and the 'recon' ablation's cost (base.py:234-235, :250-252) ------------------
+// The caller's rows are path-major (row p * per + j = frame j of group p); the src slot holds them frame-major (row j * nctx + p), so
+// that every forward loader's skip index img % nctx is the row's group (forward: MODE_RECON).  Staging of not-yet-transposed f32
+// frames: the tgt slot, which MODE_RECON does not read.
+static int recon_check(ctx_handle* h, const void* frames, int nctx, int B) {
+    TRY(check_B(h, B));
+    if (!frames) return fail(h, CTX_E_INVALID, "NULL input");
+    if (nctx < 1 || nctx > B || B % nctx) return fail(h, CTX_E_INVALID, "nctx=%d must lie in [1, B=%d] and divide B", nctx, B);
+    return CTX_OK;
+}
+static bool recon_identity(int nctx, int B) { return nctx == 1 || nctx == B; }      // one group, or one frame per group: the orders coincide
+
+// uint8 frames (and contexts) -> the src (and ctx) slot
+static int recon_stage_u8(ctx_handle* h, const uint8_t* frames, const uint8_t* ctx0, int nctx, int B) {
+    const int64_t npi = h->npi;
+    HIP_TRY(h, hipMemcpyAsync(h->u8, frames, (size_t)B * npi, hipMemcpyHostToDevice, h->stream));
+    if (ctx0) HIP_TRY(h, hipMemcpyAsync(h->u8 + B * npi, ctx0, (size_t)nctx * npi, hipMemcpyHostToDevice, h->stream));
+    if (recon_identity(nctx, B)) u8_to_f32(h->stream, h->u8, h->img + B * npi, B * npi);
+    else group_rows_u8(h->stream, h->u8, npi, h->img + B * npi, npi, npi, nctx, B / nctx);
+    if (ctx0) u8_to_f32(h->stream, h->u8 + B * npi, h->img + 2ll * B * npi, nctx * npi);
+    return CTX_OK;
+}
+
+// f32 frames on the device (anywhere, the handle's own slots included) -> the src slot
+static int recon_stage_dev(ctx_handle* h, const float* d_frames, int nctx, int B) {
+    const int64_t npi = h->npi;
+    const size_t bytes = (size_t)B * npi * sizeof(float);
+    float* slot = h->img + B * npi;
+    if (recon_identity(nctx, B)) {
+        if (d_frames != slot) HIP_TRY(h, hipMemcpyAsync(slot, d_frames, bytes, hipMemcpyDeviceToDevice, h->stream));
+        return CTX_OK;
+    }
+    if (d_frames == slot) {                           // (frames written in place, ctx_dev_frames: the transposition needs a second buffer)
+        HIP_TRY(h, hipMemcpyAsync(h->img, slot, bytes, hipMemcpyDeviceToDevice, h->stream));
+        d_frames = h->img;
+    }
+    group_rows_f32(h->stream, d_frames, npi, slot, npi, npi, nctx, B / nctx);
+    return CTX_OK;
+}
+
+static int recon_forward(ctx_handle* h, int nctx, bool inplace, int B) {
+    h->recon_nctx = nctx;
+    h->recon_inplace = inplace;
+    return forward_inference(h, B, MODE_RECON);
+}
+
+// out2 / input_z back to the host in the caller's row order
+static int recon_tail(ctx_handle* h, int nctx, int B, float* recon, float* feat) {
+    const int64_t npi = h->npi;
+    const float* z = h->Z + 2ll * B * h->Fp;
+    if (recon) {
+        const float* src = h->out;
+        if (!recon_identity(nctx, B)) {               // rows [B, 2B) of the output buffer (decoder pass 2's in a training forward) are free here
+            group_rows_f32(h->stream, h->out, npi, h->out + B * npi, npi, npi, B / nctx, nctx);
+            src = h->out + B * npi;
+        }
+        TRY(copy_d2h(h, recon, src, (size_t)B * npi * sizeof(float)));
+    }
+    if (feat) {
+        if (recon_identity(nctx, B))
+            HIP_TRY(h, hipMemcpy2DAsync(feat, h->F * sizeof(float), z, h->Fp * sizeof(float), h->F * sizeof(float), B, hipMemcpyDeviceToHost, h->stream));
+        else {                                        // rows [0, B) of the code buffer (translated_z) are free here: a packed [B, featsize] copy
+            group_rows_f32(h->stream, z, h->Fp, h->Z, h->F, h->F, B / nctx, nctx);
+            HIP_TRY(h, hipMemcpyAsync(feat, h->Z, (size_t)B * h->F * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        }
+    }
+    h->last_B = 0;
+    return finish(h);
+}
+
+int ctx_reconstruct(ctx_handle* h, const uint8_t* frames, const uint8_t* ctx0, int nctx, int B, float* recon, float* feat) {
+    if (!h) return CTX_E_INVALID;
+    TRY(need_frames(h));
+    TRY(recon_check(h, frames, nctx, B));
+    HIP_TRY(h, hipSetDevice(h->device));
+    TRY(recon_stage_u8(h, frames, ctx0, nctx, B));
+    TRY(recon_forward(h, nctx, ctx0 == nullptr, B));
+    return recon_tail(h, nctx, B, recon, feat);
+}
+
+int ctx_reconstruct_f32(ctx_handle* h, const float* frames, const float* ctx0, int nctx, int B, float* recon, float* feat) {
+    if (!h) return CTX_E_INVALID;
+    TRY(recon_check(h, frames, nctx, B));
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int64_t npi = h->npi;
+    float* land = recon_identity(nctx, B) ? h->img + B * npi : h->img;
+    HIP_TRY(h, hipMemcpyAsync(land, frames, (size_t)B * npi * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    TRY(recon_stage_dev(h, land, nctx, B));
+    if (ctx0) HIP_TRY(h, hipMemcpyAsync(h->img + 2ll * B * npi, ctx0, (size_t)nctx * npi * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    TRY(recon_forward(h, nctx, ctx0 == nullptr, B));
+    return recon_tail(h, nctx, B, recon, feat);
+}
+
+int ctx_reconstruct_dev(ctx_handle* h, const float* d_frames, const float* d_ctx0, int nctx, int B, float* recon, float* feat) {
+    if (!h) return CTX_E_INVALID;
+    TRY(recon_check(h, d_frames, nctx, B));
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int64_t npi = h->npi;
+    float* cslot = h->img + 2ll * B * npi;
+    // (the contexts first: d_ctx0 may lie in a slot the staging of the frames overwrites)
+    if (d_ctx0 && d_ctx0 != cslot) HIP_TRY(h, hipMemcpyAsync(cslot, d_ctx0, (size_t)nctx * npi * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    TRY(recon_stage_dev(h, d_frames, nctx, B));
+    TRY(recon_forward(h, nctx, d_ctx0 == nullptr, B));
+    return recon_tail(h, nctx, B, recon, feat);
+}
+
+// the cost kernel(s) on input_z, out2 and the frames of the src slot (all frame-major), then the B costs, path-major, to the host
+static int recon_costs_tail(ctx_handle* h, const ctx_handle::RewardCache& rc, int npaths, float scale, float* costs) {
+    const int B = npaths * rc.bs, o = h->opt.v[OPT_REWARD_SPLIT];
+    const bool split = h->npi % 4 == 0 && (o < 0 ? h->npi >= RC_SPLIT_MIN_NPI : o != 0);
+    if (split && !h->rpart) TRY(dev_alloc(h, &h->rpart, (int64_t)h->Bm * reward_costs_slices(h->npi)));
+    recon_costs(h->stream, h->Z + 2ll * B * h->Fp, h->Fp, h->F, h->out, h->img + B * h->npi, h->npi, rc.means, rc.bs, npaths, scale, h->rcosts,
+                split ? h->rpart : nullptr);
+    HIP_TRY(h, hipMemcpyAsync(costs, h->rcosts, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    h->rstats[CTX_REWARD_STAT_D2H_BYTES] += (int64_t)B * (int64_t)sizeof(float);
+    h->rstats[CTX_REWARD_STAT_COST_CALLS]++;
+    h->rstats[split ? CTX_REWARD_STAT_SPLIT_LAUNCHES : CTX_REWARD_STAT_PLAIN_LAUNCHES]++;
+    h->last_B = 0;
+    return finish(h);
+}
+
+static int recon_costs_check(ctx_handle* h, int vp, const void* frames, int npaths, const float* costs) {
+    if (vp < 0 || vp >= (int)h->rcache.size() || !h->rcache[vp].means) return fail(h, CTX_E_STATE, "no reward cache for viewpoint %d (ctx_reward_set_cache / ctx_reward_cache_finish first)", vp);
+    if (!frames || !costs || npaths <= 0) return fail(h, CTX_E_INVALID, "bad argument");
+    if ((int64_t)npaths * h->rcache[vp].bs > h->Bm) return fail(h, CTX_E_INVALID, "B=%lld outside [1, max_batch=%d]", (long long)npaths * h->rcache[vp].bs, h->Bm);
+    return CTX_OK;
+}
+
+int ctx_reward_costs_recon(ctx_handle* h, int vp, const uint8_t* frames, int npaths, float scale, float* costs) {
+    if (!h) return CTX_E_INVALID;
+    TRY(recon_costs_check(h, vp, frames, npaths, costs));
+    TRY(need_frames(h));
+    const ctx_handle::RewardCache& rc = h->rcache[vp];
+    const int B = npaths * rc.bs;
+    HIP_TRY(h, hipSetDevice(h->device));
+    TRY(recon_stage_u8(h, frames, nullptr, npaths, B));
+    TRY(recon_forward(h, npaths, true, B));
+    return recon_costs_tail(h, rc, npaths, scale, costs);
+}
+
+int ctx_reward_costs_recon_dev(ctx_handle* h, int vp, const float* d_frames, int npaths, float scale, float* costs) {
+    if (!h) return CTX_E_INVALID;
+    TRY(recon_costs_check(h, vp, d_frames, npaths, costs));
+    const ctx_handle::RewardCache& rc = h->rcache[vp];
+    const int B = npaths * rc.bs;
+    HIP_TRY(h, hipSetDevice(h->device));
+    TRY(recon_stage_dev(h, d_frames, npaths, B));
+    TRY(recon_forward(h, npaths, true, B));
+    return recon_costs_tail(h, rc, npaths, scale, costs);
+}
+
 // ---- the demo cache built on the device (base.py:195-223 without the host round trip of translated_z / out) ----------------------
 int ctx_reward_cache_begin(ctx_handle* h, int vp, int bs) {
     if (!h) return CTX_E_INVALID;

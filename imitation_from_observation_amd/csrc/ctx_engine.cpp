@@ -765,6 +765,7 @@ namespace ctxi {
 // Forward.  TRAIN/EVAL: st = [tgt | src] (2B), decoder = [translated | truth] (2B).
 // TRANSLATE: only what translated_z / out depend on (src encoder, ctx encoder, translate, decoder
 // pass 1) -- the subgraph TF would run for base.py:216-218.  ENCODE: `conv` encoder on src only.
+// RECON: only what out2 / input_z depend on when src == tgt (the 'recon' ablation's fetch; below).
 void forward(ctx_handle* h, int B, Mode mode) {
     OptScope os(&h->opt);
     h->act_serial++;
@@ -777,7 +778,12 @@ void forward(ctx_handle* h, int B, Mode mode) {
     const bool lanes = use_lanes(h) && mode != MODE_ENCODE;
     // images through `conv_context`: B, or the ONE frame every row shares (its code and skip activations are then read with row stride 0
     // / image index n % 1 by their consumers -- same values as B copies, 1 / B of the work)
-    const int nc = mode == MODE_TRANSLATE && h->ctx_single ? 1 : B;
+    // MODE_RECON: out2 / input_z of a feed with src == tgt -- the `conv` encoder once on the B frames (tgtimg_z IS input_z), `conv_context`
+    // on the recon_nctx contexts, no translate MLP and no decoder pass 1; the decoder runs on the `conv` codes, row r with the skips of
+    // context r % recon_nctx (frame-major rows: ctx_handle::recon_nctx)
+    const bool rec = mode == MODE_RECON;
+    const int nc = rec ? h->recon_nctx : mode == MODE_TRANSLATE && h->ctx_single ? 1 : B;
+    const float* ctx_img = h->img + (rec && h->recon_inplace ? 1 : 2) * B * npi;
     // refresh the 4-channel copy of the frames in use (what the cin = 3 loaders read)
     if (h->rt.direct3) {}
     else if (mode == MODE_TRAIN) pack_c4(h, h->img, 3ll * B * h->H * h->W);
@@ -787,20 +793,22 @@ void forward(ctx_handle* h, int B, Mode mode) {
     if (lanes) {
         fork(h, LANE_CTX);
         LaneSwap sw(h, LANE_CTX);
-        encoder_fwd(h, "conv_context", cx, h->img + 2 * B * npi, nc, h->c, h->cz, 0);
+        encoder_fwd(h, "conv_context", cx, ctx_img, nc, h->c, h->cz, 0);
     }
     if (mode == MODE_TRAIN) encoder_fwd(h, "conv", st, h->img, 2 * B, h->s, h->Z + (int64_t)B * F, 1);
     else encoder_fwd(h, "conv", st, h->img + B * npi, B, h->s, src_z, 1);
     if (mode == MODE_ENCODE) return;
     if (lanes) join(h, LANE_CTX);
-    else encoder_fwd(h, "conv_context", cx, h->img + 2 * B * npi, nc, h->c, h->cz, 0);
+    else encoder_fwd(h, "conv_context", cx, ctx_img, nc, h->c, h->cz, 0);
     // translate (arm_shaping.py:1309-1312): trans_h0 on concat([src_z, ctx_z], 1), then trans_z
-    KmPlain tcat{src_z, F, h->cz, nc == 1 && B > 1 ? 0 : F, F, B, 2 * F / KC, g_zeros};
-    fc_layer(h, "translate/trans_h0", tcat, B, 2 * F, h->Wp("translate/trans_h0/Matrix"), h->Wp("translate/trans_h0/bias"), F, 1, h->th0);
-    fc_layer(h, "translate/trans_z", km(h->th0, F, B, F), B, F, h->Wp("translate/trans_z/Matrix"), h->Wp("translate/trans_z/bias"), F, 0, h->Z);
-    // decoder (arm_shaping.py:1321-1330, :1334-1343)
+    if (!rec) {
+        KmPlain tcat{src_z, F, h->cz, nc == 1 && B > 1 ? 0 : F, F, B, 2 * F / KC, g_zeros};
+        fc_layer(h, "translate/trans_h0", tcat, B, 2 * F, h->Wp("translate/trans_h0/Matrix"), h->Wp("translate/trans_h0/bias"), F, 1, h->th0);
+        fc_layer(h, "translate/trans_z", km(h->th0, F, B, F), B, F, h->Wp("translate/trans_z/Matrix"), h->Wp("translate/trans_z/bias"), F, 0, h->Z);
+    }
+    // decoder (arm_shaping.py:1321-1330, :1334-1343); MODE_RECON: pass 2 alone, on tgtimg_z = input_z
     const int nd = mode == MODE_TRAIN ? 2 * B : B;
-    fc_layer(h, "deconv/d_h0_lin", km(h->Z, F, nd, F), nd, F, h->Wp("deconv/d_h0_lin/Matrix"), h->Wp("deconv/d_h0_lin/bias"), (int)h->D0, 1, h->dz);
+    fc_layer(h, "deconv/d_h0_lin", km(rec ? src_z : h->Z, F, nd, F), nd, F, h->Wp("deconv/d_h0_lin/Matrix"), h->Wp("deconv/d_h0_lin/bias"), (int)h->D0, 1, h->dz);
     const float* dec = h->dz;
     for (int k = 1; k <= 4; ++k) {
         const int c1 = (16 * d) >> k;                         // decoder stream | ctx skip h_{4-k}, c1 channels each
@@ -937,7 +945,9 @@ void backward(ctx_handle* h, int B, int sim_batch) {
 int forward_inference(ctx_handle* h, int B, Mode mode) {
     h->act_serial++;                 // (a replayed graph overwrites the activations too)
     if (!h->use_graphs || h->prof_on || B > 64) { forward(h, B, mode); return CTX_OK; }
-    ctx_handle::GraphSlot& g = h->graphs[(int)mode * (1 << 20) + (mode == MODE_TRANSLATE && h->ctx_single ? 1 << 19 : 0) + B];
+    // (B <= 64 here: bits 0-6; MODE_RECON's context layout: the number of contexts in bits 8-14, where they are in bit 18)
+    ctx_handle::GraphSlot& g = h->graphs[(int)mode * (1 << 20) + (mode == MODE_TRANSLATE && h->ctx_single ? 1 << 19 : 0) +
+                                         (mode == MODE_RECON ? (h->recon_nctx << 8) + (h->recon_inplace ? 1 << 18 : 0) : 0) + B];
     // A graph captured while every packed filter it uses was stale holds all its pack nodes ("self-packing": right after a training step)
     // and is valid for any later parameters -- they are read through the arena pointer at replay.  One captured on current entries
     // skips the packs: after a parameter change it is dropped and re-captured AT ONCE (the entries are stale now, so the new graph is

@@ -153,11 +153,16 @@ struct ctx_handle {
     SplitSlots slots[NLANE + 1];   // CTX_PREC_FP16X3D: the scale-slot rings (launch.h) that go with slab ([0]) and slabL[l] ([1 + l])
     float *wpack = nullptr, *wpackL[NLANE] = {};   // dconv's re-packed filters, one buffer per stream lane (concurrent launches)
     bool overlap = true;
-    // hipGraph cache of the two inference forwards (reward hook: batch-25 calls are launch-bound): key = mode * 2^20 + B
+    // hipGraph cache of the two inference forwards (reward hook: batch-25 calls are launch-bound): key = mode * 2^20 + B (+ the context layout: forward_inference)
     struct GraphSlot { int calls = 0; hipGraphExec_t exec = nullptr; uint64_t pack_version = 0; bool self_packing = false; };
     DcPackCache pack;                // packed filters of the direct kernels, valid for pack.version (dconv.h); bumped wherever parameters change
     bool ctx_single = false;         // MODE_TRANSLATE with ONE context frame for the whole batch (`[context] * batch_size`, base.py:217-218):
                                      // `conv_context` runs on that one frame and its outputs are read by every row (forward)
+    // MODE_RECON (out2 / input_z of the feed [frames, ctx, frames]): the src slot holds the B frames frame-major -- row j * recon_nctx + p
+    // is frame j of group p -- so row r reads the skips of context r % recon_nctx; the recon_nctx contexts are the first rows of the
+    // src slot (recon_inplace: the first frame of every group) or of the ctx slot
+    int recon_nctx = 1;
+    bool recon_inplace = true;
     std::map<int, GraphSlot> graphs;
     bool use_graphs = true, capturing = false;
     // data-parallel overlap: called from inside backward once the translate/* and deconv/* gradients are complete in the
@@ -249,7 +254,7 @@ struct ctx_handle {
     } while (0)
 
 namespace ctxi {
-enum Mode { MODE_TRAIN, MODE_TRANSLATE, MODE_ENCODE };
+enum Mode { MODE_TRAIN, MODE_TRANSLATE, MODE_ENCODE, MODE_RECON };
 constexpr int LANE_CTX = 0, LANE_DW = 1;
 int fail(ctx_handle* h, int code, const char* fmt, ...);
 int check_B(ctx_handle* h, int B);

@@ -207,11 +207,12 @@ void gen_rchain_weights(const ctx_handle* h, const float* base, const float* W[1
     for (int i = 0; i < 10; ++i) W[i] = base + o[i];
 }
 
-void gen_encoder_fwd(ctx_handle* h, int B, int set, int img0, int nimg, bool drop = false, bool fc = true) {
+// (in0 >= 0: the images are read at rows [in0, in0 + nimg) of the frame buffer instead; activations and codes still land at img0)
+void gen_encoder_fwd(ctx_handle* h, int B, int set, int img0, int nimg, bool drop = false, bool fc = true, int in0 = -1) {
     GenState& r = *h->gen;
     const float* P = h->arena;
     const std::string sc = set == 1 ? "conv_context" : "conv";
-    const float* in = h->img + (int64_t)img0 * h->npi;
+    const float* in = h->img + (int64_t)(in0 >= 0 ? in0 : img0) * h->npi;
     for (int k = 0; k < 4; ++k) {
         float* y = r.a[k] + (int64_t)img0 * r.gh[k] * r.gw[k] * r.cp[k];
         conv(h, sc + "/h" + std::to_string(k) + "_conv fwd", gen_geo(r, k), in, r.in_ch(k), nimg, P + r.w[set][k], r.cp[k],
@@ -264,9 +265,17 @@ void gen_forward(ctx_handle* h, int B, Mode mode) {
     const bool chain = mode == MODE_TRAIN && gen_rchain(h, B);
     // TRANSLATE: only what translated_z / out depend on (base.py:216-218) -- the src and ctx rows of the encoder batch, decoder pass 1;
     // with ONE context frame for the batch its row is encoded once and read by every row (stride 0 / image index n % 1)
-    const bool tr = mode == MODE_TRANSLATE;
-    const int nc = tr && h->ctx_single ? 1 : B;
-    if (tr && r.nset == 1) gen_encoder_fwd(h, B, 0, B, B + nc);                // img rows [src | ctx] are contiguous
+    // RECON: only what out2 / input_z depend on when src == tgt -- the `conv` encoder once on the B frames of the src slot, the context
+    // encoder on recon_nctx images, decoder pass 2 on the `conv` codes; row r reads the skips of context r % recon_nctx (frame-major
+    // rows, ctx_handle::recon_nctx).  With ONE encoder and the contexts in place (the first rows of the src slot) their skips ARE the
+    // first rows of the activations just computed: no second encoder launch.
+    const bool rec = mode == MODE_RECON;
+    const bool tr = mode == MODE_TRANSLATE || rec;                           // an inference forward
+    const int nc = rec ? h->recon_nctx : tr && h->ctx_single ? 1 : B;
+    const int skip0 = rec && r.nset == 1 && h->recon_inplace ? B : 2 * B;    // first image row of the context skips in r.a[*]
+    if (rec && r.nset == 1) gen_encoder_fwd(h, B, 0, B, h->recon_inplace ? B : B + nc);
+    else if (rec) { gen_encoder_fwd(h, B, 0, B, B); gen_encoder_fwd(h, B, 1, 2 * B, nc, false, true, h->recon_inplace ? B : 2 * B); }
+    else if (tr && r.nset == 1) gen_encoder_fwd(h, B, 0, B, B + nc);           // img rows [src | ctx] are contiguous
     else if (tr) { gen_encoder_fwd(h, B, 0, B, B); gen_encoder_fwd(h, B, 1, 2 * B, nc); }
     else if (r.nset == 1) gen_encoder_fwd(h, B, 0, 0, 3 * B, drop, !chain);
     else { gen_encoder_fwd(h, B, 0, 0, 2 * B); gen_encoder_fwd(h, B, 1, 2 * B, B); }
@@ -283,13 +292,13 @@ void gen_forward(ctx_handle* h, int B, Mode mode) {
         fc_layer(h, "translate/trans_h0", km(r.xcat, 2 * Fp, B, 2 * Fp), B, 2 * Fp, P + r.th0w, P + r.th0b, Fp, 1, r.th0);
         ew_mul(h->stream, r.th0d, Fp, r.th0, Fp, r.dM[4], Fp, B, Fp);
         fc_layer(h, "translate/trans_z", km(r.th0d, Fp, B, Fp), B, Fp, P + r.tzw, P + r.tzb, Fp, 0, h->Z);
-    } else {
+    } else if (!rec) {
         KmPlain tcat{src_z, Fp, ctx_z, nc == 1 && B > 1 ? 0 : Fp, Fp, B, 2 * Fp / KC, g_zeros};
         fc_layer(h, "translate/trans_h0", tcat, B, 2 * Fp, P + r.th0w, P + r.th0b, Fp, 1, r.th0);
         fc_layer(h, "translate/trans_z", km(r.th0, Fp, B, Fp), B, Fp, P + r.tzw, P + r.tzb, Fp, 0, h->Z);
     }
     const int nd = tr ? B : 2 * B;
-    const float* zin = h->Z;
+    const float* zin = rec ? src_z : h->Z;
     if (drop) { ew_mul(h->stream, r.zd, Fp, h->Z, Fp, r.dM[5], Fp, nd, Fp); zin = r.zd; }          // site 5: z * M5 feeds d_h0_lin (:1660)
     if (!chain) fc_layer(h, "deconv/d_h0_lin", km(zin, Fp, nd, Fp), nd, Fp, P + r.d0w, P + r.d0b, D0p, 1, r.dz);
     const float* dec = r.dz;
@@ -298,16 +307,19 @@ void gen_forward(ctx_handle* h, int B, Mode mode) {
         const int gi = 4 - k;                                   // d_hk mirrors encoder layer 4 - k (arm_shaping.py:1841-1857), whose output is the skip
         const Geo g = gen_geo(r, gi);
         const int ch = r.cp[gi], co = r.in_ch(gi);
-        const Cat in{dec, ch, r.a[gi] + 2ll * B * g.hs * g.ws * ch, ch, nc};     // [decoder | ctx third of the encoder batch]
+        const Cat in{dec, ch, r.a[gi] + (int64_t)skip0 * g.hs * g.ws * ch, ch, nc};     // [decoder | ctx third of the encoder batch]
         const std::string nm_ = "deconv/d_h" + std::to_string(k);
         if (k == 4 && co == 3) { convt3(h, nm_, g, in, nd, P + r.dw[k], P + r.db[k], h->out, tr); break; }
         Epi ep = epi_act(k < 4 ? r.e[k] : h->out, co, P + r.db[k], k < 4);
-        if (k == 4 && r.residual) {                              // out = h4 + tgtctx: the ctx frames serve both decoder passes
+        if (k == 4 && r.residual && !rec) {                              // out = h4 + tgtctx: the ctx frames serve both decoder passes
             ep.add1 = h->img + 2ll * B * h->npi; ep.lda1 = co; ep.add1_mod = (int64_t)B * h->H * h->W;     // (translate with one context frame: the entry points still lay out B copies for this add)
         }
         convt(h, nm_ + " fwd", g, in, nd, P + r.dw[k], co, ep, r.narrow, tr);
         dec = r.e[k];
     }
+    // RECON: out2 = h4 + tgtctx with the context maps repeating every nc rows -- a pass of its own, the same two additions in the same
+    // order as the epilogue's ((product + bias) + tgtctx)
+    if (rec && r.residual) add_period(h->stream, h->out, h->img + (int64_t)(h->recon_inplace ? B : 2 * B) * h->npi, (int64_t)nc * h->npi, (int64_t)B * h->npi);
 }
 
 // VJP frame / feature-map gradients, one launch per image slot [tgt | src | ctx] the caller asked for.  3-channel frames

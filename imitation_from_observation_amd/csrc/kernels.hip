@@ -936,6 +936,161 @@ void reward_costs(hipStream_t s, const float* feat, int ldf, int F, const float*
 }
 
 // ------------------------------------------------------------------------------------------------
+// The 'recon' ablation (base.py:250-252 with image_recon = model.out2): the handle keeps the frames of a launch
+// frame-major -- row j * ng + p holds frame j of path (group) p, so a row's context skip is image row % ng for every forward loader --
+// while callers hand over and get back path-major rows p * per + j.
+// group_rows: out row (r % per) * ng + r / per = in row r, for r < ng * per; n elements per row, row strides ldi / ldo.  The inverse
+// is the same call with ng and per exchanged.  uint8 input goes through prep_u8 (the bits of u8_to_f32_kernel).  V elements per lane:
+// 16 bytes of input where n, the strides and the pointers allow (uint8: 16 elements -> four float4 stores; f32: one float4).
+// ------------------------------------------------------------------------------------------------
+template <class T, int V>
+__global__ __launch_bounds__(NTHREADS) void group_rows_kernel(const T* __restrict__ in, int64_t ldi, float* __restrict__ out, int64_t ldo,
+                                                              int64_t n, int ng, int per) {
+    const int64_t nv = n / V, total = nv * ng * per;
+    for (int64_t i = (int64_t)blockIdx.x * NTHREADS + threadIdx.x; i < total; i += (int64_t)gridDim.x * NTHREADS) {
+        const int64_t r = i / nv, e = (i - r * nv) * V;
+        const T* src = in + r * ldi + e;
+        float* dst = out + ((r % per) * ng + r / per) * ldo + e;
+        if constexpr (sizeof(T) == 1 && V == 16) {
+            const uint4 q = *reinterpret_cast<const uint4*>(src);
+            const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                reinterpret_cast<float4*>(dst)[k] = make_float4(prep_u8((uint8_t)(w[k] & 255u)), prep_u8((uint8_t)((w[k] >> 8) & 255u)),
+                                                                prep_u8((uint8_t)((w[k] >> 16) & 255u)), prep_u8((uint8_t)(w[k] >> 24)));
+        } else if constexpr (sizeof(T) == 1 && V == 4) {
+            const uchar4 u = *reinterpret_cast<const uchar4*>(src);
+            *reinterpret_cast<float4*>(dst) = make_float4(prep_u8(u.x), prep_u8(u.y), prep_u8(u.z), prep_u8(u.w));
+        } else if constexpr (sizeof(T) == 1) {
+            dst[0] = prep_u8(src[0]);
+        } else if constexpr (V == 4) {
+            *reinterpret_cast<float4*>(dst) = *reinterpret_cast<const float4*>(src);
+        } else {
+            dst[0] = src[0];
+        }
+    }
+}
+
+template <class T, int V>
+static void group_rows_launch(hipStream_t s, const T* in, int64_t ldi, float* out, int64_t ldo, int64_t n, int ng, int per) {
+    hipLaunchKernelGGL((group_rows_kernel<T, V>), dim3(ew_blocks(n / V * ng * per)), dim3(NTHREADS), 0, s, in, ldi, out, ldo, n, ng, per);
+}
+static bool rows_aligned(const void* in, int64_t ldi, size_t esz, const float* out, int64_t ldo, int64_t n, int v) {
+    return n % v == 0 && (ldi * (int64_t)esz) % 16 == 0 && ldo % 4 == 0 && (uintptr_t)in % 16 == 0 && (uintptr_t)out % 16 == 0;
+}
+void group_rows_u8(hipStream_t s, const uint8_t* in, int64_t ldi, float* out, int64_t ldo, int64_t n, int ng, int per) {
+    if (rows_aligned(in, ldi, 1, out, ldo, n, 16)) group_rows_launch<uint8_t, 16>(s, in, ldi, out, ldo, n, ng, per);
+    else if (n % 4 == 0 && ldi % 4 == 0 && ldo % 4 == 0 && (uintptr_t)in % 4 == 0 && (uintptr_t)out % 16 == 0) group_rows_launch<uint8_t, 4>(s, in, ldi, out, ldo, n, ng, per);
+    else group_rows_launch<uint8_t, 1>(s, in, ldi, out, ldo, n, ng, per);
+}
+void group_rows_f32(hipStream_t s, const float* in, int64_t ldi, float* out, int64_t ldo, int64_t n, int ng, int per) {
+    if (rows_aligned(in, ldi, 4, out, ldo, n, 4)) group_rows_launch<float, 4>(s, in, ldi, out, ldo, n, ng, per);
+    else group_rows_launch<float, 1>(s, in, ldi, out, ldo, n, ng, per);
+}
+
+// x[i] += add[i % period] (period, total multiples of 4): ContextAEInception2's `out = decode + tgtctx` over frame-major rows, where
+// the context maps of the ng groups repeat every ng rows (the layer epilogues' add1_mod folds a second row block only)
+__global__ __launch_bounds__(NTHREADS) void add_period_kernel(float* __restrict__ x, const float* __restrict__ add, int64_t period, int64_t total) {
+    for (int64_t i = ((int64_t)blockIdx.x * NTHREADS + threadIdx.x) * 4; i < total; i += (int64_t)gridDim.x * NTHREADS * 4) {
+        float4 v = *reinterpret_cast<float4*>(x + i);
+        const float4 a = ldg4(add + i % period);
+        v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
+        *reinterpret_cast<float4*>(x + i) = v;
+    }
+}
+void add_period(hipStream_t s, float* x, const float* add, int64_t period, int64_t total) {
+    hipLaunchKernelGGL(add_period_kernel, dim3(ew_blocks(total / 4)), dim3(NTHREADS), 0, s, x, add, period, total);
+}
+
+// Row-wise recon cost over frame-major rows r = j * ng + p (frame j of path p; gridDim.x = ng * bs rows):
+//   costs[p * bs + j] = sum_f (means[j][f] - feat[r][f])^2 + scale * sum_e (y[r][e] - x[r][e])^2
+// the feature term formed exactly as reward_cost_kernel forms it; the image term between two per-row tensors (out2 and the frames).
+// One block per row; npi % 4 != 0 takes scalar loads.
+__global__ __launch_bounds__(NTHREADS) void recon_cost_kernel(const float* __restrict__ feat, int ldf, int F, const float* __restrict__ y,
+                                                              const float* __restrict__ x, int64_t npi, const float* __restrict__ means,
+                                                              int ng, float scale, float* __restrict__ costs) {
+    __shared__ float sh[4];
+    const int r = blockIdx.x, j = r / ng, p = r - j * ng, bs = (int)gridDim.x / ng;
+    float cf = 0.f, ci = 0.f;
+    {
+        const float* a = means + (int64_t)j * F;
+        const float* b = feat + (int64_t)r * ldf;
+        for (int f = threadIdx.x; f < F; f += NTHREADS) { const float d = a[f] - b[f]; cf += d * d; }
+    }
+    const float* a = y + (int64_t)r * npi;
+    const float* b = x + (int64_t)r * npi;
+    if (npi % 4 == 0) {
+        for (int64_t e = (int64_t)threadIdx.x * 4; e < npi; e += NTHREADS * 4) {
+            const float4 u = ldg4(a + e), v = ldg4(b + e);
+            const float d0 = u.x - v.x, d1 = u.y - v.y, d2 = u.z - v.z, d3 = u.w - v.w;
+            ci += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
+        }
+    } else {
+        for (int64_t e = threadIdx.x; e < npi; e += NTHREADS) { const float d = a[e] - b[e]; ci += d * d; }
+    }
+    const float rf = block_sum(cf, sh), ri = block_sum(ci, sh);
+    if (threadIdx.x == 0) costs[(int64_t)p * bs + j] = rf + scale * ri;
+}
+
+// The split form (frames of >= RC_SPLIT_MIN_NPI elements, npi % 4 == 0): one block per (row, RC_SLICE slice), summation order of
+// reward_cost_split_kernel (two alternating accumulators per thread, a0 + a1, the wavefront tree, the 4 wave sums in order), then the
+// slices in order -- fixed, independent of the grid.  Both operands belong to the row, so consecutive blocks walk one row's slices.
+__global__ __launch_bounds__(NTHREADS) void recon_cost_split_kernel(const float* __restrict__ y, const float* __restrict__ x, int64_t npi, int nsl,
+                                                                    float* __restrict__ part) {
+    __shared__ float sh[4];
+    const int r = (int)(blockIdx.x / (unsigned)nsl), sl = (int)(blockIdx.x % (unsigned)nsl);
+    const int64_t e0 = (int64_t)sl * RC_SLICE, e1 = e0 + RC_SLICE < npi ? e0 + RC_SLICE : npi;
+    const float* a = y + (int64_t)r * npi;
+    const float* b = x + (int64_t)r * npi;
+    constexpr int U = RC_SLICE / (4 * NTHREADS);
+    float4 u[U], v[U];
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+        const int64_t e = e0 + ((int64_t)i * NTHREADS + threadIdx.x) * 4;
+        const bool in = e < e1;
+        u[i] = in ? ldg4(a + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+        v[i] = in ? ldg4(b + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    float acc[2] = {0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+        const float d0 = u[i].x - v[i].x, d1 = u[i].y - v[i].y, d2 = u[i].z - v[i].z, d3 = u[i].w - v[i].w;
+        acc[i & 1] += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
+    }
+    const float rs = block_sum(acc[0] + acc[1], sh);
+    if (threadIdx.x == 0) part[(int64_t)r * nsl + sl] = rs;
+}
+
+__global__ __launch_bounds__(NTHREADS) void recon_cost_final_kernel(const float* __restrict__ feat, int ldf, int F, const float* __restrict__ means,
+                                                                    const float* __restrict__ part, int nsl, int ng, float scale,
+                                                                    float* __restrict__ costs) {
+    __shared__ float sh[4];
+    const int r = blockIdx.x, j = r / ng, p = r - j * ng, bs = (int)gridDim.x / ng;
+    float cf = 0.f;
+    const float* a = means + (int64_t)j * F;
+    const float* b = feat + (int64_t)r * ldf;
+    for (int f = threadIdx.x; f < F; f += NTHREADS) { const float d = a[f] - b[f]; cf += d * d; }
+    const float rf = block_sum(cf, sh);
+    if (threadIdx.x == 0) {
+        float ri = 0.f;
+        for (int s = 0; s < nsl; ++s) ri += part[(int64_t)r * nsl + s];
+        costs[(int64_t)p * bs + j] = rf + scale * ri;
+    }
+}
+
+void recon_costs(hipStream_t s, const float* feat, int ldf, int F, const float* y, const float* x, int64_t npi, const float* means,
+                 int bs, int ng, float scale, float* costs, float* part) {
+    const unsigned rows = (unsigned)(bs * ng);
+    if (part && npi % 4 == 0) {
+        const int nsl = reward_costs_slices(npi);
+        hipLaunchKernelGGL(recon_cost_split_kernel, dim3(rows * (unsigned)nsl), dim3(NTHREADS), 0, s, y, x, npi, nsl, part);
+        hipLaunchKernelGGL(recon_cost_final_kernel, dim3(rows), dim3(NTHREADS), 0, s, feat, ldf, F, means, (const float*)part, nsl, ng, scale, costs);
+        return;
+    }
+    hipLaunchKernelGGL(recon_cost_kernel, dim3(rows), dim3(NTHREADS), 0, s, feat, ldf, F, y, x, npi, means, ng, scale, costs);
+}
+
+// ------------------------------------------------------------------------------------------------
 // The demo cache of the reward hook built where the translated videos already are (rllab/sampler/base.py:195-223):
 //   acc[j][e] += sum_v x[(v * bs + j) * ld + e]   (e < cols; videos v in index order, in float64 -- np.mean's accumulation of the
 //   host path, reward.py), then  out = f32(acc / n).  One pass over x, no atomics: an accumulator element belongs to one thread.

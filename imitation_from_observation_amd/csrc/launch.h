@@ -222,6 +222,17 @@ int reward_costs_slices(int64_t npi);
 void reward_costs(hipStream_t s, const float* feat, int ldf, int F, const float* x, int64_t npi, const float* means, const float* imgs,
                   int bs, int nframes, float scale, int ablation, float* costs, float* part = nullptr);
 
+// the 'recon' ablation (base.py:250-252, image_recon = model.out2) on frame-major rows r = j * ng + p (frame j of path p):
+// group_rows_*: out row (r % per) * ng + r / per = in row r for r < ng * per (n elements per row, strides ldi / ldo; path-major ->
+// frame-major; with ng and per exchanged, back), uint8 through prep_u8's three f32 operations; add_period: x[i] += add[i % period];
+// recon_costs: costs[p * bs + j] = |means[j] - feat[r]|^2 + scale * |y[r] - x[r]|^2 -- part (nullable, bs * ng *
+// reward_costs_slices(npi) floats) selects the split form as in reward_costs.
+void group_rows_u8(hipStream_t s, const uint8_t* in, int64_t ldi, float* out, int64_t ldo, int64_t n, int ng, int per);
+void group_rows_f32(hipStream_t s, const float* in, int64_t ldi, float* out, int64_t ldo, int64_t n, int ng, int per);
+void add_period(hipStream_t s, float* x, const float* add, int64_t period, int64_t total);
+void recon_costs(hipStream_t s, const float* feat, int ldf, int F, const float* y, const float* x, int64_t npi, const float* means,
+                 int bs, int ng, float scale, float* costs, float* part = nullptr);
+
 // the reward hook's demo cache on the device (base.py:195-223): acc[j][e] += sum over the nvid videos of x[(v * bs + j) * ld + e]
 // (e < cols, float64, video order), out = f32(acc / count); bcast_row0: rows 1.. of buf [rows][n] = row 0.  cols, ld, n: multiples of 4.
 void cache_accum(hipStream_t s, const float* x, int64_t ld, int64_t cols, int bs, int nvid, double* acc);

@@ -78,6 +78,25 @@ class InceptionTranslator:
         d = self.front.features_u8_dev(fr)
         return self.tr.reward_costs_dev(vp, d, fr.shape[0] // bs, scale, ablation_type)
 
+    def reconstruct(self, frames, ctx0=None, nctx=1):
+        """(out2, input_z) of the feed [frames, ctx, frames] on uint8 frames [B,H,W,3] (Translator.reconstruct): frames (and explicit
+        contexts [nctx,H,W,3]) through the front end in one pass, the translator on its output buffer; out2 is a feature map here."""
+        fr = np.asarray(frames)
+        B = fr.shape[0]
+        if ctx0 is None:
+            return self.tr.reconstruct_dev(self.front.features_u8_dev(fr), B, None, nctx)
+        d = self.front.features_u8_dev(np.concatenate([fr, np.asarray(ctx0)]))
+        return self.tr.reconstruct_dev(d, B, d + B * self._per, nctx)
+
+    def reward_costs_recon_u8(self, vp, frames, scale):
+        """uint8 frames [npaths*bs,H,W,3] -> costs f32 [npaths, bs] of the 'recon' ablation (Translator.reward_costs_recon): front end,
+        then encoder, decoder pass 2 and the row-wise cost on its output buffer.  Only the costs come back."""
+        fr = np.asarray(frames)
+        bs = self.tr._reward_bs
+        if fr.shape[0] % bs:
+            raise ValueError(f"frames must be [npaths*{bs},H,W,3], got {fr.shape}")
+        return self.tr.reward_costs_recon_dev(vp, self.front.features_u8_dev(fr), fr.shape[0] // bs, scale)
+
     def reward_cache_begin(self, vp, bs):
         self.tr.reward_cache_begin(vp, bs)
 

@@ -45,7 +45,8 @@ class _ResidentCacheView:
 
 
 class TranslatorReward:
-    def __init__(self, translator, nvp, scale, name="strike", ablation_type="None", batch_size=25, resident=False, render_size=None):
+    def __init__(self, translator, nvp, scale, name="strike", ablation_type="None", batch_size=25, resident=False, render_size=None,
+                 image_recon=None):
         """resident=True: demo cache and cost stay on the device for EVERY translator type (mode 'oursinception' included) -- the cache
         is built there (reward_cache_begin / _add / _finish: neither the translated videos nor the finished cache cross PCIe), the
         per-path cost is computed next to the encoder (reward_costs_u8: only [paths, bs] floats come back), and `means` / `imgs` are
@@ -54,10 +55,23 @@ class TranslatorReward:
         translator's size itself (scipy.misc.imresize of the environments, on the device: resize.FrameResizer on the translator's
         stream).  Per launch group the raw frames go up once, are resized into f32 where the encoder reads them and go through the
         device cost entry; only the [paths, bs] costs come back.  The costs equal, bit for bit, those of a hook without render_size
-        fed the same frames resized on the host.  None (default): frames arrive at the translator's size, as before."""
-        if ablation_type not in ("None", "nofeat", "noimage"):
-            # 'recon' reads an undefined `image_recon` in the reference (base.py:250-252; SURVEY.md 3.4-f)
+        fed the same frames resized on the host.  None (default): frames arrive at the translator's size, as before.
+        ablation_type="recon" with image_recon="out2": cost_j = sum((means[vp][j] - input_z[j])^2) + scale * sum((out2[j] -
+        image_trans[0][j])^2), out2 = the path's frames reconstructed in the context of the path's first frame (Translator.reconstruct);
+        the reconstruction error replaces the distance to the translated demo frames.  Overwrites per viewpoint like the other
+        ablations; the feature term still needs the demo cache."""
+        if image_recon is not None and ablation_type != "recon":
+            raise ValueError("image_recon names the tensor of ablation_type='recon' only")
+        if ablation_type == "recon" and image_recon is not None:
+            # the launchers' ours_recon (run_trpo_strike.py:87, run_trpo_throw.py:77).  base.py:250-252 reads `image_recon`, which is never
+            # assigned; the trainer's __<k>recon.gif = test.out2 (train_script.py:193-195) and the commented base.py:238-241 (image_recon[j]
+            # saved next to image_trans[0][j] of the same sess.run) say it was model.out2 of the per-path feed.  The caller names it.
+            if image_recon != "out2":
+                raise ValueError(f"image_recon={image_recon!r}: 'out2' (model.out2 of the per-path feed) is the only tensor offered")
+        elif ablation_type not in ("None", "nofeat", "noimage"):
+            # 'recon' reads an undefined `image_recon` in the reference (base.py:250-252; SURVEY.md 3.4-f): image_recon="out2" names it
             raise NotImplementedError(f"ablation_type {ablation_type!r} is not runnable in the reference either")
+        self.image_recon = image_recon
         self.tr, self.nvp, self.scale, self.name = translator, int(nvp), float(scale), name
         self.ablation_type, self.batch_size = ablation_type, int(batch_size)
         self.skip = 2 if name in ("real", "sweep") else 1        # base.py:209-211
@@ -94,7 +108,8 @@ class TranslatorReward:
 
     @classmethod
     def for_sampler(cls, name, imsize, nvp, scale, modelname=None, ablation_type="None", batch_size=25,
-                    paths_per_launch=10, device=0, mode="ours", inception_ckpt=None, resident=False, render_size=None, precision=None):
+                    paths_per_launch=10, device=0, mode="ours", inception_ckpt=None, resident=False, render_size=None, precision=None,
+                    image_recon=None):
         """What BaseSampler.initialize() sets up for mode 'ours' (base.py:113-145): the model class follows the
         experiment name -- ContextAEReal for 'real'/'sweep', ContextSkipNew otherwise (:134-137) -- on the
         sampler's imsize, restored from `modelname` when given (:138).  mode 'oursinception' (:121-132): frames go
@@ -110,13 +125,14 @@ class TranslatorReward:
             if modelname is not None:
                 it.tr.load(modelname)
             return cls(it, nvp, scale, name=name, ablation_type=ablation_type, batch_size=batch_size, resident=resident,
-                       render_size=render_size)
+                       render_size=render_size, image_recon=image_recon)
         real = name in ("real", "sweep")
         tr = Translator(imsize[0], imsize[1], featsize=100 if real else 1024, max_batch=batch_size * paths_per_launch,
                         device=device, variant="real" if real else "skipnew", precision=precision)
         if modelname is not None:
             tr.load(modelname)
-        return cls(tr, nvp, scale, name=name, ablation_type=ablation_type, batch_size=batch_size, resident=resident, render_size=render_size)
+        return cls(tr, nvp, scale, name=name, ablation_type=ablation_type, batch_size=batch_size, resident=resident, render_size=render_size,
+                   image_recon=image_recon)
 
     # ------------------------------------------------------------------ base.py:195-223
     @staticmethod
@@ -290,6 +306,8 @@ class TranslatorReward:
         """costs [npaths, bs] of viewpoint vp for the uint8 frames [npaths * bs, ...] of one launch group, by the first route the
         hook and its translator allow."""
         tr, how = self.tr, (self.scale, self.ablation_type)
+        if self.ablation_type == "recon":
+            return self._group_costs_recon(vp, u8, npaths)
         if self.render_size is not None:
             rs = self._render.resizer()
             if hasattr(tr, "front") and self.resident:
@@ -310,6 +328,33 @@ class TranslatorReward:
         feats, x = tr.encode(u8)                                           # [input_z, image_trans[0]], base.py:234-235
         bs = self.batch_size
         return np.stack([self._costs_from(feats[k * bs:(k + 1) * bs], x[k * bs:(k + 1) * bs], vp) for k in range(npaths)])
+
+    def _group_costs_recon(self, vp, u8, npaths):
+        """_group_costs for ablation_type='recon' (image_recon = out2), by the same routes in the same order."""
+        tr = self.tr
+        if self.render_size is not None:
+            rs = self._render.resizer()
+            if hasattr(tr, "front") and self.resident:
+                maps = tr.front.features_dev(rs.resize_dev(u8), u8.shape[0])
+                return tr.tr.reward_costs_recon_dev(vp, maps, npaths, self.scale)
+            if not hasattr(tr, "front") and hasattr(tr, "reward_costs_recon_dev"):
+                slot = tr.dev_frames(u8.shape[0])[0]
+                return tr.reward_costs_recon_dev(vp, rs.resize_dev(u8, dst=slot), npaths, self.scale)
+            u8 = rs.resize(u8)
+        if self.resident:
+            return tr.reward_costs_recon_u8(vp, u8, self.scale)
+        if hasattr(tr, "reward_costs_recon"):
+            return tr.reward_costs_recon(vp, u8, self.scale)
+        # [input_z, out2] of base.py:234-235, every path in the context of its own first frame; image_trans[0] on the host
+        recon, feats = tr.reconstruct(u8, None, npaths)
+        if hasattr(tr, "front"):
+            x = tr.encode(u8)[1]                                           # mode 'oursinception': image_trans IS the feature tensor (base.py:132)
+        else:
+            x = ((u8.astype(np.float32) * np.float32(1.0 / 255.0)) - np.float32(0.5)) * np.float32(2.0)  # base.py:116-119, three f32 operations
+        bs = self.batch_size
+        cf = np.sum((self.means[vp][None] - np.reshape(feats, (npaths, bs, -1))) ** 2, axis=2)
+        ci = self.scale * np.sum(np.reshape(recon - x, (npaths, bs, -1)) ** 2, axis=2)
+        return cf + ci
 
     # ------------------------------------------------------------------ base.py:256-257
     def process_paths(self, paths, distributed=False):

@@ -396,6 +396,66 @@ class Translator:
         """The resident reward hook's cost call on uint8 frames (TranslatorReward(resident=True)): reward_costs."""
         return self.reward_costs(vp, frames, scale, ablation_type)
 
+    # ------------------------------------------------------------------ the 'recon' ablation (base.py:250-252, image_recon = model.out2)
+    def _recon_args(self, B, nctx):
+        nctx = int(nctx)
+        if nctx < 1 or nctx > B or B % nctx:
+            raise ValueError(f"nctx={nctx} must lie in [1, B={B}] and divide B")
+        return nctx, np.empty((B, self.H, self.W, self.C), np.float32), np.empty((B, self.featsize), np.float32)
+
+    def reconstruct(self, frames, ctx0=None, nctx=1):
+        """(out2, input_z) of the feed [frames, ctx, frames] (base.py:234-235 with model.out2 fetched): frames uint8 [B,H,W,3] in nctx
+        groups of B/nctx rows, row r decoded with the skips of context r // (B/nctx).  ctx0 uint8 [nctx,H,W,3], or None = the first
+        frame of each group (`[curimgs[0]] * batch_size`).  Returns (recon f32 [B,H,W,3], feat f32 [B,featsize])."""
+        fr = _u8(frames)
+        if fr.ndim != 4 or fr.shape[1:] != (self.H, self.W, 3):
+            raise ValueError(f"frames must be [B,{self.H},{self.W},3], got {fr.shape}")
+        B = fr.shape[0]
+        nctx, recon, feat = self._recon_args(B, nctx)
+        c0 = None if ctx0 is None else _u8(ctx0, (nctx, self.H, self.W, 3))
+        self._ck(self._lib.ctx_reconstruct(self._h, _up(fr), None if c0 is None else _up(c0), nctx, B, _fp(recon), _fp(feat)))
+        return recon, feat
+
+    def reconstruct_f32(self, frames, ctx0=None, nctx=1):
+        """reconstruct() on float inputs [B,H,W,C]: frames in [-1,1] or, for variant "inception2", feature maps."""
+        fr = _f32(frames)
+        B = fr.shape[0]
+        fr = _f32(fr, (B, self.H, self.W, self.C))
+        nctx, recon, feat = self._recon_args(B, nctx)
+        c0 = None if ctx0 is None else _f32(ctx0, (nctx, self.H, self.W, self.C))
+        self._ck(self._lib.ctx_reconstruct_f32(self._h, _fp(fr), None if c0 is None else _fp(c0), nctx, B, _fp(recon), _fp(feat)))
+        return recon, feat
+
+    def reconstruct_dev(self, d_frames, B, d_ctx0=None, nctx=1):
+        """reconstruct_f32 on DEVICE inputs (integer addresses of f32 [B,H,W,C] and, or None, [nctx,H,W,C]); host results."""
+        nctx, recon, feat = self._recon_args(int(B), nctx)
+        self._ck(self._lib.ctx_reconstruct_dev(self._h, ctypes.c_void_p(d_frames), ctypes.c_void_p(d_ctx0) if d_ctx0 else None, nctx, int(B),
+                                               _fp(recon), _fp(feat)))
+        return recon, feat
+
+    def reward_costs_recon(self, vp, frames, scale):
+        """frames uint8 [npaths*bs,H,W,3] -> costs f32 [npaths, bs] of the 'recon' ablation: sum((means[j] - input_z[p,j])^2) +
+        scale * sum((out2[p,j] - image_trans[0][p,j])^2), every path reconstructed in the context of its own first frame; only the
+        costs come back."""
+        fr = _u8(frames)
+        bs = self._reward_bs
+        if fr.ndim != 4 or fr.shape[1:] != (self.H, self.W, 3) or fr.shape[0] % bs:
+            raise ValueError(f"frames must be [npaths*{bs},{self.H},{self.W},3], got {fr.shape}")
+        costs = np.empty((fr.shape[0] // bs, bs), np.float32)
+        self._ck(self._lib.ctx_reward_costs_recon(self._h, int(vp), _up(fr), fr.shape[0] // bs, float(scale), _fp(costs)))
+        return costs
+
+    def reward_costs_recon_dev(self, vp, d_frames, npaths, scale):
+        """reward_costs_recon on frames that are on the device already (integer address of f32 [npaths*bs,H,W,C], complete in this
+        handle's stream order).  costs f32 [npaths, bs]."""
+        costs = np.empty((int(npaths), self._reward_bs), np.float32)
+        self._ck(self._lib.ctx_reward_costs_recon_dev(self._h, int(vp), ctypes.c_void_p(d_frames), int(npaths), float(scale), _fp(costs)))
+        return costs
+
+    def reward_costs_recon_u8(self, vp, frames, scale):
+        """The resident reward hook's 'recon' cost call on uint8 frames: reward_costs_recon."""
+        return self.reward_costs_recon(vp, frames, scale)
+
     def reward_cache_begin(self, vp, bs):
         """Start the demo cache of viewpoint vp ON THE DEVICE (base.py:195-223): zeroed float64 sums [bs, featsize], [bs,H,W,C]."""
         self._ck(self._lib.ctx_reward_cache_begin(self._h, int(vp), int(bs)))

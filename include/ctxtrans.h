@@ -49,7 +49,8 @@ extern "C" {
                                CTX_CNN_AVGPOOL_VALID / CTX_CNN_CONV_LINEAR, ctx_cnn_stats_*, ctx_cnn_reward_*; ctx_nn_err,
                                ctx_dp_nn_err, ctx_cnn_demos_upload, ctx_cnn_forward_sampled_dev; ctx_reward_costs_dev, ctx_reward_cache_*,
                                ctx_reward_get_cache, ctx_reward_stats, option reward_split; ctx_resize_*; the device-uint8 forms
-                               ctx_resize_u8_dev / _v, ctx_cnn_*_dev_u8, ctx_disc_stream / _data_begin / _reward_paths_dev */
+                               ctx_resize_u8_dev / _v, ctx_cnn_*_dev_u8, ctx_disc_stream / _data_begin / _reward_paths_dev;
+                               ctx_reconstruct / _f32 / _dev, ctx_reward_costs_recon / _dev */
 
 enum {
     CTX_OK = 0,
@@ -270,6 +271,26 @@ int ctx_reward_costs(ctx_handle* h, int vp, const uint8_t* frames, int npaths, f
  * Frames of >= 32768 elements (8x8x2048 maps at 299 x 299: 131072) take a split cost kernel -- one block per (frame, 8192-element
  * slice), the slices then added in order; smaller frames the one-block-per-frame kernel, in both entries. */
 int ctx_reward_costs_dev(ctx_handle* h, int vp, const float* d_frames, int npaths, float scale, int ablation, float* costs);
+
+/* The 'recon' ablation (launchers' ours_recon: ablation_type='recon'; base.py:250-252).  Its cost reads `image_recon`, which the reference
+ * never assigns; its trainer and the commented lines base.py:238-241 say what it was: model.out2 of the per-path feed
+ * [curimgs, [curimgs[0]]*bs, curimgs] -- the path's own frames through the `conv` encoder, decoded with the skips of the path's first
+ * frame.
+ * ctx_reconstruct*: out2 / input_z of the feed [frames, ctx, frames] (base.py:234-235 with the model's out2 fetched):
+ *   frames [B,H,W,C]; nctx >= 1 divides B; row r uses context r / (B/nctx); ctx0 [nctx,H,W,C], or NULL = the first frame of each group
+ *   ([curimgs[0]]*bs).  recon [B,H,W,C], feat [B,featsize]; either nullable.  Each context is encoded once; the translate MLP and
+ *   decoder pass 1 do not run.  _f32: frames in [-1,1] / feature maps on the host; _dev: on the device (stream contract of
+ *   ctx_encode_dev); results are HOST buffers.  The uint8 entry is refused for CTX_VARIANT_INCEPTION2 like the others.
+ *   B % nctx != 0 or nctx outside [1, B]: CTX_E_INVALID.
+ * ctx_reward_costs_recon*: costs[p*bs+j] = sum((means[j]-input_z[p,j])^2) + scale*sum((out2[p,j]-image_trans[0][p,j])^2), context =
+ *   frame 0 of path p; only npaths*bs floats come back.  The feature term needs the viewpoint's demo cache (means): CTX_E_STATE before
+ *   one exists.  One block per frame, or -- frames of >= 32768 elements, option reward_split as for ctx_reward_costs -- the split form;
+ *   counted by ctx_reward_stats like any other cost call. */
+int ctx_reconstruct(ctx_handle* h, const uint8_t* frames, const uint8_t* ctx0, int nctx, int B, float* recon, float* feat);
+int ctx_reconstruct_f32(ctx_handle* h, const float* frames, const float* ctx0, int nctx, int B, float* recon, float* feat);
+int ctx_reconstruct_dev(ctx_handle* h, const float* d_frames, const float* d_ctx0, int nctx, int B, float* recon, float* feat);
+int ctx_reward_costs_recon(ctx_handle* h, int vp, const uint8_t* frames, int npaths, float scale, float* costs);
+int ctx_reward_costs_recon_dev(ctx_handle* h, int vp, const float* d_frames, int npaths, float scale, float* costs);
 
 /* The demo cache built on the device (base.py:195-223: translate every demo video into the rollout's context, np.mean over the
  * videos of translated_z and out) -- neither the translated frames / maps nor the finished cache cross PCIe:
