@@ -24,6 +24,7 @@
 #include <cstdlib>
 
 #include "launch.h"
+#include "trace.h"
 
 namespace ctx {
 
@@ -232,6 +233,7 @@ void launch_c3(hipStream_t s, C3P P) {
     int grid = dev_info().cus * per_cu;
     if (grid > P.ntiles) grid = P.ntiles;
     { const int rounds = (P.ntiles + grid - 1) / grid; grid = (P.ntiles + rounds - 1) / rounds; }     // whole rounds of tiles per block
+    trace_launch("c3conv | S %d NB %d TWB %d hin %d win %d ntiles %d grid %d nimg %d", S, NB, TWB, P.hin, P.win, P.ntiles, grid, P.nimg);
     hipLaunchKernelGGL((c3conv_kernel<S, NB, TWB>), dim3((unsigned)grid), dim3(C3_THREADS), lds, s, P);
 }
 

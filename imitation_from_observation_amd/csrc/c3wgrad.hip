@@ -20,6 +20,7 @@
 #include <cstdlib>
 
 #include "launch.h"
+#include "trace.h"
 
 namespace ctx {
 
@@ -218,6 +219,8 @@ void launch_w3(hipStream_t s, W3P P, int ngroups) {
     constexpr size_t red_b = (size_t)2 * W3_RB * NB * 256 * sizeof(float);
     constexpr size_t lds = tiles_b > red_b ? tiles_b : red_b;
     ensure_dyn_lds((const void*)c3wgrad_kernel<S, NB, TWB>, lds);
+    trace_launch("c3wgrad | S %d NB %d TWB %d two %d nmod2 %d hs %d ws %d ntiles %d nbl %d ngroups %d nimg %d", S, NB, TWB, P.s2 ? 1 : 0, P.nmod2, P.hs, P.ws, P.ntiles, P.nbl,
+                 ngroups, P.nimg);
     hipLaunchKernelGGL((c3wgrad_kernel<S, NB, TWB>), dim3((unsigned)(P.nbl * ngroups)), dim3(W3_THREADS), lds, s, P);
 }
 

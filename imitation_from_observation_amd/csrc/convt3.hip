@@ -20,6 +20,7 @@
 #include <cstdlib>
 
 #include "launch.h"
+#include "trace.h"
 
 namespace ctx {
 
@@ -247,6 +248,8 @@ void launch_ct3(hipStream_t s, Ct3 A, int TW) {
     int grid = 256 * per_cu;
     if (grid > A.ntiles) grid = A.ntiles;
     { const int rounds = (A.ntiles + grid - 1) / grid; grid = (A.ntiles + rounds - 1) / rounds; }
+    trace_launch("convt3 | form valu S %d P %d NT %d TW %d c1 %d c2 %d nmod2 %d hin %d win %d ntiles %d grid %d nimg %d", S, P, NT, TW, A.c1, A.c2, A.nmod2, A.hin, A.win,
+                 A.ntiles, grid, A.nimg);
     hipLaunchKernelGGL((convt3_kernel<S, P, NT>), dim3((unsigned)grid), dim3(NT), lds, s, A);
 }
 

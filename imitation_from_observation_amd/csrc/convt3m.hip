@@ -25,6 +25,7 @@
 
 #include "launch.h"
 #include "options.h"
+#include "trace.h"
 
 namespace ctx {
 
@@ -281,6 +282,7 @@ bool launch_ct3m(hipStream_t s, Ct3m A) {
     int grid = dev_info().cus;
     if (grid > A.nimg) grid = A.nimg;
     { const int rounds = (A.nimg + grid - 1) / grid; grid = (A.nimg + rounds - 1) / rounds; }
+    trace_launch("convt3 | form mfma S %d KQH %d nmod2 %d hin %d win %d grid %d rounds %d nimg %d", S, KQH, A.nmod2, A.hin, A.win, grid, (A.nimg + grid - 1) / grid, A.nimg);
     hipLaunchKernelGGL((convt3m_kernel<S, KQH, NWM, NWG>), dim3((unsigned)grid), dim3((NWM + NWG) * 64), lds, s, A);
     return true;
 }

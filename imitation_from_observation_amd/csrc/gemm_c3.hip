@@ -1,5 +1,6 @@
 // the 3-channel edge layers: cin = 3 conv and the cout = 3 transposed conv as a product + gather
 #include "gemm_launch.h"
+#include "trace.h"
 namespace ctx {
 void convt3_product(hipStream_t s, const KmCat2& a, const float* w, int cb, float* P, int M, SplitWs ws) {
     // B[k][n] = w[ky,kx,c,k] with n = (ky*5+kx)*3+c: the filter itself, rows n contiguous in k
@@ -10,6 +11,7 @@ void convt3_product(hipStream_t s, const KmCat2& a, const float* w, int cb, floa
 }
 // the same product for a transposed conv to `ca` output channels: P[pixel][(ky*5+kx)*ca + c] (convt_gather adds the taps of an output pixel)
 void convt_product(hipStream_t s, const KmCat2& a, const float* w, int cb, int ca, float* P, int M, SplitWs ws) {
+    trace_launch("convt_product | M %d N %d cb %d ca %d", M, 25 * ca, cb, ca);
     KmPlain b{w, cb, nullptr, 0, cb, 25 * ca, cb / KC, a.zeros};
     Epi ep;
     ep.out1 = P; ep.ld1 = 25 * ca;

@@ -29,7 +29,7 @@ enum Opt {
     OPT_CNN_DCONV,     // Inception front end, f32: 1 = layers of <= 32 input and output channels (Conv2d_2a_3x3) on the direct kernels of dconv.h;
                        // 0 = implicit GEMM
     OPT_CNN_STEM4,     // 1: the front end's 3-channel first conv on the 4-channel gather
-    OPT_TRACE_LAUNCH,  // 1: one stderr line per distinct implicit-GEMM launch shape (diagnostics)
+    OPT_TRACE_LAUNCH,  // 1: one stderr line per distinct launch of the implicit GEMM (gemm_launch.h) and of the launchers that use trace.h (diagnostics)
     OPT_ADAM_PRIO,     // HIP priority of the early-Adam stream, read at create: 1 low (its own hardware queue), 0 normal, -1 high; 2 (default) = 1 for
                        // exact-f32 handles, 0 for split-bf16 ones; reads back resolved
     OPT_REWARD_SPLIT,  // the reward hook's cost on frames of a multiple of 4 elements: -1 (default) = the split kernel from 32768 elements per frame

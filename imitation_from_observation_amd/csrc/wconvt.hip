@@ -22,6 +22,7 @@
 #include <cstdlib>
 
 #include "launch.h"
+#include "trace.h"
 
 namespace ctx {
 
@@ -560,6 +561,8 @@ void launch_wr(hipStream_t s, WcT P) {
     P.gn = P.ca / G::COLS;
     const int nig = (P.nimg + G::IMGT - 1) / G::IMGT;
     const int items = (nig + 7) / 8 * 8 * HS * P.gn;
+    trace_launch("wconvt | form wr HS %d WS %d PB %d XS %d ks 1 nimg %d imgt %d c1 %d c2 %d nmod2 %d ca %d blocks %d", HS, WS, PB, (int)XS, P.nimg, G::IMGT, P.c1, P.c2,
+                 P.nmod2, P.ca, items);
     ensure_dyn_lds((const void*)wconvt_row_kernel<HS, WS, PB, XS>, G::lds);
     hipLaunchKernelGGL((wconvt_row_kernel<HS, WS, PB, XS>), dim3((unsigned)items), dim3(WC_THREADS), G::lds, s, P);
 }
@@ -572,6 +575,8 @@ void launch_wc(hipStream_t s, const WcT& P) {
     static_assert(lds <= 65536, "two blocks per CU");
     const int ntile = ((P.nimg + IMGT - 1) / IMGT) * TPI;
     const int items = (ntile + 7) / 8 * 8 * P.gn * P.ksplit;      // whole groups of 8 tiles: the XCD mapping above
+    trace_launch("wconvt | form wc HS %d WS %d NB %d XS 0 ks %d nimg %d imgt %d c1 %d c2 %d nmod2 %d ca %d blocks %d", HS, WS, NB, P.ksplit, P.nimg, IMGT, P.c1, P.c2,
+                 P.nmod2, P.ca, items);
     hipLaunchKernelGGL((wconvt_kernel<HS, WS, NB>), dim3((unsigned)items), dim3(WC_THREADS), lds, s, P);
 }
 

@@ -191,7 +191,14 @@ const char* ctx_last_error(const ctx_handle* h);
  *   cnn_lanes   -1   Inception front end: branch lanes; -1 = in the split-bf16 mode only      (ctx_cnn handles: environment at create) [fixed at create]
  *   cnn_dconv    1   Inception front end (f32): layers of <= 32 input and output channels on the direct kernels (dconv.h); 0 = implicit GEMM  [fixed at create]
  *   cnn_stem4    1   Inception front end: the 3-channel first conv on the 4-channel gather    (ctx_cnn handles: environment at create) [fixed at create]
- *   trace_launch 0   one stderr line per distinct implicit-GEMM launch shape
+ *   trace_launch 0   one stderr line per distinct launch, `family | key value ...` (diagnostics, and how tests/test_gpu_ragged_routes.py and
+ *                    tests/test_gpu_fp16x3d_ranges.py see which kernel a layer ran).  Families:
+ *                      igemm          M N nprob chunks tile tiles nsplit swz  [loader A x loader B]   (gemm_launch.h: launch_igemm)
+ *                      wconvt         form wc|wr, HS WS, NB (wc) or PB (wr), XS, ks, nimg, imgt = images per tile, c1 c2 nmod2 ca, blocks
+ *                      convt3         form valu (S P NT TW ... ntiles grid nimg) or mfma (S KQH ... grid rounds nimg): d_h4's forward
+ *                      c3conv         S NB TWB hin win ntiles grid nimg;   c3wgrad  S NB TWB two nmod2 hs ws ntiles nbl ngroups nimg
+ *                      convt_product  M N cb ca (the starved inference route; its product is an igemm line as well)
+ *                    One set of seen lines per process; the other launchers (dconv.h, rchain.hip, elementwise) print nothing.
  *   adam_prio    2   HIP priority of the early-Adam stream (1 low: its own hardware queue; 0 normal; -1 high; 2 = low for exact-f32 handles,
  *                    normal for split-bf16 ones, reads back resolved)  [fixed at create]
  *   reward_split -1  the reward hook's image term (ctx_reward_costs / ctx_reward_costs_dev): -1 = the split kernel for frames of >= 32768

@@ -8,8 +8,10 @@ elements before its backward pass runs.  Returns the number of aligned elements.
 import numpy as np
 
 
-def align_skipnew_cache(tr, c, B):
-    """tr: Translator that has just run a forward on the same inputs; c: oracle cache from ctx_oracle.forward."""
+def align_skipnew_cache(tr, c, B, undo=None):
+    """tr: Translator that has just run a forward on the same inputs; c: oracle cache from ctx_oracle.forward.
+    undo: a list that receives (array, flat indices, the values they held) for every edit, so that a caller which shares one
+    oracle cache between several device runs can put it back (restore_cache)."""
     cache_of = {}
     for k in range(5):
         cache_of[f"s{k}"] = [(c["e_tgt"][k], slice(0, B)), (c["e_src"][k], slice(B, 2 * B))]
@@ -29,9 +31,21 @@ def align_skipnew_cache(tr, c, B):
             m = (got[sl] >= 0) != (arr >= 0)
             if m.any():
                 worst = max(worst, float(np.abs(arr[m]).max() / np.abs(arr).max()))
+                if undo is not None:
+                    assert arr.flags.c_contiguous               # restore_cache writes through arr.reshape(-1), which must be a view
+                    undo.append((arr, np.flatnonzero(m), arr[m].copy()))
                 arr[m] = np.where(got[sl][m] >= 0, 1e-300, -1e-300)
                 nflip += int(m.sum())
     return nflip, worst
+
+
+def restore_cache(undo):
+    """Take back the edits align_skipnew_cache recorded in `undo` (latest first); empties the list."""
+    while undo:
+        arr, idx, vals = undo.pop()
+        flat = arr.reshape(-1)
+        assert np.shares_memory(flat, arr)
+        flat[idx] = vals
 
 
 def align_gen_cache(tr, c, B):
