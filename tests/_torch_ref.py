@@ -6,8 +6,49 @@ import torch
 import torch.nn.functional as F
 
 
-def lrelu(x):
-    return torch.maximum(x, 0.2 * x)
+class _LreluOnBranch(torch.autograd.Function):
+    """max(x, 0.2 x) whose backward multiplies by where(mask, 1, 0.2): lrelu differentiated on a GIVEN branch (True = the positive
+    one).  The mask is kept by reference, not saved for backward, so that a caller may rewrite it in place between two backwards of one
+    retained graph (the value does not depend on it)."""
+
+    @staticmethod
+    def forward(ctx, x, mask):
+        ctx.mask = mask
+        return torch.maximum(x, 0.2 * x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return torch.where(ctx.mask, g, g * 0.2), None
+
+
+def lrelu(x, site=None, branches=None):
+    """branches (optional): callable (site, x) -> boolean mask of x's shape, or None for lrelu's own derivative.  site names the lrelu
+    as tests/_align.py's site maps do: ("e_tgt" | "e_src" | "e_ctx", k) for encoder layer k (4 = h4_lin, 5 = hz_lin), ("trans_h0", None),
+    ("d1" | "d2", k) for decoder pass 1 / 2 (0 = d_h0_lin, 1..3 = d_h1..d_h3)."""
+    mask = branches(site, x) if branches is not None else None
+    if mask is None:
+        return torch.maximum(x, 0.2 * x)
+    return _LreluOnBranch.apply(x, mask)
+
+
+class Branches:
+    """A `branches` argument that records every site's pre-activation and differentiates each on a mask of its own, which starts as
+    the site's own signs (x >= 0: the un-hooked derivative, bit for bit, wherever x != 0) and can be rewritten between backwards."""
+
+    def __init__(self):
+        self.x, self.mask, self.calls = {}, {}, []
+
+    def __call__(self, site, x):
+        assert site not in self.x, site
+        self.calls.append(site)
+        self.x[site] = x.detach()
+        self.mask[site] = self.x[site] >= 0
+        return self.mask[site]
+
+    def set(self, masks):
+        """Differentiate on `masks` (site -> boolean tensor) from now on; sites not named go back to their own signs."""
+        for site, own in self.x.items():
+            self.mask[site].copy_(masks[site] if site in masks else own >= 0)
 
 
 def tf_conv(x_nhwc, w_hwio, b):
@@ -28,30 +69,30 @@ def tf_deconv(x_nhwc, w_hwoi, b):
     return y.permute(0, 2, 3, 1)
 
 
-def forward(p, src, ctx, tgt, H, W, gf):
-    def enc(scope, img, z_lrelu):
+def forward(p, src, ctx, tgt, H, W, gf, branches=None):
+    def enc(scope, img, z_lrelu, st):
         acts, h = [], img
         for k in range(4):
-            h = lrelu(tf_conv(h, p[f"{scope}/h{k}_conv/w"], p[f"{scope}/h{k}_conv/biases"]))
+            h = lrelu(tf_conv(h, p[f"{scope}/h{k}_conv/w"], p[f"{scope}/h{k}_conv/biases"]), (st, k), branches)
             acts.append(h)
-        h4 = lrelu(h.reshape(h.shape[0], -1) @ p[f"{scope}/h4_lin/Matrix"] + p[f"{scope}/h4_lin/bias"])
+        h4 = lrelu(h.reshape(h.shape[0], -1) @ p[f"{scope}/h4_lin/Matrix"] + p[f"{scope}/h4_lin/bias"], (st, 4), branches)
         z = h4 @ p[f"{scope}/hz_lin/Matrix"] + p[f"{scope}/hz_lin/bias"]
-        return acts, (lrelu(z) if z_lrelu else z)
+        return acts, (lrelu(z, (st, 5), branches) if z_lrelu else z)
 
-    def dec(z, skips):
-        h = lrelu(z @ p["deconv/d_h0_lin/Matrix"] + p["deconv/d_h0_lin/bias"]).reshape(-1, H // 16, W // 16, 8 * gf)
+    def dec(z, skips, st):
+        h = lrelu(z @ p["deconv/d_h0_lin/Matrix"] + p["deconv/d_h0_lin/bias"], (st, 0), branches).reshape(-1, H // 16, W // 16, 8 * gf)
         for k in range(1, 5):
             h = tf_deconv(torch.cat([h, skips[4 - k]], 3), p[f"deconv/d_h{k}/w"], p[f"deconv/d_h{k}/biases"])
             if k < 4:
-                h = lrelu(h)
+                h = lrelu(h, (st, k), branches)
         return h
 
-    skips, ctx_z = enc("conv_context", ctx, False)
-    _, src_z = enc("conv", src, True)
-    _, tgt_z = enc("conv", tgt, True)
-    th0 = lrelu(torch.cat([src_z, ctx_z], 1) @ p["translate/trans_h0/Matrix"] + p["translate/trans_h0/bias"])
+    skips, ctx_z = enc("conv_context", ctx, False, "e_ctx")
+    _, src_z = enc("conv", src, True, "e_src")
+    _, tgt_z = enc("conv", tgt, True, "e_tgt")
+    th0 = lrelu(torch.cat([src_z, ctx_z], 1) @ p["translate/trans_h0/Matrix"] + p["translate/trans_h0/bias"], ("trans_h0", None), branches)
     trans_z = th0 @ p["translate/trans_z/Matrix"] + p["translate/trans_z/bias"]
-    out, out2 = dec(trans_z, skips), dec(tgt_z, skips)
+    out, out2 = dec(trans_z, skips, "d1"), dec(tgt_z, skips, "d2")
     sim = ((trans_z - tgt_z) ** 2).mean() * 1e3
     r1 = 0.5 * ((tgt - out) ** 2).sum()
     r2 = 0.5 * ((tgt - out2) ** 2).sum()
@@ -76,32 +117,32 @@ def tf_deconv_s(x_nhwc, w_hwoi, b, s):
     return y.permute(0, 2, 3, 1)
 
 
-def forward_real(p, src, ctx, tgt, H, W):
+def forward_real(p, src, ctx, tgt, H, W, branches=None):
     """ContextAEReal (arm_shaping.py:1599-1684), keep_prob = 1."""
     NS = (1, 2, 1, 2)
 
-    def enc(img):
+    def enc(img, st):
         acts, h = [], img
         for k in range(4):
-            h = lrelu(tf_conv_s(h, p[f"conv/h{k}_conv/w"], p[f"conv/h{k}_conv/biases"], NS[k]))
+            h = lrelu(tf_conv_s(h, p[f"conv/h{k}_conv/w"], p[f"conv/h{k}_conv/biases"], NS[k]), (st, k), branches)
             acts.append(h)
-        h4 = lrelu(h.reshape(h.shape[0], -1) @ p["conv/h4_lin/Matrix"] + p["conv/h4_lin/bias"])
-        return acts, lrelu(h4 @ p["conv/hz_lin/Matrix"] + p["conv/hz_lin/bias"])
+        h4 = lrelu(h.reshape(h.shape[0], -1) @ p["conv/h4_lin/Matrix"] + p["conv/h4_lin/bias"], (st, 4), branches)
+        return acts, lrelu(h4 @ p["conv/hz_lin/Matrix"] + p["conv/hz_lin/bias"], (st, 5), branches)
 
-    def dec(z, skips):
-        h = lrelu(z @ p["deconv/d_h0_lin/Matrix"] + p["deconv/d_h0_lin/bias"]).reshape(-1, H // 4, W // 4, 8)
+    def dec(z, skips, st):
+        h = lrelu(z @ p["deconv/d_h0_lin/Matrix"] + p["deconv/d_h0_lin/bias"], (st, 0), branches).reshape(-1, H // 4, W // 4, 8)
         for k in range(1, 5):
             h = tf_deconv_s(torch.cat([h, skips[4 - k]], 3), p[f"deconv/d_h{k}/w"], p[f"deconv/d_h{k}/biases"], NS[4 - k])
             if k < 4:
-                h = lrelu(h)
+                h = lrelu(h, (st, k), branches)
         return h
 
-    _, src_z = enc(src)
-    _, tgt_z = enc(tgt)
-    skips, ctx_z = enc(ctx)
-    th0 = lrelu(torch.cat([src_z, ctx_z], 1) @ p["translate/trans_h0/Matrix"] + p["translate/trans_h0/bias"])
+    _, src_z = enc(src, "e_src")
+    _, tgt_z = enc(tgt, "e_tgt")
+    skips, ctx_z = enc(ctx, "e_ctx")
+    th0 = lrelu(torch.cat([src_z, ctx_z], 1) @ p["translate/trans_h0/Matrix"] + p["translate/trans_h0/bias"], ("trans_h0", None), branches)
     trans_z = th0 @ p["translate/trans_z/Matrix"] + p["translate/trans_z/bias"]
-    out, out2 = dec(trans_z, skips), dec(tgt_z, skips)
+    out, out2 = dec(trans_z, skips, "d1"), dec(tgt_z, skips, "d2")
     sim = ((trans_z - tgt_z) ** 2).mean() * 1e3
     r1 = 0.5 * ((tgt - out) ** 2).sum()
     r2 = 0.5 * ((tgt - out2) ** 2).sum()
@@ -138,36 +179,36 @@ def tf_deconv_ks(x_nhwc, w_hwoi, b, out_hw, s):
     return y.permute(0, 2, 3, 1)
 
 
-def forward_incep2(p, src, ctx, tgt, H, W, strides, filters):
+def forward_incep2(p, src, ctx, tgt, H, W, strides, filters, branches=None):
     """arm_shaping.py:1792-1894 through torch ops + autograd."""
     sizes, h, w = [], H, W
     for s in strides:
         h, w = -(-h // s), -(-w // s)
         sizes.append((h, w))
 
-    def enc(scope, img):
+    def enc(scope, img, st):
         acts, hh = [], img
         for k in range(4):
-            hh = lrelu(tf_conv_ks(hh, p[f"{scope}/h{k}_conv/w"], p[f"{scope}/h{k}_conv/biases"], strides[k]))
+            hh = lrelu(tf_conv_ks(hh, p[f"{scope}/h{k}_conv/w"], p[f"{scope}/h{k}_conv/biases"], strides[k]), (st, k), branches)
             acts.append(hh)
-        h4 = lrelu(hh.reshape(hh.shape[0], -1) @ p[f"{scope}/h4_lin/Matrix"] + p[f"{scope}/h4_lin/bias"])
-        return acts, lrelu(h4 @ p[f"{scope}/hz_lin/Matrix"] + p[f"{scope}/hz_lin/bias"])
+        h4 = lrelu(hh.reshape(hh.shape[0], -1) @ p[f"{scope}/h4_lin/Matrix"] + p[f"{scope}/h4_lin/bias"], (st, 4), branches)
+        return acts, lrelu(h4 @ p[f"{scope}/hz_lin/Matrix"] + p[f"{scope}/hz_lin/bias"], (st, 5), branches)
 
-    def dec(z, skips):
-        hh = lrelu(z @ p["deconv/d_h0_lin/Matrix"] + p["deconv/d_h0_lin/bias"]).reshape(-1, sizes[3][0], sizes[3][1], filters[3])
+    def dec(z, skips, st):
+        hh = lrelu(z @ p["deconv/d_h0_lin/Matrix"] + p["deconv/d_h0_lin/bias"], (st, 0), branches).reshape(-1, sizes[3][0], sizes[3][1], filters[3])
         outs = [sizes[2], sizes[1], sizes[0], (H, W)]
         for k in range(1, 5):
             hh = tf_deconv_ks(torch.cat([hh, skips[4 - k]], 3), p[f"deconv/d_h{k}/w"], p[f"deconv/d_h{k}/biases"], outs[k - 1], strides[4 - k])
             if k < 4:
-                hh = lrelu(hh)
+                hh = lrelu(hh, (st, k), branches)
         return hh
 
-    skips, ctx_z = enc("conv_context", ctx)
-    _, src_z = enc("conv", src)
-    _, tgt_z = enc("conv", tgt)
-    th0 = lrelu(torch.cat([src_z, ctx_z], 1) @ p["translate/trans_h0/Matrix"] + p["translate/trans_h0/bias"])
+    skips, ctx_z = enc("conv_context", ctx, "e_ctx")
+    _, src_z = enc("conv", src, "e_src")
+    _, tgt_z = enc("conv", tgt, "e_tgt")
+    th0 = lrelu(torch.cat([src_z, ctx_z], 1) @ p["translate/trans_h0/Matrix"] + p["translate/trans_h0/bias"], ("trans_h0", None), branches)
     trans_z = th0 @ p["translate/trans_z/Matrix"] + p["translate/trans_z/bias"]
-    out, out2 = dec(trans_z, skips) + ctx, dec(tgt_z, skips) + ctx
+    out, out2 = dec(trans_z, skips, "d1") + ctx, dec(tgt_z, skips, "d2") + ctx
     sim = ((trans_z - tgt_z) ** 2).mean() * 1e3
     r1, r2 = 0.5 * ((tgt - out) ** 2).sum(), 0.5 * ((tgt - out2) ** 2).sum()
     return dict(input_z=src_z, translated_z=trans_z, out=out, out2=out2, simloss=sim, recon1=r1, recon2=r2, loss=r1 + r2 + sim)
