@@ -88,6 +88,7 @@ int ctx_create_ex(const ctx_config* cfg, int device, void* stream, void* arena, 
     }
     if (rc == CTX_OK) {
         set_routing(h);
+        if (h->gen) gen_plan(h); else skip_plan(h);      // (after the routing: `direct` reads rt.direct3)
         rc = h->gen ? gen_alloc(h) : alloc_buffers(h);
     }
     // packed-filter cache (dconv.h: DcPackCache): only where the library owns the parameters -- a caller-owned arena (ctx_create_ex) may be
@@ -1108,9 +1109,9 @@ int ctx_last_outputs(ctx_handle* h, float* out, float* out2, float* tgt) {
     return finish(h);
 }
 
-// Test hook: copy an internal device buffer to the host (names: img Z dZ cz th0 dz out dout dDz dsim2
-// dth0 dcz, s0..s4 c0..c4 dS0..dS4 dC0..dC4 dSk0..dSk3, e1..e3 dE1..dE3; ContextAEReal / ContextAEInception2: img Z dZ out dz th0
-// a0..a4 e1..e3).  n = floats to copy.
+// Test hook: copy an internal device buffer to the host.  Names of every handle: img Z dZ out dout dz dDz th0 dth0 dsim2, e1..e3
+// dE1..dE3 dSk0..dSk3; ContextSkipNew also: cz dcz, s0..s4 c0..c4 dS0..dS4 dC0..dC4; ContextAEReal / ContextAEInception2 also: a0..a4
+// (conv outputs over the stacked [tgt | src | ctx] images, a4 = h4 [3B, Fp]).  n = floats to copy.
 int ctx_debug_read(ctx_handle* h, const char* name, float* host, size_t n) {
     if (!h || !name || !host) return CTX_E_INVALID;
     const std::string s(name);
@@ -1121,29 +1122,19 @@ int ctx_debug_read(ctx_handle* h, const char* name, float* host, size_t n) {
         return -1;
     };
     int k;
-    if (h->gen) {   // table-driven models: a0..a3 conv outputs over the stacked [tgt | src | ctx] images, a4 = h4 [3B, Fp], e1..e3, dz, th0, Z
-        const GenState& r = *h->gen;
-        if (s == "img") p = h->img; else if (s == "Z") p = h->Z; else if (s == "dZ") p = h->dZ; else if (s == "out") p = h->out;
-        else if (s == "dz") p = r.dz; else if (s == "th0") p = r.th0;
-        else if ((k = idx("a", 0, 4)) >= 0) p = r.a[k];
-        else if ((k = idx("e", 1, 3)) >= 0) p = r.e[k];
-        if (!p) return fail(h, CTX_E_INVALID, "unknown debug buffer '%s' (table-driven models: img Z dZ out dz th0 a0..a4 e1..e3)", name);
-        HIP_TRY(h, hipSetDevice(h->device));
-        HIP_TRY(h, hipMemcpyAsync(host, p, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        return finish(h);
-    }
     if (s == "img") p = h->img; else if (s == "Z") p = h->Z; else if (s == "dZ") p = h->dZ;
-    else if (s == "cz") p = h->cz; else if (s == "th0") p = h->th0; else if (s == "dz") p = h->dz;
-    else if (s == "out") p = h->out; else if (s == "dout") p = h->dout; else if (s == "dDz") p = h->dDz;
-    else if (s == "dsim2") p = h->dsim2; else if (s == "dth0") p = h->dth0; else if (s == "dcz") p = h->dcz;
+    else if (s == "out") p = h->out; else if (s == "dout") p = h->dout; else if (s == "dz") p = h->dz; else if (s == "dDz") p = h->dDz;
+    else if (s == "th0") p = h->th0; else if (s == "dth0") p = h->dth0; else if (s == "dsim2") p = h->dsim2;
     else if ((k = idx("dSk", 0, 3)) >= 0) p = h->dSk[k];
+    else if ((k = idx("dE", 1, 3)) >= 0) p = h->dE[k];
+    else if ((k = idx("e", 1, 3)) >= 0) p = h->e[k];
+    else if (h->gen) { if ((k = idx("a", 0, 4)) >= 0) p = h->gen->a[k]; }
+    else if (s == "cz") p = h->cz; else if (s == "dcz") p = h->dcz;
     else if ((k = idx("dS", 0, 4)) >= 0) p = h->dS[k];
     else if ((k = idx("dC", 0, 4)) >= 0) p = h->dC[k];
-    else if ((k = idx("dE", 1, 3)) >= 0) p = h->dE[k];
     else if ((k = idx("s", 0, 4)) >= 0) p = h->s[k];
     else if ((k = idx("c", 0, 4)) >= 0) p = h->c[k];
-    else if ((k = idx("e", 1, 3)) >= 0) p = h->e[k];
-    if (!p) return fail(h, CTX_E_INVALID, "unknown debug buffer '%s'", name);
+    if (!p) return fail(h, CTX_E_INVALID, "unknown debug buffer '%s' (names: ctx_debug_read in ctx_abi.cpp)", name);
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipMemcpyAsync(host, p, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     return finish(h);

@@ -2,8 +2,9 @@
 // (gym/envs/mujoco/arm_shaping.py:1272-1354), the table-driven engine of ContextAEReal / ContextAEInception2 (ctxtrans_gen.inc), the
 // captured inference forwards.  No CPU code path: every contraction runs in the HIP kernels of igemm.h / kernels.hip / the direct kernels.
 // Both engines launch their layers through the helpers under "layer launch helpers": fc_layer / fc_dx / fc_dw, and conv / convt / wgrad
-// / convt3, which alone choose the kernel of a conv-type layer; the rules in which the variants differ are the handle's routing record
-// (ctx_handle::rt, set_routing).
+// / convt3, which alone choose the kernel of a conv-type layer from the handle's routing record (ctx_handle::rt, set_routing).  Both run
+// translate MLP, d_h0_lin and d_h1 .. d_h4, forward and backward, through translate_fwd / decoder_fwd / decoder_bwd / fc_middle_bwd
+// on the handle's buffers and its record ctx_handle::dec.  Their own are the encoders, whose launch orders differ, and rchain.
 #include "ctx_internal.h"
 
 namespace ctxi {
@@ -193,6 +194,22 @@ int alloc_tail(ctx_handle* h, int64_t slab_floats, int64_t maxc) {
     return CTX_OK;
 }
 
+// ... and share in the middle: the activations of translate MLP, d_h0_lin and d_h1 .. d_h3 with their gradients (sized by h->dec)
+int alloc_middle(ctx_handle* h) {
+    const int64_t B = h->Bm, F = h->Fp;
+    TRY(dev_alloc(h, &h->th0, B * F));
+    TRY(dev_alloc(h, &h->dth0, B * F));
+    TRY(dev_alloc(h, &h->dsim2, 2 * B * F));
+    TRY(dev_alloc(h, &h->dz, 2 * B * h->D0));
+    TRY(dev_alloc(h, &h->dDz, 2 * B * h->D0));
+    for (int k = 1; k <= 3; ++k) {   // e[k]: output of d_hk = the input grid and width of the encoder layer 4 - k it mirrors
+        const int64_t n = (int64_t)h->dec.g[4 - k].hb * h->dec.g[4 - k].wb * h->dec.co[4 - k];
+        TRY(dev_alloc(h, &h->e[k], 2 * B * n));
+        TRY(dev_alloc(h, &h->dE[k], 2 * B * n));
+    }
+    return CTX_OK;
+}
+
 int alloc_buffers(ctx_handle* h) {
     const int64_t B = h->Bm, d = h->d, F = h->F;
     TRY(dev_alloc(h, &h->u8, 3 * B * h->npi));
@@ -214,16 +231,7 @@ int alloc_buffers(ctx_handle* h) {
     TRY(dev_alloc(h, &h->dC[4], B * F));
     TRY(dev_alloc(h, &h->cz, B * F));
     TRY(dev_alloc(h, &h->dcz, B * F));
-    TRY(dev_alloc(h, &h->th0, B * F));
-    TRY(dev_alloc(h, &h->dth0, B * F));
-    TRY(dev_alloc(h, &h->dsim2, 2 * B * F));
-    TRY(dev_alloc(h, &h->dz, 2 * B * h->D0));
-    TRY(dev_alloc(h, &h->dDz, 2 * B * h->D0));
-    for (int k = 1; k <= 3; ++k) {   // e[k]: output of d_hk, spatial H >> (4-k), channels 8d >> k
-        const int64_t pix = (int64_t)h->hh[4 - k] * h->ww[4 - k], ch = (8 * d) >> k;
-        TRY(dev_alloc(h, &h->e[k], 2 * B * pix * ch));
-        TRY(dev_alloc(h, &h->dE[k], 2 * B * pix * ch));
-    }
+    TRY(alloc_middle(h));
     TRY(dev_alloc(h, &h->out, 2 * B * h->npi));
     // d_h4's scatter product exists only where the direct 3-channel kernel (convt3.hip) does not run: the split-bf16 mode / odd shapes
     // (a handle on the direct kernel keeps a small one for the starved inference launches, which take the product + gather route: forward)
@@ -506,8 +514,6 @@ void fc_dw(ctx_handle* h, const std::string& name, const XL& x, int K, const flo
 // handle's routing record (h->rt) and two facts of the call: `direct` (this layer runs on the direct kernels of dconv.h) and `infer`
 // (an inference forward: translate / encode).  The engines decide which buffers a layer reads and writes and on which lane it runs.
 
-// a SAME-padded K x K stride-s layer: big grid hb x wb (conv input = transposed-conv output), small grid hs x ws, pad = pad_before
-struct Geo { int hb, wb, hs, ws, s, pad, K; };
 double useful_frac(const Geo& g) { return tap_frac_p(g.hb, g.wb, g.hs, g.ws, g.K, g.s, g.pad); }
 // small-grid operand [x1 | x2] of c1 + c2 channels, x2 (a decoder layer's ctx skip) read at image index img % nmod2; c2 = 0: x1 alone
 struct Cat { const float* x1; int c1; const float* x2 = nullptr; int c2 = 0; int nmod2 = 1; };
@@ -672,26 +678,36 @@ void convt3(ctx_handle* h, const std::string& name, const Geo& g, const Cat& in,
     else convt3_gather_s1_t(h->stream, h->P3, b, out, nimg, hs, ws);
 }
 
-// ContextSkipNew's layer k (encoder h_k; decoder d_h(4-k) mirrors it): 5x5 stride 2 from the grid H >> k
-Geo skip_geo(const ctx_handle* h, int k) { return Geo{h->hh[k], h->ww[k], h->hh[k + 1], h->ww[k + 1], 2, 1, 5}; }
-
-struct Scope {
-    float *w[4], *b[4], *w4, *b4, *wz, *bz;
-    float *gw[4], *gb[4], *gw4, *gb4, *gwz, *gbz;
-};
-
-Scope scope_of(ctx_handle* h, const std::string& sc) {
+Scope scope_of(const ctx_handle* h, const std::string& sc) {
     Scope s;
+    auto at = [&](const std::string& name, float*& w, float*& g) {
+        w = h->arena + h->find((sc + name).c_str()); g = w + h->Ppad;
+    };
     for (int k = 0; k < 4; ++k) {
-        const std::string base = sc + "/h" + std::to_string(k) + "_conv/";
-        s.w[k] = h->Wp((base + "w").c_str()); s.b[k] = h->Wp((base + "biases").c_str());
-        s.gw[k] = h->Gp((base + "w").c_str()); s.gb[k] = h->Gp((base + "biases").c_str());
+        at("/h" + std::to_string(k) + "_conv/w", s.w[k], s.gw[k]);
+        at("/h" + std::to_string(k) + "_conv/biases", s.b[k], s.gb[k]);
     }
-    s.w4 = h->Wp((sc + "/h4_lin/Matrix").c_str()); s.b4 = h->Wp((sc + "/h4_lin/bias").c_str());
-    s.wz = h->Wp((sc + "/hz_lin/Matrix").c_str()); s.bz = h->Wp((sc + "/hz_lin/bias").c_str());
-    s.gw4 = h->Gp((sc + "/h4_lin/Matrix").c_str()); s.gb4 = h->Gp((sc + "/h4_lin/bias").c_str());
-    s.gwz = h->Gp((sc + "/hz_lin/Matrix").c_str()); s.gbz = h->Gp((sc + "/hz_lin/bias").c_str());
+    at("/h4_lin/Matrix", s.w4, s.gw4); at("/h4_lin/bias", s.b4, s.gb4);
+    at("/hz_lin/Matrix", s.wz, s.gwz); at("/hz_lin/bias", s.bz, s.gbz);
     return s;
+}
+
+// ContextSkipNew's share of ctx_create: the record of the shared sequences and the two encoders' parameters, by name, once
+void skip_plan(ctx_handle* h) {
+    DecoderPlan& p = h->dec;
+    for (int gi = 0; gi < 4; ++gi) {
+        p.g[gi] = Geo{h->hh[gi], h->ww[gi], h->hh[gi + 1], h->ww[gi + 1], 2, 1, 5};   // encoder h_gi and its mirror: 5x5 stride 2 from the grid H >> gi
+        p.ch[gi] = h->d << gi;
+        p.co[gi] = gi ? h->d << (gi - 1) : 3;
+        p.direct[gi] = p.co[gi] == 3 && h->rt.direct3;
+        p.dw[4 - gi] = h->find(("deconv/d_h" + std::to_string(4 - gi) + "/w").c_str());
+        p.db[4 - gi] = h->find(("deconv/d_h" + std::to_string(4 - gi) + "/biases").c_str());
+    }
+    p.th0w = h->find("translate/trans_h0/Matrix"); p.th0b = h->find("translate/trans_h0/bias");
+    p.tzw = h->find("translate/trans_z/Matrix"); p.tzb = h->find("translate/trans_z/bias");
+    p.d0w = h->find("deconv/d_h0_lin/Matrix"); p.d0b = h->find("deconv/d_h0_lin/bias");
+    h->enc_conv = scope_of(h, "conv");
+    h->enc_ctx = scope_of(h, "conv_context");
 }
 
 // arm_shaping.py:1282-1288 / :1290-1307: four conv+lrelu, h4_lin+lrelu, hz_lin (+lrelu for `conv`)
@@ -701,7 +717,7 @@ void encoder_fwd(ctx_handle* h, const std::string& scn, const Scope& sc, const f
     const float* in = x;
     for (int k = 0; k < 4; ++k) {
         const int ca = k ? d << (k - 1) : 3;
-        conv(h, scn + "/h" + std::to_string(k) + "_conv fwd", skip_geo(h, k), in, ca, nimg, sc.w[k], d << k, epi_act(act[k], d << k, sc.b[k], 1),
+        conv(h, scn + "/h" + std::to_string(k) + "_conv fwd", h->dec.g[k], in, ca, nimg, sc.w[k], d << k, epi_act(act[k], d << k, sc.b[k], 1),
              ca == 3 && h->rt.direct3);
         in = act[k];
     }
@@ -725,11 +741,6 @@ void seed_grads(ctx_handle* h, int B, int sim_batch, float* dsim2, int ldz, int 
     vjp_seed(h->stream, h->dout + half, half, a->loss_weight, a->d_out2, half, 1, half);
     if (a->loss_weight != 1.f || a->d_translated_z) vjp_seed(h->stream, dsim2, ldz, a->loss_weight, a->d_translated_z, F, B, F);
     if (a->loss_weight != 1.f) vjp_seed(h->stream, dsim2 + (int64_t)B * ldz, ldz, a->loss_weight, nullptr, 0, B, ldz);
-}
-
-// VJP: the caller's d input_z joins the gradient of src_z (row block 2 of dZ, stride ldz) before src_z's lrelu' is applied
-void seed_input_z(ctx_handle* h, int B, int ldz) {
-    if (h->vjp && h->vjp->d_input_z) vjp_seed(h->stream, h->dZ + 2ll * B * ldz, ldz, 1.f, h->vjp->d_input_z, h->F, B, h->F);
 }
 
 // VJP frame gradients of a 3-channel first layer: d frames = conv2d_transpose(dA0, W_h0) with the h0 filter in its own layout
@@ -758,6 +769,118 @@ void frame_grads3(ctx_handle* h, const float* dA0, int c, int slot0, int nimg, i
     }
 }
 
+// ---- the part of the net every variant shares: translate MLP, d_h0_lin, d_h1 .. d_h4 -------------------------------------------
+// One launch sequence each, on the handle's buffers and h->dec; what depends on the call is an argument: the context code rows, the
+// ctx skips (skip[gi] from image skip0 on), row counts, `drop` (this step applies dropout: only a handle with masks is asked to).
+
+// translate (arm_shaping.py:1309-1312): trans_h0 on concat([src_z, ctx_z], 1), then trans_z into Z rows [0, B); nc == 1: ONE context code for all rows
+void translate_fwd(ctx_handle* h, int B, const float* ctx_z, int nc, bool drop) {
+    const DecoderPlan& p = h->dec;
+    const float* P = h->arena;
+    const int F = h->Fp;
+    const float* src_z = h->Z + 2ll * B * F;
+    if (drop) {                                                               // sites 3, 4: concat([src_z, ctx_z]) * M3, trans_h0 * M4 (:1650-1651)
+        ew_mul(h->stream, h->xcat, 2 * F, src_z, F, h->dM[3], 2 * F, B, F);
+        ew_mul(h->stream, h->xcat + F, 2 * F, ctx_z, F, h->dM[3] + F, 2 * F, B, F);
+    }
+    const KmPlain tcat{src_z, F, ctx_z, nc == 1 && B > 1 ? 0 : F, F, B, 2 * F / KC, g_zeros};
+    fc_layer(h, "translate/trans_h0", drop ? km(h->xcat, 2 * F, B, 2 * F) : tcat, B, 2 * F, P + p.th0w, P + p.th0b, F, 1, h->th0);
+    if (drop) ew_mul(h->stream, h->th0d, F, h->th0, F, h->dM[4], F, B, F);
+    fc_layer(h, "translate/trans_z", km(drop ? h->th0d : h->th0, F, B, F), B, F, P + p.tzw, P + p.tzb, F, 0, h->Z);
+}
+
+// decoder (arm_shaping.py:1321-1330, :1334-1343) over nd rows: dz = d_h0_lin(zin) -- zin null: dz is there already (rchain wrote it) --
+// then d_h1 .. d_h4; row r reads the ctx skips of image skip0 + r % nc of skip[gi]
+void decoder_fwd(ctx_handle* h, int B, const float* zin, int nd, const float* const skip[4], int skip0, int nc, bool infer, bool rec, bool drop) {
+    const DecoderPlan& p = h->dec;
+    const float* P = h->arena;
+    const int F = h->Fp, D0 = (int)h->D0;
+    if (zin && drop) { ew_mul(h->stream, h->zd, F, zin, F, h->dM[5], F, nd, F); zin = h->zd; }     // site 5: z * M5 feeds d_h0_lin (:1660)
+    if (zin) fc_layer(h, "deconv/d_h0_lin", km(zin, F, nd, F), nd, F, P + p.d0w, P + p.d0b, D0, 1, h->dz);
+    const float* dec = h->dz;
+    if (drop) { ew_mul(h->stream, h->dzd, D0, h->dz, D0, h->dM[6], D0, nd, D0); dec = h->dzd; }    // site 6: reshape(z_) * M6 feeds d_h1 (:1661)
+    for (int k = 1; k <= 4; ++k) {
+        const int gi = 4 - k;                                   // d_hk mirrors encoder layer 4 - k (arm_shaping.py:1841-1857), whose output is the skip
+        const int ch = p.ch[gi], co = p.co[gi];
+        const Cat in{dec, ch, skip[gi] + (int64_t)skip0 * p.g[gi].hs * p.g[gi].ws * ch, ch, nc};     // [decoder stream | ctx skip h_gi], ch channels each
+        const std::string nm_ = "deconv/d_h" + std::to_string(k);
+        if (k == 4 && co == 3) { convt3(h, nm_, p.g[gi], in, nd, P + p.dw[k], P + p.db[k], h->out, infer); break; }
+        Epi ep = epi_act(k < 4 ? h->e[k] : h->out, co, P + p.db[k], k < 4);
+        if (k == 4 && p.residual && !rec) {                              // out = h4 + tgtctx: the ctx frames serve both decoder passes
+            ep.add1 = h->img + 2ll * B * h->npi; ep.lda1 = co; ep.add1_mod = (int64_t)B * h->H * h->W;     // (translate with one context frame: the entry points still lay out B copies for this add)
+        }
+        convt(h, nm_ + " fwd", p.g[gi], in, nd, P + p.dw[k], co, ep, p.direct[gi], infer);
+        dec = h->e[k];
+    }
+    // RECON: out2 = h4 + tgtctx with the context maps repeating every nc rows -- a pass of its own, the same two additions in the same
+    // order as the epilogue's ((product + bias) + tgtctx)
+    if (rec && p.residual) add_period(h->stream, h->out, h->img + (int64_t)(h->recon_inplace ? B : 2 * B) * h->npi, (int64_t)nc * h->npi, (int64_t)B * h->npi);
+}
+
+// d_h4 .. d_h1 backward, both passes at once (2B rows) from h->dout: per layer the filter gradient on the side lane, then the input gradient
+void decoder_bwd(ctx_handle* h, int B, const float* const skip[4], int skip0, bool drop) {
+    const DecoderPlan& p = h->dec;
+    float* G = h->arena + h->Ppad;
+    const float* dy = h->dout;
+    for (int k = 4; k >= 1; --k) {
+        const int gi = 4 - k;
+        const int ch = p.ch[gi], ca = p.co[gi];
+        const std::string nm_ = "deconv/d_h" + std::to_string(k);
+        // (with dropout d_h1 was fed dz * M6: the same sign as dz wherever M6 > 0, so it also serves as the lrelu' reference; the
+        // gradient is multiplied by M6 after the launch -- the two factors commute)
+        const float* dec_in = k > 1 ? h->e[k - 1] : (drop ? h->dzd : h->dz);
+        float* d_dec = k > 1 ? h->dE[k - 1] : h->dDz;
+        // filter gradient dw[tap][a = deconv output channel][b = channel of [decoder | skip]]
+        { Side sd(h, LANE_DW);
+          wgrad(h, nm_, p.g[gi], dy, ca, Cat{dec_in, ch, skip[gi] + (int64_t)skip0 * p.g[gi].hs * p.g[gi].ws * ch, ch, B}, 2 * B, G + p.dw[k], G + p.db[k], p.direct[gi]); }
+        // input gradient of a conv2d_transpose (any stride) = the SAME conv2d of dy with the filter read [K,K,ca,cb]; cols < ch are the
+        // decoder stream (masked by its lrelu), cols >= ch the ctx skip of this pass
+        Epi ed;
+        ed.out1 = d_dec; ed.ld1 = ch; ed.nsplit = ch; ed.mask = dec_in; ed.ldm = ch; ed.out2 = h->dSk[gi]; ed.ld2 = ch;
+        conv(h, nm_ + " dx", p.g[gi], dy, ca, 2 * B, h->arena + p.dw[k], 2 * ch, ed, p.direct[gi]);
+        dy = d_dec;
+    }
+    if (drop) ew_mul(h->stream, h->dDz, (int)h->D0, h->dDz, (int)h->D0, h->dM[6], (int)h->D0, 2 * B, (int)h->D0);       // site 6
+}
+
+// d_h0_lin, trans_z, trans_h0 backward from dDz into dZ ([trans_z | tgt_z | src_z] rows) and d_ctx_z; translate/*, deconv/* are then final
+void fc_middle_bwd(ctx_handle* h, int B, const float* ctx_z, float* d_ctx_z, bool drop) {
+    const DecoderPlan& p = h->dec;
+    const float* P = h->arena;
+    float* G = h->arena + h->Ppad;
+    const int F = h->Fp, D0 = (int)h->D0;
+    float* d_src_z = h->dZ + 2ll * B * F;
+    // d_h0_lin: input Z[0:2B] = [trans_z | tgt_z]; simloss adds +-c(trans_z - tgt_z) to its gradient
+    { Side sd(h, LANE_DW); fc_dw(h, "deconv/d_h0_lin", nm(drop ? h->zd : h->Z, F, F, 2 * B), F, h->dDz, 2 * B, D0, G + p.d0w, G + p.d0b); }
+    Epi ep;
+    ep.out1 = h->dZ; ep.ld1 = F;
+    if (!drop) { ep.add1 = h->dsim2; ep.lda1 = F; }
+    fc_dx(h, "deconv/d_h0_lin", h->dDz, 2 * B, D0, P + p.d0w, F, ep);
+    // site 5: d z = (d_h0_lin's input gradient) * M5 + the simloss seed, which sees the un-dropped codes
+    if (drop) drop_fin(h->stream, h->dZ, h->dZ, h->dM[5], h->dsim2, nullptr, nullptr, 2ll * B * F);
+    // translate MLP: d trans_z = dZ[0:B]
+    { Side sd(h, LANE_DW); fc_dw(h, "translate/trans_z", nm(drop ? h->th0d : h->th0, F, F, B), F, h->dZ, B, F, G + p.tzw, G + p.tzb); }
+    Epi e1;
+    e1.out1 = h->dth0; e1.ld1 = F; e1.mask = h->th0; e1.ldm = F;
+    fc_dx(h, "translate/trans_z", h->dZ, B, F, P + p.tzw, F, e1);
+    if (drop) ew_mul(h->stream, h->dth0, F, h->dth0, F, h->dM[4], F, B, F);          // site 4
+    {
+        Side sd(h, LANE_DW);
+        if (drop) fc_dw(h, "translate/trans_h0", nm(h->xcat, 2 * F, 2 * F, B), 2 * F, h->dth0, B, F, G + p.th0w, G + p.th0b);
+        else fc_dw(h, "translate/trans_h0", NmPlain2{h->Z + 2ll * B * F, F, ctx_z, F, F, 2 * F, B, g_zeros}, 2 * F, h->dth0, B, F, G + p.th0w, G + p.th0b);
+    }
+    Epi e2;   // d concat: cols < F -> d src_z (row block 2 of dZ), cols >= F -> d ctx_z
+    e2.out1 = d_src_z; e2.ld1 = F; e2.nsplit = F; e2.out2 = d_ctx_z; e2.ld2 = F;
+    fc_dx(h, "translate/trans_h0", h->dth0, B, F, P + p.th0w, 2 * F, e2);
+    if (drop) {                                                                        // site 3, both halves of the concat
+        ew_mul(h->stream, d_src_z, F, d_src_z, F, h->dM[3], 2 * F, B, F);
+        ew_mul(h->stream, d_ctx_z, F, d_ctx_z, F, h->dM[3] + F, 2 * F, B, F);
+    }
+    // VJP: the caller's d input_z joins the gradient of src_z before src_z's lrelu' is applied
+    if (h->vjp && h->vjp->d_input_z) vjp_seed(h->stream, d_src_z, F, 1.f, h->vjp->d_input_z, h->F, B, h->F);
+    fire_bucket(h, p.th0w);
+}
+
 }  // namespace ctxi
 #include "ctxtrans_gen.inc"
 namespace ctxi {
@@ -769,11 +892,10 @@ namespace ctxi {
 void forward(ctx_handle* h, int B, Mode mode) {
     OptScope os(&h->opt);
     h->act_serial++;
-    if (h->gen) { gen_forward(h, B, mode); return; }
     g_zeros = h->zeros;
-    const int d = h->d, F = h->F;
+    if (h->gen) { gen_forward(h, B, mode); return; }
+    const int F = h->F;
     const int64_t npi = h->npi;
-    const Scope st = scope_of(h, "conv"), cx = scope_of(h, "conv_context");
     float* src_z = h->Z + 2ll * B * F;
     const bool lanes = use_lanes(h) && mode != MODE_ENCODE;
     // images through `conv_context`: B, or the ONE frame every row shares (its code and skip activations are then read with row stride 0
@@ -793,34 +915,17 @@ void forward(ctx_handle* h, int B, Mode mode) {
     if (lanes) {
         fork(h, LANE_CTX);
         LaneSwap sw(h, LANE_CTX);
-        encoder_fwd(h, "conv_context", cx, ctx_img, nc, h->c, h->cz, 0);
+        encoder_fwd(h, "conv_context", h->enc_ctx, ctx_img, nc, h->c, h->cz, 0);
     }
-    if (mode == MODE_TRAIN) encoder_fwd(h, "conv", st, h->img, 2 * B, h->s, h->Z + (int64_t)B * F, 1);
-    else encoder_fwd(h, "conv", st, h->img + B * npi, B, h->s, src_z, 1);
+    if (mode == MODE_TRAIN) encoder_fwd(h, "conv", h->enc_conv, h->img, 2 * B, h->s, h->Z + (int64_t)B * F, 1);
+    else encoder_fwd(h, "conv", h->enc_conv, h->img + B * npi, B, h->s, src_z, 1);
     if (mode == MODE_ENCODE) return;
     if (lanes) join(h, LANE_CTX);
-    else encoder_fwd(h, "conv_context", cx, ctx_img, nc, h->c, h->cz, 0);
-    // translate (arm_shaping.py:1309-1312): trans_h0 on concat([src_z, ctx_z], 1), then trans_z
-    if (!rec) {
-        KmPlain tcat{src_z, F, h->cz, nc == 1 && B > 1 ? 0 : F, F, B, 2 * F / KC, g_zeros};
-        fc_layer(h, "translate/trans_h0", tcat, B, 2 * F, h->Wp("translate/trans_h0/Matrix"), h->Wp("translate/trans_h0/bias"), F, 1, h->th0);
-        fc_layer(h, "translate/trans_z", km(h->th0, F, B, F), B, F, h->Wp("translate/trans_z/Matrix"), h->Wp("translate/trans_z/bias"), F, 0, h->Z);
-    }
-    // decoder (arm_shaping.py:1321-1330, :1334-1343); MODE_RECON: pass 2 alone, on tgtimg_z = input_z
+    else encoder_fwd(h, "conv_context", h->enc_ctx, ctx_img, nc, h->c, h->cz, 0);
+    if (!rec) translate_fwd(h, B, h->cz, nc, false);
+    // decoder; MODE_RECON: pass 2 alone, on tgtimg_z = input_z
     const int nd = mode == MODE_TRAIN ? 2 * B : B;
-    fc_layer(h, "deconv/d_h0_lin", km(rec ? src_z : h->Z, F, nd, F), nd, F, h->Wp("deconv/d_h0_lin/Matrix"), h->Wp("deconv/d_h0_lin/bias"), (int)h->D0, 1, h->dz);
-    const float* dec = h->dz;
-    for (int k = 1; k <= 4; ++k) {
-        const int c1 = (16 * d) >> k;                         // decoder stream | ctx skip h_{4-k}, c1 channels each
-        const std::string nm_ = "deconv/d_h" + std::to_string(k);
-        const float* w = h->Wp((nm_ + "/w").c_str());
-        const float* b = h->Wp((nm_ + "/biases").c_str());
-        const Cat in{dec, c1, h->c[4 - k], c1, nc};
-        if (k == 4) { convt3(h, nm_, skip_geo(h, 0), in, nd, w, b, h->out, mode != MODE_TRAIN); break; }
-        const int ca = (8 * d) >> k;
-        convt(h, nm_ + " fwd", skip_geo(h, 4 - k), in, nd, w, ca, epi_act(h->e[k], ca, b, 1), false, mode != MODE_TRAIN);
-        dec = h->e[k];
-    }
+    decoder_fwd(h, B, rec ? src_z : h->Z, nd, h->c, 0, nc, mode != MODE_TRAIN, rec, false);
 }
 
 // d loss / d params into the grad arena (what AdamOptimizer.minimize differentiates,
@@ -828,60 +933,17 @@ void forward(ctx_handle* h, int B, Mode mode) {
 void backward(ctx_handle* h, int B, int sim_batch) {
     OptScope os(&h->opt);
     h->act_serial++;
-    if (h->gen) { gen_backward(h, B, sim_batch); return; }
     g_zeros = h->zeros;
+    if (h->gen) { gen_backward(h, B, sim_batch); return; }
     const int d = h->d, F = h->F;
     const int64_t npi = h->npi;
     float* tgt_z = h->Z + (int64_t)B * F;
-    float* src_z = h->Z + 2ll * B * F;
     seed_grads(h, B, sim_batch, h->dsim2, F, 0);
     if (!h->rt.direct3) pack_c4(h, h->dout, 2ll * B * h->H * h->W);
 
-    // ---- decoder, both passes at once (batch 2B)
-    const float* dy = h->dout;
-    for (int k = 4; k >= 1; --k) {
-        const int c1 = (16 * d) >> k;
-        const int ca = k < 4 ? (8 * d) >> k : 3;
-        const Geo g = skip_geo(h, 4 - k);
-        const std::string nm_ = "deconv/d_h" + std::to_string(k);
-        const float* dec_in = k > 1 ? h->e[k - 1] : h->dz;      // decoder half of the concat input
-        float* d_dec = k > 1 ? h->dE[k - 1] : h->dDz;
-        const bool direct = ca == 3 && h->rt.direct3;
-        { Side sd(h, LANE_DW);
-          wgrad(h, nm_, g, dy, ca, Cat{dec_in, c1, h->c[4 - k], c1, B}, 2 * B, h->Gp((nm_ + "/w").c_str()), h->Gp((nm_ + "/biases").c_str()), direct); }
-        // input gradient = SAME stride-2 conv of dy with the same filter read as [5,5,ca,cb]; cols < c1
-        // are the decoder stream (masked by its lrelu), cols >= c1 the ctx skip of this pass
-        Epi ed;
-        ed.out1 = d_dec; ed.ld1 = c1; ed.nsplit = c1; ed.mask = dec_in; ed.ldm = c1;
-        ed.out2 = h->dSk[4 - k]; ed.ld2 = c1;
-        conv(h, nm_ + " dx", g, dy, ca, 2 * B, h->Wp((nm_ + "/w").c_str()), 2 * c1, ed, direct);
-        dy = d_dec;
-    }
-    // d_h0_lin: input Z[0:2B] = [trans_z | tgt_z]; simloss adds +-c(trans_z - tgt_z) to its gradient
-    {
-        const int D0 = (int)h->D0;
-        { Side sd(h, LANE_DW);
-          fc_dw(h, "deconv/d_h0_lin", nm(h->Z, F, F, 2 * B), F, h->dDz, 2 * B, D0, h->Gp("deconv/d_h0_lin/Matrix"), h->Gp("deconv/d_h0_lin/bias")); }
-        Epi ep;
-        ep.out1 = h->dZ; ep.ld1 = F; ep.add1 = h->dsim2; ep.lda1 = F;
-        fc_dx(h, "deconv/d_h0_lin", h->dDz, 2 * B, D0, h->Wp("deconv/d_h0_lin/Matrix"), F, ep);
-    }
-    // ---- translate MLP: d trans_z = dZ[0:B]
-    {
-        { Side sd(h, LANE_DW);
-          fc_dw(h, "translate/trans_z", nm(h->th0, F, F, B), F, h->dZ, B, F, h->Gp("translate/trans_z/Matrix"), h->Gp("translate/trans_z/bias")); }
-        Epi e1;
-        e1.out1 = h->dth0; e1.ld1 = F; e1.mask = h->th0; e1.ldm = F;
-        fc_dx(h, "translate/trans_z", h->dZ, B, F, h->Wp("translate/trans_z/Matrix"), F, e1);
-        NmPlain2 tcat{src_z, F, h->cz, F, F, 2 * F, B, g_zeros};
-        { Side sd(h, LANE_DW);
-          fc_dw(h, "translate/trans_h0", tcat, 2 * F, h->dth0, B, F, h->Gp("translate/trans_h0/Matrix"), h->Gp("translate/trans_h0/bias")); }
-        Epi e2;   // d concat: cols < F -> d src_z (row block 2 of dZ), cols >= F -> d ctx_z
-        e2.out1 = h->dZ + 2ll * B * F; e2.ld1 = F; e2.nsplit = F; e2.out2 = h->dcz; e2.ld2 = F;
-        fc_dx(h, "translate/trans_h0", h->dth0, B, F, h->Wp("translate/trans_h0/Matrix"), 2 * F, e2);
-        seed_input_z(h, B, F);
-    }
-    fire_bucket(h, h->find("translate/trans_h0/Matrix"));
+    // ---- decoder (both passes at once, batch 2B) and FC middle
+    decoder_bwd(h, B, h->c, 0, false);
+    fc_middle_bwd(h, B, h->cz, h->dcz, false);
     // ---- encoders
     auto encoder_bwd = [&](const std::string& scn, const Scope& sc, const float* x, int nimg, float* const act[5], float* dzp, float* const dA[5],
                            bool with_skips, int dw_lane, int slot0) {
@@ -896,12 +958,12 @@ void backward(ctx_handle* h, int B, int sim_batch) {
         if (with_skips) { e3.add1 = h->dSk[3]; e3.lda1 = K3; e3.add2 = h->dSk[3] + (int64_t)B * K3; e3.lda2 = K3; }
         fc_dx(h, scn + "/h4_lin", dA[4], nimg, F, sc.w4, K3, e3);
         {   // h4_lin / hz_lin of this encoder (2/3 of its parameters) are done with
-            const int64_t lin0 = h->find((scn + "/h4_lin/Matrix").c_str()), lin1 = lin0 + (int64_t)K3 * F + F + (int64_t)F * F + F;
+            const int64_t lin0 = sc.w4 - h->arena, lin1 = lin0 + (int64_t)K3 * F + F + (int64_t)F * F + F;
             if (h->dp_in_step) dp_bucket(h, lin0, lin1, dw_lane);
             else if (!h->bucket_fn) adam_early(h, lin0, lin1, dw_lane);
         }
         for (int k = 3; k >= 0; --k) {
-            const Geo g = skip_geo(h, k);
+            const Geo g = h->dec.g[k];
             const int ca = k ? d << (k - 1) : 3, cb = d << k;
             const std::string ln = scn + "/h" + std::to_string(k) + "_conv";
             { Side sd(h, dw_lane);
@@ -928,12 +990,12 @@ void backward(ctx_handle* h, int B, int sim_batch) {
         // everything it reads (dcz, dSk[*], c[*]) was produced before this point
         fork(h, LANE_CTX);
         LaneSwap sw(h, LANE_CTX);
-        encoder_bwd("conv_context", scope_of(h, "conv_context"), h->img + 2 * B * npi, B, h->c, h->dcz, h->dC, true, -1, 2);
+        encoder_bwd("conv_context", h->enc_ctx, h->img + 2 * B * npi, B, h->c, h->dcz, h->dC, true, -1, 2);
     }
     { ProfScope ps(h, "conv/hz_lin lrelu'", K_EW, 0.0); lrelu_mask(h->stream, dSz, tgt_z, 2ll * B * F); }
-    encoder_bwd("conv", scope_of(h, "conv"), h->img, 2 * B, h->s, dSz, h->dS, false, LANE_DW, 0);
+    encoder_bwd("conv", h->enc_conv, h->img, 2 * B, h->s, dSz, h->dS, false, LANE_DW, 0);
     if (lanes) { join(h, LANE_CTX); join(h, LANE_DW); }
-    else encoder_bwd("conv_context", scope_of(h, "conv_context"), h->img + 2 * B * npi, B, h->c, h->dcz, h->dC, true, -1, 2);
+    else encoder_bwd("conv_context", h->enc_ctx, h->img + 2 * B * npi, B, h->c, h->dcz, h->dC, true, -1, 2);
     h->have_grads = true;
 
 }

@@ -1,5 +1,7 @@
 // ctx_internal.h -- what the translation units of libctxtrans.so share: the handle (HBM layout below), the table-driven engine's state,
 // and the entry points of the launch sequences (ctx_engine.cpp) that the C ABI (ctx_abi.cpp) and the RCCL client (ctx_dp.cpp) call.
+// The handle owns what translate MLP and decoder work on in every variant (th0, dz, e[], their gradients, dSk[], dsim2, the dropout
+// masks) and the record `dec` each engine fills at create; GenState keeps the table-driven engine's own tables and encoder activations.
 // Nothing here is part of the public interface (include/ctxtrans.h).
 //
 // Batching (what makes each filter gradient a single launch): the `conv` encoder runs once on the
@@ -73,15 +75,8 @@ struct GenState {
     int64_t w[2][4], b[2][4], w4[2], b4[2], wz[2], bz[2], th0w, th0b, tzw, tzb, d0w, d0b, dw[5], db[5];
     // ---- activations (NHWC, cp[k] channels) and their gradients
     float *a[5] = {}, *dA[5] = {};           // a[0..3] conv outputs over 3B images [tgt | src | ctx], a[4] = h4 [3B, Fp]
-    float *th0 = nullptr, *dth0 = nullptr, *dz = nullptr, *dDz = nullptr;
-    float *e[4] = {}, *dE[4] = {};           // e[1..3] decoder outputs over 2B
-    float* dSk[4] = {};                      // d loss / d skip h_k, both decoder passes (2B)
-    float* dsim2 = nullptr;
-    // tf.nn.dropout of ContextAEReal's training graph (keep_prob < 1 only; arm_shaping.py:1637-1661): per site the factors
-    // mask / keep_prob (dM[1..6]: sites 1 flatten(h3), 2 h4, 3 concat([src_z, ctx_z]), 4 trans_h0, 5 z, 6 reshape(z_)) and the dropped
-    // copy the next layer reads
-    float* dM[7] = {};
-    float *x1d = nullptr, *x2d = nullptr, *xcat = nullptr, *th0d = nullptr, *zd = nullptr, *dzd = nullptr, *graw = nullptr;
+    // dropout sites 1 and 2 (factors: ctx_handle::dM): the dropped copies h4_lin / hz_lin read, and h4_lin's raw input gradient
+    float *x1d = nullptr, *x2d = nullptr, *graw = nullptr;
     int in_grid_h(int k, int H) const { return k ? gh[k - 1] : H; }
     int in_grid_w(int k, int W) const { return k ? gw[k - 1] : W; }
     int in_ch(int k) const { return k ? cp[k - 1] : C0; }
@@ -101,6 +96,25 @@ struct Routing {
                                  // handle's split arithmetic (dconv.h: FMT; option dconv bit 16); false: the exact-f32 direct kernel
 };
 
+// a SAME-padded K x K stride-s layer: big grid hb x wb (conv input = transposed-conv output), small grid hs x ws, pad = pad_before
+struct Geo { int hb, wb, hs, ws, s, pad, K; };
+
+// What translate_fwd / decoder_fwd / decoder_bwd / fc_middle_bwd (ctx_engine.cpp) need to know about a model beyond the handle's F (real
+// code width), Fp (code row stride) and D0 (flatten width): plain data, filled at create (skip_plan | gen_plan).  d_h(4-gi) mirrors h_gi.
+struct DecoderPlan {
+    Geo g[4];
+    int ch[4], co[4];            // width of each half of d_h(4-gi)'s input [decoder stream | ctx skip h_gi]; width of its output
+    bool direct[4];              // the layer runs on the direct kernels of dconv.h: narrow || (3-channel side && rt.direct3)
+    bool residual = false;       // out = decode(.) + ctx frame
+    int64_t th0w, th0b, tzw, tzb, d0w, d0b, dw[5], db[5];   // arena offsets (floats) of translate/*, deconv/d_h0_lin/*, deconv/d_hK/{w,biases}
+};
+
+// one ContextSkipNew encoder's parameters and their gradients in the arena (resolved once at create)
+struct Scope {
+    float *w[4], *b[4], *w4, *b4, *wz, *bz;
+    float *gw[4], *gb[4], *gw4, *gb4, *gwz, *gbz;
+};
+
 }  // namespace ctxi
 using ctxi::GenState;
 using ctxi::ParamInfo;
@@ -111,6 +125,8 @@ struct ctx_handle {
     Options opt{};               // this handle's switches (options.h; ctx_set_option): the process defaults (environment) at ctx_create
     GenState* gen = nullptr;     // CTX_VARIANT_REAL / CTX_VARIANT_INCEPTION2 state (ctxtrans_gen.inc)
     Routing rt{};                // conv-layer routing rules of this variant (set_routing, at create)
+    ctxi::DecoderPlan dec{};     // geometry, widths and parameter offsets of the shared translate / decoder sequences (at create)
+    ctxi::Scope enc_conv{}, enc_ctx{};   // ContextSkipNew: the parameters of its `conv` / `conv_context` encoders
     int Fp = 0;                  // row stride of the code buffers Z / dZ (featsize, or featsize padded to 32 for REAL)
     int device = 0;
     hipStream_t stream = nullptr;
@@ -129,7 +145,7 @@ struct ctx_handle {
     int H, W, d, F, Bm;
     int hh[5], ww[5];   // hh[k] = H >> k
     int64_t npi;        // H*W*3
-    int64_t D0;         // d_h0_lin width = 8d * h16 * w16
+    int64_t D0;         // d_h0_lin width = row stride of dz / dDz: 8d * h16 * w16, or GenState::D0p
 
     // buffers (see header comment)
     uint8_t* u8 = nullptr;
@@ -139,6 +155,11 @@ struct ctx_handle {
     float *dz = nullptr, *e[4] = {}, *out = nullptr;                 // e[1..3] decoder activations
     float *dout = nullptr, *dE[4] = {}, *dSk[4] = {}, *dDz = nullptr, *dsim2 = nullptr;
     float *dth0 = nullptr, *dcz = nullptr, *dS[5] = {}, *dC[5] = {};
+    // tf.nn.dropout of ContextAEReal's training graph (keep_prob < 1 only; arm_shaping.py:1637-1661): per site the factors
+    // mask / keep_prob (dM[1..6]: sites 1 flatten(h3), 2 h4, 3 concat([src_z, ctx_z]), 4 trans_h0, 5 z, 6 reshape(z_)) and, for the sites
+    // of the shared sequences, the dropped copy the next layer reads.  All null on a handle without dropout.
+    float* dM[7] = {};
+    float *xcat = nullptr, *th0d = nullptr, *zd = nullptr, *dzd = nullptr;
     float *scratch = nullptr, *slab = nullptr, *scalars = nullptr;
     float* zeros = nullptr;   // 256 B of zeros for the branch-free loaders
     // second lane: the conv_context encoder (forward and backward) is independent of the `conv` encoder chain
@@ -233,9 +254,7 @@ struct ctx_handle {
     std::vector<ctx_prof_entry> prof_entries;
     std::vector<double> prof_ms;
 
-    float* Wp(const char* name) const { return arena + find(name); }
-    float* Gp(const char* name) const { return arena + Ppad + find(name); }
-    int64_t find(const char* name) const {
+    int64_t find(const char* name) const {   // arena offset of a parameter (create only: the launch sequences use dec / enc_*)
         for (auto& p : params)
             if (p.name == name) return p.offset;
         return -1;
@@ -274,6 +293,8 @@ int adam_step(ctx_handle* h, float lr);
 int gen_alloc(ctx_handle* h);
 int alloc_buffers(ctx_handle* h);
 void set_routing(ctx_handle* h);
+void skip_plan(ctx_handle* h);     // fill h->dec (and ContextSkipNew's encoder scopes) at create, after set_routing
+void gen_plan(ctx_handle* h);
 bool use_lanes(const ctx_handle* h);
 void adam_begin(ctx_handle* h, float lr);
 void adam_end(ctx_handle* h);

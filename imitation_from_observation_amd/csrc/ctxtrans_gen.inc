@@ -1,5 +1,6 @@
 // ctxtrans_gen.inc -- the table-driven translator engine behind CTX_VARIANT_REAL and CTX_VARIANT_INCEPTION2.
-// Included by ctx_engine.cpp (ContextSkipNew keeps its own hand-scheduled three-lane path there).
+// Included by ctx_engine.cpp.  Its own here: the models' layout, their encoders, rchain and the frame gradients; translate MLP and
+// decoder are the sequences ContextSkipNew runs too (ctx_engine.cpp: translate_fwd .. fc_middle_bwd), on the record gen_plan fills.
 //
 //   ContextAEReal        gym/envs/mujoco/arm_shaping.py:1599-1684   k 5, strides 1/2/1/2, filters 32/16/16/8, ONE encoder
 //                        (scope "conv") for src, tgt and ctx, 3-channel frames, featsize 100        (names 'real', 'sweep')
@@ -23,7 +24,7 @@
 // tf.nn.dropout(., keep_prob) in ContextAEReal with the module-level keep_prob = 1.0 (arm_shaping.py:1476) is the identity.
 // Filter / bias gradients run on the LANE_DW side stream beside the input-gradient chain (Side scopes below).
 // Every layer launches through the layer helpers of ctx_engine.cpp (fc_* and conv / convt / wgrad / convt3, with this model's routing
-// record ctx_handle::rt); this file says which buffers each layer reads and writes, not which kernel runs it.
+// record ctx_handle::rt); this file says which buffers the encoders' layers read and write, not which kernel runs them.
 
 namespace ctxi {
 
@@ -155,28 +156,19 @@ int gen_alloc(ctx_handle* h) {
         const int64_t pix = (int64_t)r.gh[k] * r.gw[k];
         TRY(dev_alloc(h, &r.a[k], 3 * B * pix * r.cp[k]));
         TRY(dev_alloc(h, &r.dA[k], 3 * B * pix * r.cp[k]));
-        TRY(dev_alloc(h, &r.dSk[k], 2 * B * pix * r.cp[k]));
+        TRY(dev_alloc(h, &h->dSk[k], 2 * B * pix * r.cp[k]));
         maxc = std::max<int64_t>(maxc, 2 * r.cp[k]);
     }
     TRY(dev_alloc(h, &r.a[4], 3 * B * Fp));
     TRY(dev_alloc(h, &r.dA[4], 3 * B * Fp));
-    TRY(dev_alloc(h, &r.th0, B * Fp));
-    TRY(dev_alloc(h, &r.dth0, B * Fp));
-    TRY(dev_alloc(h, &r.dsim2, 2 * B * Fp));
-    TRY(dev_alloc(h, &r.dz, 2 * B * r.D0p));
-    TRY(dev_alloc(h, &r.dDz, 2 * B * r.D0p));
-    for (int k = 1; k <= 3; ++k) {          // e[k]: output of d_hk on the grid / width of encoder layer 3-k
-        const int64_t n = (int64_t)r.gh[3 - k] * r.gw[3 - k] * r.cp[3 - k];
-        TRY(dev_alloc(h, &r.e[k], 2 * B * n));
-        TRY(dev_alloc(h, &r.dE[k], 2 * B * n));
-    }
+    TRY(alloc_middle(h));
     if (h->cfg.keep_prob > 0.f && h->cfg.keep_prob < 1.f) {
-        TRY(dev_alloc(h, &r.dM[1], 3 * B * r.D0p)); TRY(dev_alloc(h, &r.x1d, 3 * B * r.D0p)); TRY(dev_alloc(h, &r.graw, 3 * B * r.D0p));
-        TRY(dev_alloc(h, &r.dM[2], 3 * B * Fp)); TRY(dev_alloc(h, &r.x2d, 3 * B * Fp));
-        TRY(dev_alloc(h, &r.dM[3], 2 * B * Fp)); TRY(dev_alloc(h, &r.xcat, 2 * B * Fp));
-        TRY(dev_alloc(h, &r.dM[4], B * Fp)); TRY(dev_alloc(h, &r.th0d, B * Fp));
-        TRY(dev_alloc(h, &r.dM[5], 2 * B * Fp)); TRY(dev_alloc(h, &r.zd, 2 * B * Fp));
-        TRY(dev_alloc(h, &r.dM[6], 2 * B * r.D0p)); TRY(dev_alloc(h, &r.dzd, 2 * B * r.D0p));
+        TRY(dev_alloc(h, &h->dM[1], 3 * B * r.D0p)); TRY(dev_alloc(h, &r.x1d, 3 * B * r.D0p)); TRY(dev_alloc(h, &r.graw, 3 * B * r.D0p));
+        TRY(dev_alloc(h, &h->dM[2], 3 * B * Fp)); TRY(dev_alloc(h, &r.x2d, 3 * B * Fp));
+        TRY(dev_alloc(h, &h->dM[3], 2 * B * Fp)); TRY(dev_alloc(h, &h->xcat, 2 * B * Fp));
+        TRY(dev_alloc(h, &h->dM[4], B * Fp)); TRY(dev_alloc(h, &h->th0d, B * Fp));
+        TRY(dev_alloc(h, &h->dM[5], 2 * B * Fp)); TRY(dev_alloc(h, &h->zd, 2 * B * Fp));
+        TRY(dev_alloc(h, &h->dM[6], 2 * B * r.D0p)); TRY(dev_alloc(h, &h->dzd, 2 * B * r.D0p));
     }
     TRY(dev_alloc(h, &h->out, 2 * B * h->npi));
     TRY(dev_alloc(h, &h->dout, 2 * B * h->npi));
@@ -189,9 +181,24 @@ int gen_alloc(ctx_handle* h) {
 // encoder layer k (decoder d_h(4-k) mirrors it): grid in = grid out * effective stride
 Geo gen_geo(const GenState& r, int k) { return Geo{r.gh[k] * r.se[k], r.gw[k] * r.se[k], r.gh[k], r.gw[k], r.se[k], r.pd[k], r.Kk[k]}; }
 
-// encoder `set` over images [img0, img0 + nimg) of the stacked batch [tgt | src | ctx]
+// the table-driven models' share of ctx_create: the record of the shared sequences from the tables of gen_spec / gen_layout
+void gen_plan(ctx_handle* h) {
+    const GenState& r = *h->gen;
+    DecoderPlan& p = h->dec;
+    for (int gi = 0; gi < 4; ++gi) {
+        p.g[gi] = gen_geo(r, gi);
+        p.ch[gi] = r.cp[gi];
+        p.co[gi] = r.in_ch(gi);
+        p.direct[gi] = r.narrow || (p.co[gi] == 3 && h->rt.direct3);
+    }
+    p.residual = r.residual;
+    p.th0w = r.th0w; p.th0b = r.th0b; p.tzw = r.tzw; p.tzb = r.tzb; p.d0w = r.d0w; p.d0b = r.d0b;
+    for (int k = 1; k <= 4; ++k) { p.dw[k] = r.dw[k]; p.db[k] = r.db[k]; }
+    h->D0 = r.D0p;
+}
+
 // dropout is part of the TRAINING graph only (keep_prob is fed as 1.0 by the sampler and by validation: ablations.py:556)
-bool gen_drop(const ctx_handle* h) { return h->gen && h->gen->dM[1] && h->drop_on; }
+bool gen_drop(const ctx_handle* h) { return h->dM[1] && h->drop_on; }
 
 // the FC middle in three launches (rchain.hip): TRAINING-mode forward / backward of a one-encoder model with 128-wide padded codes
 // (every block of it streams all five matrices, so it pays where the launch latency of ~40 implicit-GEMM launches is the larger cost: measured on
@@ -207,6 +214,7 @@ void gen_rchain_weights(const ctx_handle* h, const float* base, const float* W[1
     for (int i = 0; i < 10; ++i) W[i] = base + o[i];
 }
 
+// encoder `set` over images [img0, img0 + nimg) of the stacked batch [tgt | src | ctx]
 // (in0 >= 0: the images are read at rows [in0, in0 + nimg) of the frame buffer instead; activations and codes still land at img0)
 void gen_encoder_fwd(ctx_handle* h, int B, int set, int img0, int nimg, bool drop = false, bool fc = true, int in0 = -1) {
     GenState& r = *h->gen;
@@ -224,14 +232,14 @@ void gen_encoder_fwd(ctx_handle* h, int B, int set, int img0, int nimg, bool dro
     float* a4 = r.a[4] + (int64_t)img0 * Fp;
     if (drop) {                                                   // site 1: flatten(h3) * M1 feeds h4_lin (arm_shaping.py:1637)
         float* x1 = r.x1d + (int64_t)img0 * D0p;
-        ew_mul(h->stream, x1, D0p, in, D0p, r.dM[1] + (int64_t)img0 * D0p, D0p, nimg, D0p);
+        ew_mul(h->stream, x1, D0p, in, D0p, h->dM[1] + (int64_t)img0 * D0p, D0p, nimg, D0p);
         in = x1;
     }
     fc_layer(h, sc + "/h4_lin", km(in, D0p, nimg, D0p), nimg, D0p, P + r.w4[set], P + r.b4[set], Fp, 1, a4);
     const float* x2 = a4;
     if (drop) {                                                   // site 2: h4 * M2 feeds hz_lin (:1638)
         float* x2d = r.x2d + (int64_t)img0 * Fp;
-        ew_mul(h->stream, x2d, Fp, a4, Fp, r.dM[2] + (int64_t)img0 * Fp, Fp, nimg, Fp);
+        ew_mul(h->stream, x2d, Fp, a4, Fp, h->dM[2] + (int64_t)img0 * Fp, Fp, nimg, Fp);
         x2 = x2d;
     }
     // Z rows: [trans_z | tgt_z | src_z | ctx_z]; lrelu on every z (arm_shaping.py:1638, :1812)
@@ -239,9 +247,7 @@ void gen_encoder_fwd(ctx_handle* h, int B, int set, int img0, int nimg, bool dro
 }
 
 void gen_forward(ctx_handle* h, int B, Mode mode) {
-    g_zeros = h->zeros;
     GenState& r = *h->gen;
-    const float* P = h->arena;
     const int Fp = r.Fp, D0p = (int)r.D0p;
     if (r.C0 == 3 && !h->rt.direct3) {                                        // refresh the 4-channel copy of the frames in use
         if (mode == MODE_ENCODE) pack_c4(h, h->img + (int64_t)B * h->npi, (int64_t)B * h->H * h->W);
@@ -255,12 +261,12 @@ void gen_forward(ctx_handle* h, int B, Mode mode) {
         // batch sees B * world distinct masks instead of the same B on every shard
         const uint32_t seed = (uint32_t)h->drop_seed ^ (h->dp_comm ? 0x9E3779B9u * (uint32_t)h->dp_rank : 0u), step = (uint32_t)(h->drop_step >= 0 ? h->drop_step : h->adam_t);
         const int F = h->F, f3 = r.nf[3], c3 = r.cp[3], D0 = r.gh[3] * r.gw[3] * f3;
-        drop_factors(h->stream, r.dM[1], 3 * B, D0p, c3, f3, D0, kp, seed, step, 1);
-        drop_factors(h->stream, r.dM[2], 3 * B, Fp, Fp, F, F, kp, seed, step, 2);
-        drop_factors(h->stream, r.dM[3], B, 2 * Fp, Fp, F, 2 * F, kp, seed, step, 3);
-        drop_factors(h->stream, r.dM[4], B, Fp, Fp, F, F, kp, seed, step, 4);
-        drop_factors(h->stream, r.dM[5], 2 * B, Fp, Fp, F, F, kp, seed, step, 5);
-        drop_factors(h->stream, r.dM[6], 2 * B, D0p, c3, f3, D0, kp, seed, step, 6);
+        drop_factors(h->stream, h->dM[1], 3 * B, D0p, c3, f3, D0, kp, seed, step, 1);
+        drop_factors(h->stream, h->dM[2], 3 * B, Fp, Fp, F, F, kp, seed, step, 2);
+        drop_factors(h->stream, h->dM[3], B, 2 * Fp, Fp, F, 2 * F, kp, seed, step, 3);
+        drop_factors(h->stream, h->dM[4], B, Fp, Fp, F, F, kp, seed, step, 4);
+        drop_factors(h->stream, h->dM[5], 2 * B, Fp, Fp, F, F, kp, seed, step, 5);
+        drop_factors(h->stream, h->dM[6], 2 * B, D0p, c3, f3, D0, kp, seed, step, 6);
     }
     const bool chain = mode == MODE_TRAIN && gen_rchain(h, B);
     // TRANSLATE: only what translated_z / out depend on (base.py:216-218) -- the src and ctx rows of the encoder batch, decoder pass 1;
@@ -279,47 +285,15 @@ void gen_forward(ctx_handle* h, int B, Mode mode) {
     else if (tr) { gen_encoder_fwd(h, B, 0, B, B); gen_encoder_fwd(h, B, 1, 2 * B, nc); }
     else if (r.nset == 1) gen_encoder_fwd(h, B, 0, 0, 3 * B, drop, !chain);
     else { gen_encoder_fwd(h, B, 0, 0, 2 * B); gen_encoder_fwd(h, B, 1, 2 * B, B); }
-    float* src_z = h->Z + 2ll * B * Fp;
-    float* ctx_z = h->Z + 3ll * B * Fp;
+    // Z rows: [trans_z | tgt_z | src_z | ctx_z]; RECON: the decoder runs on src_z
+    const int nd = tr ? B : 2 * B;
     if (chain) {
         const float* W[10];
-        gen_rchain_weights(h, P, W);
+        gen_rchain_weights(h, h->arena, W);
         ProfScope ps(h, "h4_lin .. d_h0_lin fwd", K_RCHAIN, 2.0 * ((double)3 * B * (r.D0p + Fp) * Fp + (double)B * 3 * Fp * Fp + (double)2 * B * Fp * r.D0p));
-        rchain_fwd(h->stream, B, (int)r.D0p, r.a[3], r.a[4], h->Z, r.th0, r.dz, W);
-    } else if (drop) {                                                               // sites 3, 4: concat([src_z, ctx_z]) * M3, trans_h0 * M4 (:1650-1651)
-        ew_mul(h->stream, r.xcat, 2 * Fp, src_z, Fp, r.dM[3], 2 * Fp, B, Fp);
-        ew_mul(h->stream, r.xcat + Fp, 2 * Fp, ctx_z, Fp, r.dM[3] + Fp, 2 * Fp, B, Fp);
-        fc_layer(h, "translate/trans_h0", km(r.xcat, 2 * Fp, B, 2 * Fp), B, 2 * Fp, P + r.th0w, P + r.th0b, Fp, 1, r.th0);
-        ew_mul(h->stream, r.th0d, Fp, r.th0, Fp, r.dM[4], Fp, B, Fp);
-        fc_layer(h, "translate/trans_z", km(r.th0d, Fp, B, Fp), B, Fp, P + r.tzw, P + r.tzb, Fp, 0, h->Z);
-    } else if (!rec) {
-        KmPlain tcat{src_z, Fp, ctx_z, nc == 1 && B > 1 ? 0 : Fp, Fp, B, 2 * Fp / KC, g_zeros};
-        fc_layer(h, "translate/trans_h0", tcat, B, 2 * Fp, P + r.th0w, P + r.th0b, Fp, 1, r.th0);
-        fc_layer(h, "translate/trans_z", km(r.th0, Fp, B, Fp), B, Fp, P + r.tzw, P + r.tzb, Fp, 0, h->Z);
-    }
-    const int nd = tr ? B : 2 * B;
-    const float* zin = rec ? src_z : h->Z;
-    if (drop) { ew_mul(h->stream, r.zd, Fp, h->Z, Fp, r.dM[5], Fp, nd, Fp); zin = r.zd; }          // site 5: z * M5 feeds d_h0_lin (:1660)
-    if (!chain) fc_layer(h, "deconv/d_h0_lin", km(zin, Fp, nd, Fp), nd, Fp, P + r.d0w, P + r.d0b, D0p, 1, r.dz);
-    const float* dec = r.dz;
-    if (drop) { ew_mul(h->stream, r.dzd, D0p, r.dz, D0p, r.dM[6], D0p, nd, D0p); dec = r.dzd; }    // site 6: reshape(z_) * M6 feeds d_h1 (:1661)
-    for (int k = 1; k <= 4; ++k) {
-        const int gi = 4 - k;                                   // d_hk mirrors encoder layer 4 - k (arm_shaping.py:1841-1857), whose output is the skip
-        const Geo g = gen_geo(r, gi);
-        const int ch = r.cp[gi], co = r.in_ch(gi);
-        const Cat in{dec, ch, r.a[gi] + (int64_t)skip0 * g.hs * g.ws * ch, ch, nc};     // [decoder | ctx third of the encoder batch]
-        const std::string nm_ = "deconv/d_h" + std::to_string(k);
-        if (k == 4 && co == 3) { convt3(h, nm_, g, in, nd, P + r.dw[k], P + r.db[k], h->out, tr); break; }
-        Epi ep = epi_act(k < 4 ? r.e[k] : h->out, co, P + r.db[k], k < 4);
-        if (k == 4 && r.residual && !rec) {                              // out = h4 + tgtctx: the ctx frames serve both decoder passes
-            ep.add1 = h->img + 2ll * B * h->npi; ep.lda1 = co; ep.add1_mod = (int64_t)B * h->H * h->W;     // (translate with one context frame: the entry points still lay out B copies for this add)
-        }
-        convt(h, nm_ + " fwd", g, in, nd, P + r.dw[k], co, ep, r.narrow, tr);
-        dec = r.e[k];
-    }
-    // RECON: out2 = h4 + tgtctx with the context maps repeating every nc rows -- a pass of its own, the same two additions in the same
-    // order as the epilogue's ((product + bias) + tgtctx)
-    if (rec && r.residual) add_period(h->stream, h->out, h->img + (int64_t)(h->recon_inplace ? B : 2 * B) * h->npi, (int64_t)nc * h->npi, (int64_t)B * h->npi);
+        rchain_fwd(h->stream, B, D0p, r.a[3], r.a[4], h->Z, h->th0, h->dz, W);
+    } else if (!rec) translate_fwd(h, B, h->Z + 3ll * B * Fp, nc, drop);
+    decoder_fwd(h, B, chain ? nullptr : rec ? h->Z + 2ll * B * Fp : h->Z, nd, r.a, skip0, nc, tr, rec, drop);
 }
 
 // VJP frame / feature-map gradients, one launch per image slot [tgt | src | ctx] the caller asked for.  3-channel frames
@@ -347,35 +321,15 @@ void gen_frame_grads(ctx_handle* h, int B) {
 }
 
 void gen_backward(ctx_handle* h, int B, int sim_batch) {
-    g_zeros = h->zeros;
     GenState& r = *h->gen;
     const float* P = h->arena;
     float* G = h->arena + h->Ppad;
     const int Fp = r.Fp, D0p = (int)r.D0p, F = h->F;
     const bool drop = gen_drop(h);
-    seed_grads(h, B, sim_batch, r.dsim2, Fp, F);
+    seed_grads(h, B, sim_batch, h->dsim2, Fp, F);
     if (r.C0 == 3 && !h->rt.direct3) pack_c4(h, h->dout, 2ll * B * h->H * h->W);
-    // ---- decoder, both passes (2B)
-    const float* dy = h->dout;
-    for (int k = 4; k >= 1; --k) {
-        const int gi = 4 - k;
-        const Geo g = gen_geo(r, gi);
-        const int ch = r.cp[gi], ca = r.in_ch(gi);
-        const std::string nm_ = "deconv/d_h" + std::to_string(k);
-        // (with dropout d_h1 was fed dz * M6: the same sign as dz wherever M6 > 0, so it also serves as the lrelu' reference; the
-        // gradient is multiplied by M6 after the launch -- the two factors commute)
-        const float* dec_in = k > 1 ? r.e[k - 1] : (drop ? r.dzd : r.dz);
-        float* d_dec = k > 1 ? r.dE[k - 1] : r.dDz;
-        // filter gradient dw[tap][a = deconv output channel][b = channel of [decoder | skip]]
-        { Side sd(h, LANE_DW);
-          wgrad(h, nm_, g, dy, ca, Cat{dec_in, ch, r.a[gi] + 2ll * B * g.hs * g.ws * ch, ch, B}, 2 * B, G + r.dw[k], G + r.db[k], r.narrow); }
-        // input gradient of a conv2d_transpose (any stride) = the SAME conv2d of dy with the filter read [K,K,ca,cb]
-        Epi ed;
-        ed.out1 = d_dec; ed.ld1 = ch; ed.nsplit = ch; ed.mask = dec_in; ed.ldm = ch; ed.out2 = r.dSk[gi]; ed.ld2 = ch;
-        conv(h, nm_ + " dx", g, dy, ca, 2 * B, P + r.dw[k], 2 * ch, ed, r.narrow);
-        dy = d_dec;
-    }
-    if (drop) ew_mul(h->stream, r.dDz, D0p, r.dDz, D0p, r.dM[6], D0p, 2 * B, D0p);       // site 6
+    // ---- decoder, both passes (2B): the ctx skips are the last third of the encoder batch
+    decoder_bwd(h, B, r.a, 2 * B, drop);
     // image ranges.  Weights (and filter gradients): one encoder -> all 3B rows at once; two -> `conv` on [0,2B), `conv_context`
     // on [2B,3B).  Input gradients: rows of tgt/src images have no skip term, ctx rows add both decoder passes' skip gradients.
     struct Part { int img0, nimg, set; bool skips; };   // images [img0, img0 + nimg) of [tgt | src | ctx] through encoder `set`
@@ -391,46 +345,15 @@ void gen_backward(ctx_handle* h, int B, int sim_batch) {
         gen_rchain_weights(h, P, W);
         const double fdx = 2.0 * ((double)2 * B * D0p * Fp + (double)B * 3 * Fp * Fp + (double)3 * B * (Fp + D0p) * Fp);
         { ProfScope ps(h, "d_h0_lin .. h4_lin dx", K_RCHAIN, fdx);
-          rchain_bwd(h->stream, B, D0p, r.dDz, r.dsim2, h->dZ, r.dth0, r.dA[4], r.dA[3], h->Z, r.th0, r.a[4], r.a[3], r.dSk[3], W); }
+          rchain_bwd(h->stream, B, D0p, h->dDz, h->dsim2, h->dZ, h->dth0, r.dA[4], r.dA[3], h->Z, h->th0, r.a[4], r.a[3], h->dSk[3], W); }
         { Side sd(h, LANE_DW);
           float* Gp[10];
           { const float* Wg[10]; gen_rchain_weights(h, G, Wg); for (int i = 0; i < 10; ++i) Gp[i] = const_cast<float*>(Wg[i]); }
           ProfScope ps(h, "h4_lin .. d_h0_lin dw db", K_RCHAIN, fdx);
-          rchain_dw(h->stream, B, D0p, r.a[3], r.a[4], h->Z, r.th0, r.dA[4], h->dZ, r.dth0, r.dDz, Gp); }
+          rchain_dw(h->stream, B, D0p, r.a[3], r.a[4], h->Z, h->th0, r.dA[4], h->dZ, h->dth0, h->dDz, Gp); }
         fire_bucket(h, r.th0w);
     } else {
-    {
-        { Side sd(h, LANE_DW); fc_dw(h, "deconv/d_h0_lin", nm(drop ? r.zd : h->Z, Fp, Fp, 2 * B), Fp, r.dDz, 2 * B, D0p, G + r.d0w, G + r.d0b); }
-        Epi ep;
-        ep.out1 = h->dZ; ep.ld1 = Fp;
-        if (!drop) { ep.add1 = r.dsim2; ep.lda1 = Fp; }
-        fc_dx(h, "deconv/d_h0_lin", r.dDz, 2 * B, D0p, P + r.d0w, Fp, ep);
-        // site 5: d z = (d_h0_lin's input gradient) * M5 + the simloss seed, which sees the un-dropped codes
-        if (drop) drop_fin(h->stream, h->dZ, h->dZ, r.dM[5], r.dsim2, nullptr, nullptr, 2ll * B * Fp);
-    }
-    float* src_z = h->Z + 2ll * B * Fp;
-    float* ctx_z = h->Z + 3ll * B * Fp;
-    {
-        { Side sd(h, LANE_DW); fc_dw(h, "translate/trans_z", nm(drop ? r.th0d : r.th0, Fp, Fp, B), Fp, h->dZ, B, Fp, G + r.tzw, G + r.tzb); }
-        Epi e1;
-        e1.out1 = r.dth0; e1.ld1 = Fp; e1.mask = r.th0; e1.ldm = Fp;
-        fc_dx(h, "translate/trans_z", h->dZ, B, Fp, P + r.tzw, Fp, e1);
-        if (drop) ew_mul(h->stream, r.dth0, Fp, r.dth0, Fp, r.dM[4], Fp, B, Fp);          // site 4
-        {
-            Side sd(h, LANE_DW);
-            if (drop) fc_dw(h, "translate/trans_h0", nm(r.xcat, 2 * Fp, 2 * Fp, B), 2 * Fp, r.dth0, B, Fp, G + r.th0w, G + r.th0b);
-            else fc_dw(h, "translate/trans_h0", NmPlain2{src_z, Fp, ctx_z, Fp, Fp, 2 * Fp, B, g_zeros}, 2 * Fp, r.dth0, B, Fp, G + r.th0w, G + r.th0b);
-        }
-        Epi e2;   // d concat: cols < Fp -> d src_z (row block 2), cols >= Fp -> d ctx_z (row block 3)
-        e2.out1 = h->dZ + 2ll * B * Fp; e2.ld1 = Fp; e2.nsplit = Fp; e2.out2 = h->dZ + 3ll * B * Fp; e2.ld2 = Fp;
-        fc_dx(h, "translate/trans_h0", r.dth0, B, Fp, P + r.th0w, 2 * Fp, e2);
-        if (drop) {                                                                        // site 3, both halves of the concat
-            ew_mul(h->stream, h->dZ + 2ll * B * Fp, Fp, h->dZ + 2ll * B * Fp, Fp, r.dM[3], 2 * Fp, B, Fp);
-            ew_mul(h->stream, h->dZ + 3ll * B * Fp, Fp, h->dZ + 3ll * B * Fp, Fp, r.dM[3] + Fp, 2 * Fp, B, Fp);
-        }
-        seed_input_z(h, B, Fp);
-    }
-    fire_bucket(h, r.th0w);
+    fc_middle_bwd(h, B, h->Z + 3ll * B * Fp, h->dZ + 3ll * B * Fp, drop);     // ctx_z, d ctx_z: row block 3
     // ---- encoders over [tgt | src | ctx] (3B); every z has an lrelu
     const int n3 = 3 * B;
     float* dSz = h->dZ + (int64_t)B * Fp;
@@ -446,7 +369,7 @@ void gen_backward(ctx_handle* h, int B, int sim_batch) {
         e4.out1 = r.dA[4] + (int64_t)q.img0 * Fp; e4.ld1 = Fp; e4.mask = r.a[4] + (int64_t)q.img0 * Fp; e4.ldm = Fp;
         fc_dx(h, scn(q.set) + "/hz_lin", dSz + (int64_t)q.img0 * Fp, q.nimg, Fp, P + r.wz[q.set], Fp, e4);
     }
-    if (drop) ew_mul(h->stream, r.dA[4], Fp, r.dA[4], Fp, r.dM[2], Fp, n3, Fp);             // site 2 (commutes with lrelu' of h4)
+    if (drop) ew_mul(h->stream, r.dA[4], Fp, r.dA[4], Fp, h->dM[2], Fp, n3, Fp);             // site 2 (commutes with lrelu' of h4)
     for (int i = 0; i < r.nset; ++i) {
         const Part& q = wparts[i];
         Side sd(h, LANE_DW);
@@ -459,12 +382,12 @@ void gen_backward(ctx_handle* h, int B, int sim_batch) {
         if (drop) {     // site 1: d h3 = ((h4_lin's input gradient) * M1 + the skip gradients) * lrelu'(h3): the product comes first
             e3.out1 = r.graw + o3; e3.ld1 = D0p;
             fc_dx(h, scn(q.set) + "/h4_lin", r.dA[4] + (int64_t)q.img0 * Fp, q.nimg, Fp, P + r.w4[q.set], D0p, e3);
-            drop_fin(h->stream, r.dA[3] + o3, r.graw + o3, r.dM[1] + o3, q.skips ? r.dSk[3] : nullptr,
-                     q.skips ? r.dSk[3] + (int64_t)B * D0p : nullptr, r.a[3] + o3, (int64_t)q.nimg * D0p);
+            drop_fin(h->stream, r.dA[3] + o3, r.graw + o3, h->dM[1] + o3, q.skips ? h->dSk[3] : nullptr,
+                     q.skips ? h->dSk[3] + (int64_t)B * D0p : nullptr, r.a[3] + o3, (int64_t)q.nimg * D0p);
             continue;
         }
         e3.out1 = r.dA[3] + o3; e3.ld1 = D0p; e3.mask = r.a[3] + o3; e3.ldm = D0p;
-        if (q.skips) { e3.add1 = r.dSk[3]; e3.lda1 = D0p; e3.add2 = r.dSk[3] + (int64_t)B * D0p; e3.lda2 = D0p; }
+        if (q.skips) { e3.add1 = h->dSk[3]; e3.lda1 = D0p; e3.add2 = h->dSk[3] + (int64_t)B * D0p; e3.lda2 = D0p; }
         fc_dx(h, scn(q.set) + "/h4_lin", r.dA[4] + (int64_t)q.img0 * Fp, q.nimg, Fp, P + r.w4[q.set], D0p, e3);
     }
     }   // (!chain)
@@ -488,7 +411,7 @@ void gen_backward(ctx_handle* h, int B, int sim_batch) {
             const int64_t bo = (int64_t)q.img0 * g.hb * g.wb * ca;
             Epi ed;
             ed.out1 = r.dA[k - 1] + bo; ed.ld1 = ca; ed.mask = r.a[k - 1] + bo; ed.ldm = ca;
-            if (q.skips) { ed.add1 = r.dSk[k - 1]; ed.lda1 = ca; ed.add2 = r.dSk[k - 1] + (int64_t)B * g.hb * g.wb * ca; ed.lda2 = ca; }
+            if (q.skips) { ed.add1 = h->dSk[k - 1]; ed.lda1 = ca; ed.add2 = h->dSk[k - 1] + (int64_t)B * g.hb * g.wb * ca; ed.lda2 = ca; }
             convt(h, scn(q.set) + "/h" + std::to_string(k) + "_conv dx", g, dyk(q), q.nimg, P + r.w[q.set][k], ca, ed, r.narrow, false);
         }
     }
