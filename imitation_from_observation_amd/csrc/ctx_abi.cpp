@@ -879,6 +879,44 @@ int ctx_dev_adam(ctx_handle* h, float lr) {
     return CTX_OK;
 }
 
+// ---- guarded Adam (include/ctxtrans.h; the launches: ctx_engine.cpp adam_end) ----------------------------------------------------
+int ctx_set_grad_guard(ctx_handle* h, float clip_norm, int skip_nonfinite) {
+    if (!h) return CTX_E_INVALID;
+    if (!(clip_norm >= 0.f)) return fail(h, CTX_E_INVALID, "clip_norm must be >= 0 (0 = no clipping)");      // (NaN fails the comparison)
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (clip_norm > 0.f || skip_nonfinite) TRY(guard_alloc(h));
+    if (h->guard_ctl) HIP_TRY(h, hipMemsetAsync(h->guard_ctl, 0, sizeof(GuardCtl), h->stream));      // statistics count from here
+    h->guard_clip = clip_norm;
+    h->guard_skip = skip_nonfinite != 0;
+    return CTX_OK;
+}
+
+int ctx_grad_norm(ctx_handle* h, double* norm) {
+    if (!h || !norm) return CTX_E_INVALID;
+    if (!h->have_grads) return fail(h, CTX_E_STATE, "ctx_grad_norm before any backward");
+    HIP_TRY(h, hipSetDevice(h->device));
+    TRY(guard_alloc(h));
+    guard_enqueue(h, 1, 0.f, false, false);
+    GuardCtl c;
+    HIP_TRY(h, hipMemcpyAsync(&c, h->guard_ctl + 1, sizeof c, hipMemcpyDeviceToHost, h->stream));
+    TRY(finish(h));
+    *norm = c.norm;
+    return CTX_OK;
+}
+
+int ctx_grad_guard_stats(ctx_handle* h, double* last_norm, float* last_factor, int64_t* steps_skipped, int64_t* steps_clipped) {
+    if (!h) return CTX_E_INVALID;
+    HIP_TRY(h, hipSetDevice(h->device));
+    GuardCtl c{};
+    if (h->guard_ctl) HIP_TRY(h, hipMemcpyAsync(&c, h->guard_ctl, sizeof c, hipMemcpyDeviceToHost, h->stream));
+    TRY(finish(h));
+    if (last_norm) *last_norm = c.norm;
+    if (last_factor) *last_factor = c.factor;
+    if (steps_skipped) *steps_skipped = c.steps_skipped;
+    if (steps_clipped) *steps_clipped = c.steps_clipped;
+    return CTX_OK;
+}
+
 int ctx_dev_scalars(ctx_handle* h, float scalars[4]) {
     if (!h || !scalars) return CTX_E_INVALID;
     HIP_TRY(h, hipSetDevice(h->device));

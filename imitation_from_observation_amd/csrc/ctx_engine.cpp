@@ -319,8 +319,9 @@ struct Side {
 // loses another 0.05 ms, but ContextAEReal's small launches then run truly side by side and get slower (2.71 -> 3.11 ms), so the
 // library does not ask for it (profiles/archive/round4_e_early_adam_queues.txt).  ON by default (option "early_adam"; read at every step).
 void adam_launch(ctx_handle* h, hipStream_t s, int64_t first, int64_t end) {
-    adam(s, h->arena + first, h->arena + h->Ppad + first, h->arena + 2 * h->Ppad + first, h->arena + 3 * h->Ppad + first, end - first,
-         h->adam_lr_t, 0.9f, 0.999f, 1e-8f);
+    float *p = h->arena + first, *g = p + h->Ppad, *m = g + h->Ppad, *v = m + h->Ppad;
+    if (guard_on(h)) adam_guarded(s, p, g, m, v, end - first, h->adam_lr_t, 0.9f, 0.999f, 1e-8f, h->guard_ctl);   // (ctx_set_grad_guard, below)
+    else adam(s, p, g, m, v, end - first, h->adam_lr_t, 0.9f, 0.999f, 1e-8f);
 }
 void adam_begin(ctx_handle* h, float lr) {
     const bool env_on = h->opt.v[OPT_EARLY_ADAM] != 0;
@@ -331,7 +332,36 @@ void adam_begin(ctx_handle* h, float lr) {
     h->pack.version++;               // the parameters change in this step: packed filters are stale from here on
     // (only where the update is worth hiding: ContextAEReal's 1.2 M parameters are a 7 us update, and the slices' events and queue hops
     // among its 5-30 us launches cost 0.4 ms of a 2.6 ms step -- bench.py's secondary leg against forward_backward + adam on one box: 3.00 -> 2.58 ms, round 5)
-    h->adam_early_on = env_on && h->adam_stream && use_lanes(h) && h->P >= (4ll << 20);
+    // (and never under a guard: the clip factor and the skip decision exist only after the last gradient is written)
+    h->adam_early_on = env_on && h->adam_stream && use_lanes(h) && h->P >= (4ll << 20) && !guard_on(h);
+}
+
+// ---- guarded Adam (ctx_set_grad_guard) ---------------------------------------------------------------
+// One more HBM pass beside Adam's seven: the sum of squares of the gradient arena in f64, then one block that turns it into {norm, clip
+// factor, apply} in device memory, which adam_guarded_kernel reads -- nothing returns to the host.  The sum covers exactly the floats
+// Adam updates that a backward writes: ContextSkipNew's arena is dense over [0, P); the table-driven engine's holds channel-padded
+// tensors whose pad gradients are exact zeros (ctxtrans_gen.inc) up to the end of its last tensor, and at most 3 floats between two
+// tensors that stay the zeros of ctx_create.  [that end, Ppad) belongs to no tensor and stays out.
+// The loads of the sum are PLAIN.  MEASURED (profiles/grad_guard.txt): the nontemporal form reads 3 % faster (31.1 against 32.4 us for
+// ContextSkipNew's 190 MB) but the Adam launch behind it then takes 262 us instead of 224 -- the gradient arena fits the Infinity Cache and
+// a plain read leaves it there for Adam -- and the step 0.04 ms longer.  The other form is a build with EXTRA=-DCTX_GUARD_NT=1, which
+// tools/bench_grad_guard.py --lib measures.
+#ifndef CTX_GUARD_NT
+#define CTX_GUARD_NT 0
+#endif
+constexpr bool GUARD_NT = CTX_GUARD_NT != 0;
+int guard_alloc(ctx_handle* h) {
+    if (h->guard_ctl) return CTX_OK;
+    TRY(dev_alloc(h, &h->guard_part, GUARD_BLOCKS));
+    GuardCtl* c = nullptr;
+    TRY(dev_alloc(h, &c, 2));
+    HIP_TRY(h, hipMemsetAsync(c, 0, 2 * sizeof(GuardCtl), h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->guard_ctl = c;
+    return CTX_OK;
+}
+void guard_enqueue(ctx_handle* h, int which, float clip, bool skip, bool count) {
+    grad_guard(h->stream, h->arena + h->Ppad, h->gen ? h->gen->pend : h->P, h->guard_part, h->guard_ctl + which, clip, skip, count, GUARD_NT);
 }
 // [first, end) is final in the order of the CURRENT stream plus (lane >= 0) of that side lane
 void adam_early(ctx_handle* h, int64_t first, int64_t end, int lane) {
@@ -349,6 +379,8 @@ void adam_end(ctx_handle* h) {
     std::sort(h->adam_done.begin(), h->adam_done.end());
     int64_t at = 0;
     ProfScope ps(h, "adam", "adam", 0.0);
+    // under a guard no slice went early (adam_begin): the norm and the control block first, then one guarded launch over the whole arena
+    if (guard_on(h)) guard_enqueue(h, 0, h->guard_clip, h->guard_skip, true);
     for (size_t i = 0; i <= h->adam_done.size(); ++i) {
         const int64_t stop = i < h->adam_done.size() ? h->adam_done[i].first : h->Ppad;
         if (stop > at) adam_launch(h, h->stream, at, stop);

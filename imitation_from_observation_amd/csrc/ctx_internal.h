@@ -71,6 +71,7 @@ struct GenState {
     struct Seg { int64_t roff, poff, size, map0; };   // map0 < 0: contiguous copy; else real2pad[map0 + i]
     std::vector<Seg> segs;
     std::vector<int32_t> real2pad;
+    int64_t pend = 0;            // end of the last tensor in the padded arena: [pend, Ppad) belongs to no tensor and no backward writes it
     // padded parameter offsets (floats into the arena), per encoder set
     int64_t w[2][4], b[2][4], w4[2], b4[2], wz[2], bz[2], th0w, th0b, tzw, tzb, d0w, d0b, dw[5], db[5];
     // ---- activations (NHWC, cp[k] channels) and their gradients
@@ -235,6 +236,12 @@ struct ctx_handle {
     bool adam_early_on = false;
     float adam_lr_t = 0.f;
     std::vector<std::pair<int64_t, int64_t>> adam_done;   // [first, end) slices already enqueued in this step
+    // guarded Adam (ctx_set_grad_guard; off = both zero: no extra launch): adam_end takes the gradient norm first and Adam reads the clip
+    // factor / the skip decision from guard_ctl[0].  guard_ctl[1] is ctx_grad_norm's own block.  Allocated at the first use (guard_alloc).
+    float guard_clip = 0.f;
+    bool guard_skip = false;
+    double* guard_part = nullptr;     // [GUARD_BLOCKS] block partials of the sum of squares
+    GuardCtl* guard_ctl = nullptr;    // [2]
     // tf.nn.dropout (CTX_VARIANT_REAL with keep_prob < 1): on only while a TRAINING step (forward + backward) is being enqueued
     bool drop_on = false;
     uint64_t drop_seed = 0;
@@ -298,6 +305,9 @@ void gen_plan(ctx_handle* h);
 bool use_lanes(const ctx_handle* h);
 void adam_begin(ctx_handle* h, float lr);
 void adam_end(ctx_handle* h);
+inline bool guard_on(const ctx_handle* h) { return h->guard_clip > 0.f || h->guard_skip; }
+int guard_alloc(ctx_handle* h);
+void guard_enqueue(ctx_handle* h, int which, float clip, bool skip, bool count);   // norm of the gradient arena -> guard_ctl[which]
 bool d_h4_direct(const ctx_handle* h, int c1, int c2, int hs, int ws, int stride);
 void join(ctx_handle* h, int lane);
 void fork(ctx_handle* h, int lane);

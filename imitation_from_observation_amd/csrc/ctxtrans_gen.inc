@@ -139,6 +139,7 @@ int gen_layout(const ctx_config& c, GenState& r, std::vector<ParamInfo>& real, i
         add("deconv/d_h" + std::to_string(k) + "/biases", {cout}, {coutp}, nullptr, &r.db[k]);
     }
     P = offr;
+    r.pend = offp;
     Ppadded = round_up(offp, 64);
     return CTX_OK;
 }

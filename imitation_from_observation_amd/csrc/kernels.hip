@@ -1438,4 +1438,103 @@ void adam(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n
     hipLaunchKernelGGL(adam_kernel, dim3(ew_blocks(n / 4)), dim3(NTHREADS), 0, s, p, g, m, v, n, lr_t, b1, b2, eps);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Guarded Adam (ctx_set_grad_guard): sum of g^2 -> {norm, clip factor, apply} in device memory -> Adam on g * factor, or nothing.
+// Every square and every sum is f64: the square of an f32 is exact there and a finite f32 gradient cannot overflow the sum, so
+// "the sum is non-finite" <=> "some gradient element is".  The order of the sum is fixed by GUARD_BLOCKS, not by the device: a thread
+// adds its grid-strided floats in index order, a wave64 tree joins the lanes, thread 0 adds the four wave sums in order and stores
+// the block's partial; grad_guard_final_kernel adds the partials in index order.  No atomics, no last-block hand-over.
+// ------------------------------------------------------------------------------------------------
+template <bool NT>
+__global__ __launch_bounds__(NTHREADS) void grad_sumsq_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ part) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const f4* g4 = reinterpret_cast<const f4*>(g);
+    const int64_t n4 = n >> 2, stride = (int64_t)GUARD_BLOCKS * NTHREADS;
+    auto ld = [&](int64_t i) { return NT ? __builtin_nontemporal_load(g4 + i) : g4[i]; };
+    double acc = 0.0;
+    int64_t i = (int64_t)blockIdx.x * NTHREADS + threadIdx.x;
+    for (; i + 3 * stride < n4; i += 4 * stride) {      // four 16-byte loads in flight per thread, added in index order
+        f4 a[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a[k] = ld(i + k * stride);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { const double x = (double)a[k][j]; acc = fma(x, x, acc); }
+    }
+    for (; i < n4; i += stride) {
+        const f4 a = ld(i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const double x = (double)a[j]; acc = fma(x, x, acc); }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)            // n % 4 floats past the last whole 16 bytes
+        for (int64_t j = n4 * 4; j < n; ++j) { const double x = (double)g[j]; acc = fma(x, x, acc); }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    __shared__ double ws[NTHREADS / 64];
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+}
+
+__global__ __launch_bounds__(NTHREADS) void grad_guard_final_kernel(const double* __restrict__ part, GuardCtl* __restrict__ ctl, float clip,
+                                                                    int skip_nonfinite, int count) {
+    __shared__ double sp[GUARD_BLOCKS];
+    for (int i = threadIdx.x; i < GUARD_BLOCKS; i += NTHREADS) sp[i] = part[i];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double s = 0.0;
+    for (int i = 0; i < GUARD_BLOCKS; ++i) s += sp[i];
+    const double norm = sqrt(s), c = (double)clip;
+    const bool finite = isfinite(s);
+    const bool clipped = finite && c > 0.0 && norm > c;         // norm <= clip, or no clip: factor is exactly 1
+    const uint32_t apply = skip_nonfinite && !finite ? 0u : 1u;
+    ctl->sumsq = s;
+    ctl->norm = norm;
+    ctl->factor = clipped ? (float)(c / norm) : 1.f;
+    ctl->apply = apply;
+    if (count) {
+        ctl->steps_skipped += apply ? 0 : 1;
+        ctl->steps_clipped += clipped ? 1 : 0;
+    }
+}
+
+__global__ __launch_bounds__(NTHREADS) void adam_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                float* __restrict__ v, int64_t n, float lr_t, float b1, float b2,
+                                                                float eps, const GuardCtl* __restrict__ ctl) {
+    if (ctl->apply == 0) return;      // (uniform) a skipped step reads and writes nothing
+    const float factor = ctl->factor, c1 = 1.f - b1, c2 = 1.f - b2;
+    // adam_kernel's accesses and adam_kernel's arithmetic on g * factor.  The two fmaf are the contractions the compiler makes of
+    // adam_kernel's  b1 m + c1 g  and  b2 v + c2 (g g)  (its ISA: v_pk_mul c1 g, v_pk_fma b1 m; v_pk_mul g g, v_pk_mul c2 ., v_pk_fma
+    // b2 v); they are spelled out here because the extra multiply in front changed which product the compiler fused.  With factor = 1
+    // the update equals adam_kernel's bit for bit (tests/test_gpu_grad_guard.py holds the two against each other).
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    for (int64_t i = ((int64_t)blockIdx.x * NTHREADS + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * 256 * 4) {
+        const f4 gg = __builtin_nontemporal_load(reinterpret_cast<const f4*>(g + i)) * factor;
+        f4 mm = __builtin_nontemporal_load(reinterpret_cast<const f4*>(m + i));
+        f4 vv = __builtin_nontemporal_load(reinterpret_cast<const f4*>(v + i));
+        f4 pp = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p + i));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            mm[k] = __builtin_fmaf(b1, mm[k], c1 * gg[k]);
+            vv[k] = __builtin_fmaf(b2, vv[k], c2 * (gg[k] * gg[k]));
+            pp[k] = pp[k] - lr_t * mm[k] / (sqrtf(vv[k]) + eps);
+        }
+        __builtin_nontemporal_store(mm, reinterpret_cast<f4*>(m + i));
+        __builtin_nontemporal_store(vv, reinterpret_cast<f4*>(v + i));
+        __builtin_nontemporal_store(pp, reinterpret_cast<f4*>(p + i));
+    }
+}
+
+void grad_guard(hipStream_t s, const float* g, int64_t n, double* part, GuardCtl* ctl, float clip, int skip_nonfinite, int count,
+                bool nontemporal) {
+    if (nontemporal) hipLaunchKernelGGL((grad_sumsq_kernel<true>), dim3(GUARD_BLOCKS), dim3(NTHREADS), 0, s, g, n, part);
+    else hipLaunchKernelGGL((grad_sumsq_kernel<false>), dim3(GUARD_BLOCKS), dim3(NTHREADS), 0, s, g, n, part);
+    hipLaunchKernelGGL(grad_guard_final_kernel, dim3(1), dim3(NTHREADS), 0, s, part, ctl, clip, skip_nonfinite, count);
+}
+
+void adam_guarded(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float b1, float b2, float eps,
+                  const GuardCtl* ctl) {
+    hipLaunchKernelGGL(adam_guarded_kernel, dim3(ew_blocks(n / 4)), dim3(NTHREADS), 0, s, p, g, m, v, n, lr_t, b1, b2, eps, ctl);
+}
+
 }  // namespace ctx

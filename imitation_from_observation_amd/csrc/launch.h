@@ -262,4 +262,18 @@ void lrelu_mask(hipStream_t s, float* g, const float* act, int64_t n);
 void adam(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float b1, float b2,
           float eps);
 
+// Guarded Adam (ctx_set_grad_guard).  grad_guard: sum of g[0, n)^2 in f64 through `part` (GUARD_BLOCKS doubles), then {norm, factor,
+// apply} and -- `count` -- the counters into *ctl; adam_guarded: adam() on g * ctl->factor, or nothing at all when ctl->apply == 0.
+constexpr int GUARD_BLOCKS = 1024;   // grid of the sum: a constant, so that the order of the sum (the bits of the norm) is the same on every device
+struct GuardCtl {
+    double sumsq, norm;
+    float factor;
+    uint32_t apply;
+    int64_t steps_skipped, steps_clipped;
+};
+void grad_guard(hipStream_t s, const float* g, int64_t n, double* part, GuardCtl* ctl, float clip, int skip_nonfinite, int count,
+                bool nontemporal);
+void adam_guarded(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float b1, float b2, float eps,
+                  const GuardCtl* ctl);
+
 }  // namespace ctx

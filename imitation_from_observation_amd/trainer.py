@@ -101,7 +101,8 @@ class ModelTrainer:
 
     def __init__(self, idims, nvideos, ntrain, batch_size, model, nitr, save_every, nlen, nskip, rescale=True, inception=False,
                  strides=None, kernels=None, filters=None, *, vdata=None, basedir="model/", device=0, seed=0, translator=None,
-                 precision=None, log=print, rank=0, world=1, dp_unique_id=None, videos=None, device_resize=False):
+                 precision=None, log=print, rank=0, world=1, dp_unique_id=None, videos=None, device_resize=False,
+                 grad_clip=None, skip_nonfinite=False):
         """The reference's 14 positional arguments (train_script.py:29-30; the launchers omit the last five, SURVEY.md 3.4-b,
         hence the defaults), then: vdata (array or .npy path of the demo tensor), basedir (logger._snapshot_dir), device,
         seed of the parameter initialiser, an optional ready-made translator (tests), the arithmetic (precision: "f32" | "bf16x3" | "fp16x3" | "fp16x3d",
@@ -110,7 +111,10 @@ class ModelTrainer:
         dp_unique_id: the 128-byte blob of Translator.dp_unique_id() made on rank 0 and shipped to every rank by the launcher (omitted:
         broadcast through an initialised torch.distributed group; not needed when `translator` already went through dp_init).
         device_resize: with `videos=`, the demo frames are resized on the device (demo_pipeline.device_resize: the same bytes as the
-        host resize, one call per video) instead of on the host."""
+        host resize, one call per video) instead of on the host.
+        grad_clip / skip_nonfinite: Translator.set_grad_guard -- clip every step's gradient by its global norm (data parallel: of the
+        reduced gradient), leave parameters and Adam moments untouched on a step whose gradient is non-finite (one extra log line
+        then).  Defaults: no guard, logs and checkpoints as without these keywords."""
         if model not in self.MODELS:
             raise ValueError(f"model must be one of {sorted(self.MODELS)}")
         self.idims, self.nvideos, self.ntrain, self.batch_size = tuple(idims), nvideos, ntrain, batch_size
@@ -119,6 +123,7 @@ class ModelTrainer:
         self.strides, self.kernels, self.filters = strides, kernels, filters
         self.vdata, self.basedir, self.device, self.seed = vdata, basedir, device, seed
         self.device_resize = bool(device_resize)
+        self.grad_clip, self.skip_nonfinite = grad_clip, bool(skip_nonfinite)
         self.videos = videos       # decoded demo videos (arrays [51, H, W, 3] uint8 or callables returning them): train_script.py:59-96
         self.translator, self.precision, self.log = translator, precision, log
         self.rank, self.world, self.dp_unique_id = int(rank), int(world), dp_unique_id
@@ -266,11 +271,20 @@ class ModelTrainer:
             return ev, tgt
 
         core = getattr(tr, "tr", tr)                               # the Translator inside an InceptionTranslator
+        guarded = self.grad_clip is not None or self.skip_nonfinite
+        if guarded:
+            core.set_grad_guard(self.grad_clip, self.skip_nonfinite)
+        skipped = 0
         rows = []
         for itr in range(1, self.nitr):
             choicesrc = np.random.choice(ntrain, B)
             choicetgt = np.random.choice(ntrain, B)
             sc = train_step(choicesrc, choicetgt)
+            if guarded and self.skip_nonfinite:                # (the step has synchronised for its scalars: the counters are final)
+                now = core.guard_stats()["steps_skipped"]
+                if now > skipped:
+                    skipped = now
+                    log("%s skipped: non-finite gradient, parameters and Adam moments unchanged (%s so far)" % (itr, skipped))
             if itr % 4 == 0:
                 if dp_incep:                                   # the tgt maps exist only on the device, one shard per rank
                     err = int(tr.dp_nn_err(nlen))

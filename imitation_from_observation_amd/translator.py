@@ -646,6 +646,26 @@ class Translator:
     def dev_adam(self, lr=1e-4):
         self._ck(self._lib.ctx_dev_adam(self._h, float(lr)))
 
+    # ------------------------------------------------------------------ guarded Adam (include/ctxtrans.h: ctx_set_grad_guard)
+    def set_grad_guard(self, clip_norm=None, skip_nonfinite=True):
+        """Guard every later Adam update of this handle, on the device: clip the gradient by its global norm (clip_norm; None / 0 =
+        no clipping; tf.clip_by_global_norm) and / or leave parameters and moments untouched when a gradient element is non-finite
+        (skip_nonfinite).  set_grad_guard(None, False) = no guard, the default.  A step that is neither clipped nor skipped is
+        bit-identical to the unguarded one.  The Adam step count advances on a skipped step too (guard_stats()["steps_skipped"])."""
+        self._ck(self._lib.ctx_set_grad_guard(self._h, float(clip_norm or 0.0), int(bool(skip_nonfinite))))
+
+    def grad_norm(self):
+        """Global norm (float64, summed on the device) of the gradients now in the gradient arena.  Synchronises."""
+        n = ctypes.c_double()
+        self._ck(self._lib.ctx_grad_norm(self._h, ctypes.byref(n)))
+        return float(n.value)
+
+    def guard_stats(self):
+        """dict(last_norm, last_factor, steps_skipped, steps_clipped) of the guarded steps since set_grad_guard.  Synchronises."""
+        n, f, sk, cl = ctypes.c_double(), ctypes.c_float(), ctypes.c_int64(), ctypes.c_int64()
+        self._ck(self._lib.ctx_grad_guard_stats(self._h, ctypes.byref(n), ctypes.byref(f), ctypes.byref(sk), ctypes.byref(cl)))
+        return dict(last_norm=float(n.value), last_factor=float(f.value), steps_skipped=int(sk.value), steps_clipped=int(cl.value))
+
     def dev_scalars(self):
         sc = np.empty(4, np.float32)
         self._ck(self._lib.ctx_dev_scalars(self._h, _fp(sc)))

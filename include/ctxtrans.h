@@ -50,7 +50,8 @@ extern "C" {
                                ctx_dp_nn_err, ctx_cnn_demos_upload, ctx_cnn_forward_sampled_dev; ctx_reward_costs_dev, ctx_reward_cache_*,
                                ctx_reward_get_cache, ctx_reward_stats, option reward_split; ctx_resize_*; the device-uint8 forms
                                ctx_resize_u8_dev / _v, ctx_cnn_*_dev_u8, ctx_disc_stream / _data_begin / _reward_paths_dev;
-                               ctx_reconstruct / _f32 / _dev, ctx_reward_costs_recon / _dev */
+                               ctx_reconstruct / _f32 / _dev, ctx_reward_costs_recon / _dev;
+                               ctx_set_grad_guard, ctx_grad_norm, ctx_grad_guard_stats */
 
 enum {
     CTX_OK = 0,
@@ -92,6 +93,11 @@ enum {
  *                      large  an operand with |x| * 64 >= 65520 (|x| >= 1023.75) becomes +-inf in its hi term: the
  *                             product is non-finite and the inf / NaN reaches the scalars or features of that
  *                             call.  A large operand never yields a wrong finite number.
+ *                      after  such a call (here and in CTX_PREC_FP16X3D below, and in any mode after an inf / NaN in a frame)
+ *                             the handle stays usable for INFERENCE calls, which change no state.  A TRAINING step
+ *                             carries the non-finite gradient through Adam into every parameter and both moment
+ *                             arenas -- unless ctx_set_grad_guard(skip_nonfinite) is set, under which that step
+ *                             leaves parameters and moments untouched and the handle stays usable.
  *                    The scale 2^6 is fixed (CTX_PREC_FP16X3D is the form with per-operand scales).
  *   CTX_PREC_FP16X3D the three fp16 terms of CTX_PREC_FP16X3 with a power-of-two scale PER OPERAND of each product launch:
  *                    x * 2^e with e = 14 - floor(log2(largest |x| of that operand)), taken on the device in front of
@@ -401,6 +407,34 @@ int ctx_dev_train_step(ctx_handle* h, const float* d_src, const float* d_ctx, co
 typedef void (*ctx_bucket_fn)(void* user, int bucket, int64_t first, int64_t count);
 int ctx_set_grad_bucket_callback(ctx_handle* h, ctx_bucket_fn fn, void* user);
 int ctx_dev_adam(ctx_handle* h, float lr);
+/* ---- guarded Adam: gradient norm, clip-by-global-norm, skip of a non-finite step, all on the device ----
+ * With a guard set, every Adam update of this handle (ctx_train_step*, ctx_dev_train_step, ctx_dev_adam, ctx_dp_train_step*) is
+ * preceded by one more pass over the gradient arena on the same stream: sum of g^2 in f64 over every float the backward writes
+ * (the square of an f32 is exact in f64 and a finite f32 gradient cannot overflow the f64 sum: the sum is non-finite if and only if
+ * some gradient element is), summed in a fixed order that depends on neither the device nor the batch.  From it, on the device:
+ *   norm    = sqrt(sum)
+ *   factor  = 1 exactly when clip_norm == 0 or norm <= clip_norm (such a step is bit-identical to the unguarded one), else
+ *             (float)(clip_norm / norm) with the division in f64: tf.clip_by_global_norm's  g * clip / max(norm, clip)
+ *   apply   = 0 if skip_nonfinite is set and the sum is non-finite, else 1.  With skip_nonfinite clear a non-finite sum gives
+ *             factor = 1, apply = 1: the unguarded behaviour, poison included.
+ * Adam then reads factor and apply from device memory: apply == 0 reads and writes nothing -- parameters, m and v stay as they were;
+ * otherwise it updates with g * factor.  Nothing returns to the host: a guarded ctx_dev_train_step stays asynchronous.
+ *   - The factor exists only after the last gradient is written, so under a guard the early Adam slices are not used, whatever option
+ *     "early_adam" says (its value is not changed).
+ *   - The step counter behind the bias correction (and the dropout mask step) is host state and advances on a SKIPPED step too: the
+ *     host cannot know of the skip without synchronising.  steps_skipped is the correction for a caller that wants the number of
+ *     applied steps; the scalars of a skipped step are non-finite.
+ *   - Data parallel: the norm is taken on the all-reduced gradient, so every rank computes the same norm, factor and skip decision
+ *     (no extra collective) and replicas stay bit-identical; one rank's NaN makes all ranks skip.
+ * clip_norm == 0: no clipping; clip_norm == 0 and skip_nonfinite == 0: no guard (the default; no extra launch).  NaN or negative
+ * clip_norm: CTX_E_INVALID.  Setting a guard resets the counters. */
+int ctx_set_grad_guard(ctx_handle* h, float clip_norm, int skip_nonfinite);
+/* The global norm of the gradients now in the gradient arena, whether a guard is set or not (the guard's statistics are not touched).
+ * CTX_E_STATE before any backward.  Synchronises the stream. */
+int ctx_grad_norm(ctx_handle* h, double* norm);
+/* norm and factor of the last guarded step and the counts of skipped / clipped steps since ctx_set_grad_guard (zeros before the
+ * first).  Synchronises the stream.  Any pointer may be NULL. */
+int ctx_grad_guard_stats(ctx_handle* h, double* last_norm, float* last_factor, int64_t* steps_skipped, int64_t* steps_clipped);
 /* Synchronises and copies {loss, simloss, recon1, recon2} of the last forward. */
 int ctx_dev_scalars(ctx_handle* h, float scalars[4]);
 /* Device pointer to the parameters (flat, ctx_param_info order).  WRITABLE: a caller may update the weights through it (its own
