@@ -89,7 +89,8 @@ int ctx_create_ex(const ctx_config* cfg, int device, void* stream, void* arena, 
     if (rc == CTX_OK) {
         set_routing(h);
         if (h->gen) gen_plan(h); else skip_plan(h);      // (after the routing: `direct` reads rt.direct3)
-        rc = h->gen ? gen_alloc(h) : alloc_buffers(h);
+        rc = tensor_spans(h);      // every tensor on a 16-byte group of the arena, in both layouts (ctx_set_param_lr_scale's kernels)
+        if (rc == CTX_OK) rc = h->gen ? gen_alloc(h) : alloc_buffers(h);
     }
     // packed-filter cache (dconv.h: DcPackCache): only where the library owns the parameters -- a caller-owned arena (ctx_create_ex) may be
     // written behind the handle's back, there every launch packs as before
@@ -218,7 +219,38 @@ static int arena_io(ctx_handle* h, int slot, float* host, const float* chost, si
 
 int ctx_set_params(ctx_handle* h, const float* flat, size_t n) { return flat ? arena_io(h, 0, nullptr, flat, n) : CTX_E_INVALID; }
 int ctx_get_params(ctx_handle* h, float* flat, size_t n) { return flat ? arena_io(h, 0, flat, nullptr, n) : CTX_E_INVALID; }
-int ctx_get_grads(ctx_handle* h, float* flat, size_t n) { return flat ? arena_io(h, 1, flat, nullptr, n) : CTX_E_INVALID; }
+int ctx_get_grads(ctx_handle* h, float* flat, size_t n) {
+    if (!flat) return CTX_E_INVALID;
+    TRY(arena_io(h, 1, flat, nullptr, n));
+    // a frozen tensor (ctx_set_param_lr_scale) reads as zeros, whether a masked backward left its launch out or not
+    for (size_t i = 0; i < h->lr_scale.size(); ++i)
+        if (h->lr_scale[i] == 0.f) memset(flat + h->params[i].offset, 0, (size_t)h->params[i].size * sizeof(float));
+    return CTX_OK;
+}
+
+// ---- training a subset of the parameters (include/ctxtrans.h; the plan and the launches: ctx_engine.cpp plan_mask, adam_end) ----------
+int ctx_set_param_lr_scale(ctx_handle* h, const float* scale, int n) {
+    if (!h) return CTX_E_INVALID;
+    if (!scale) { h->lr_scale.clear(); plan_mask(h); return CTX_OK; }
+    const int np = (int)h->params.size();
+    if (n != np) return fail(h, CTX_E_INVALID, "expected %d scales (ctx_param_count), got %d", np, n);
+    if (np > ADAM_SEG_MAX || h->Ppad >= (1ll << 32)) return fail(h, CTX_E_INVALID, "the segmented Adam kernel holds %d tensors of an arena below 2^32 floats", ADAM_SEG_MAX);
+    bool ones = true;
+    for (int i = 0; i < n; ++i) {
+        if (!(scale[i] >= 0.f) || !std::isfinite(scale[i])) return fail(h, CTX_E_INVALID, "scale[%d] of %s must be finite and >= 0", i, h->params[i].name.c_str());
+        ones = ones && scale[i] == 1.f;
+    }
+    if (ones) h->lr_scale.clear();       // every tensor at 1 IS no mask: the launches of a handle that never heard of one
+    else h->lr_scale.assign(scale, scale + n);
+    plan_mask(h);
+    return CTX_OK;
+}
+
+int ctx_get_param_lr_scale(const ctx_handle* h, float* scale, int n) {
+    if (!h || !scale || n != (int)h->params.size()) return CTX_E_INVALID;
+    for (int i = 0; i < n; ++i) scale[i] = h->lr_scale.empty() ? 1.f : h->lr_scale[i];
+    return CTX_OK;
+}
 
 int ctx_set_adam_state(ctx_handle* h, const float* m, const float* v, size_t n, int64_t step) {
     if (!h || !m || !v || step < 0) return CTX_E_INVALID;

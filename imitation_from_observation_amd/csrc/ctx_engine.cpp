@@ -40,11 +40,13 @@ struct ProfScope {
             e.useful_frac = (float)useful;
             h->prof_entries.push_back(e);
             h->prof_ms.push_back(0.0);
-            hipEvent_t a, b;
-            (void)hipEventCreate(&a);
-            (void)hipEventCreate(&b);
-            h->prof_ev.push_back(a);
-            h->prof_ev.push_back(b);
+            if ((int)h->prof_ev.size() < 2 * (idx + 1)) {      // (plan_mask drops the entries, not their events)
+                hipEvent_t a, b;
+                (void)hipEventCreate(&a);
+                (void)hipEventCreate(&b);
+                h->prof_ev.push_back(a);
+                h->prof_ev.push_back(b);
+            }
         }
         (void)hipEventRecord(h->prof_ev[2 * idx], h->stream);
     }
@@ -327,13 +329,102 @@ void adam_begin(ctx_handle* h, float lr) {
     const bool env_on = h->opt.v[OPT_EARLY_ADAM] != 0;
     const double b1 = 0.9, b2 = 0.999;
     h->adam_t += 1;
-    h->adam_lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow(b2, (double)h->adam_t)) / (1.0 - std::pow(b1, (double)h->adam_t)));
+    auto lr_t_of = [&](float lr_) { return (float)((double)lr_ * std::sqrt(1.0 - std::pow(b2, (double)h->adam_t)) / (1.0 - std::pow(b1, (double)h->adam_t))); };
+    h->adam_lr_t = lr_t_of(lr);
+    // under a mask every run has its own: the f32 product lr * scale through the same expression, so a tensor at scale s steps exactly
+    // as an unmasked handle steps it at the learning rate float(lr * s)
+    for (int s = 0; s < h->segs.n; ++s) { const float lr_s = lr * h->seg_scale[s]; h->segs.lr_t[s] = lr_t_of(lr_s); }
     h->adam_done.clear();
     h->pack.version++;               // the parameters change in this step: packed filters are stale from here on
     // (only where the update is worth hiding: ContextAEReal's 1.2 M parameters are a 7 us update, and the slices' events and queue hops
     // among its 5-30 us launches cost 0.4 ms of a 2.6 ms step -- bench.py's secondary leg against forward_backward + adam on one box: 3.00 -> 2.58 ms, round 5)
-    // (and never under a guard: the clip factor and the skip decision exist only after the last gradient is written)
-    h->adam_early_on = env_on && h->adam_stream && use_lanes(h) && h->P >= (4ll << 20) && !guard_on(h);
+    // (and never under a guard: the clip factor and the skip decision exist only after the last gradient is written; nor under a
+    // mask: its update is ONE segmented launch at the end of the step)
+    h->adam_early_on = env_on && h->adam_stream && use_lanes(h) && h->P >= (4ll << 20) && !guard_on(h) && !masked(h);
+}
+
+// ---- training a subset of the parameters (ctx_set_param_lr_scale) ------------------------------------------------------------------
+// Tensor i of ctx_param_info owns the arena floats [first, end) up to the next tensor's first (the last: up to the next 16-byte boundary):
+// ContextSkipNew's arena is dense and only its last tensor (deconv/d_h4/biases, 3 floats) is no multiple of 4; the table-driven layout
+// pads every tensor to one.  The segmented kernels work on whole 16-byte groups, so no group may belong to two tensors.
+int tensor_spans(ctx_handle* h) {
+    const size_t n = h->params.size();
+    h->span.resize(n);
+    for (size_t i = 0; i < n; ++i) h->span[i].first = h->gen ? h->gen->segs[i].poff : h->params[i].offset;
+    for (size_t i = 0; i < n; ++i) {
+        h->span[i].second = i + 1 < n ? h->span[i + 1].first : round_up(h->gen ? h->gen->pend : h->P, 4);
+        if (h->span[i].first % 4 || h->span[i].second <= h->span[i].first)
+            return fail(h, CTX_E_INVALID, "parameter %s does not start on a 16-byte group of the arena", h->params[i].name.c_str());
+    }
+    return CTX_OK;
+}
+
+// From h->lr_scale: the trainable runs of the segmented kernels (adjacent tensors of equal scale are one run) and which launch groups
+// a plain backward keeps (Prune, ctx_internal.h).
+void plan_mask(ctx_handle* h) {
+    h->segs = AdamSegs{};
+    h->prune = Prune{};
+    h->prof_entries.clear();         // ctx_profile_step names its entries at their first run: another mask is another sequence
+    h->prof_ms.clear();
+    if (!masked(h)) return;
+    AdamSegs& T = h->segs;
+    uint32_t total = 0;
+    int64_t last_end = -1;
+    for (size_t i = 0; i < h->params.size(); ++i) {
+        const float sc = h->lr_scale[i];
+        if (sc == 0.f) continue;
+        const int64_t g0 = h->span[i].first / 4, g1 = (h->span[i].second + 3) / 4;
+        if (!(T.n && last_end == g0 && h->seg_scale[T.n - 1] == sc)) {
+            T.first[T.n] = (uint32_t)g0; T.pre[T.n] = total; h->seg_scale[T.n] = sc;
+            ++T.n;
+        }
+        total += (uint32_t)(g1 - g0);
+        T.pre[T.n] = total;
+        last_end = g1;
+    }
+    Prune& q = h->prune;
+    q.on = true;
+    auto tr = [&](const std::string& name) {
+        for (size_t i = 0; i < h->params.size(); ++i) if (h->params[i].name == name) return h->lr_scale[i] != 0.f;
+        return false;
+    };
+    for (int k = 1; k <= 4; ++k) { const std::string s = "deconv/d_h" + std::to_string(k); q.dec[k][0] = tr(s + "/w"); q.dec[k][1] = tr(s + "/biases"); }
+    q.d0[0] = tr("deconv/d_h0_lin/Matrix"); q.d0[1] = tr("deconv/d_h0_lin/bias");
+    q.tz[0] = tr("translate/trans_z/Matrix"); q.tz[1] = tr("translate/trans_z/bias");
+    q.th0[0] = tr("translate/trans_h0/Matrix"); q.th0[1] = tr("translate/trans_h0/bias");
+    bool skip_grad[4];               // someone needs d loss / d (ctx skip h_gi): a trainable tensor of conv_context's h0 .. h_gi
+    if (h->gen) {                    // gen_backward's encoder loop is not pruned: it reads every code and skip gradient
+        for (int e = 0; e < 2; ++e) { q.enc_any[e] = true; for (int l = 0; l < 6; ++l) q.enc_dx[e][l] = q.enc[e][l][0] = q.enc[e][l][1] = true; }
+        for (bool& b : skip_grad) b = true;
+    } else {
+        for (int e = 0; e < 2; ++e) {
+            const std::string sc = e ? "conv_context" : "conv";
+            for (int k = 0; k < 4; ++k) { const std::string s = sc + "/h" + std::to_string(k) + "_conv"; q.enc[e][k][0] = tr(s + "/w"); q.enc[e][k][1] = tr(s + "/biases"); }
+            q.enc[e][4][0] = tr(sc + "/h4_lin/Matrix"); q.enc[e][4][1] = tr(sc + "/h4_lin/bias");
+            q.enc[e][5][0] = tr(sc + "/hz_lin/Matrix"); q.enc[e][5][1] = tr(sc + "/hz_lin/bias");
+            bool below = false;      // a trainable tensor in a layer in front of l: l's input gradient has a reader
+            for (int l = 0; l < 6; ++l) { q.enc_dx[e][l] = below; below = below || q.enc[e][l][0] || q.enc[e][l][1]; }
+            q.enc_any[e] = below;
+        }
+        for (int gi = 0; gi < 4; ++gi) skip_grad[gi] = q.enc_dx[1][gi + 1];
+    }
+    // the FC middle, from the encoders back to the decoder: trans_h0's input gradient is d src_z | d ctx_z, trans_z's is d trans_h0,
+    // d_h0_lin's is d [trans_z | tgt_z]
+    q.th0_dx = q.enc_any[0] || q.enc_any[1];
+    q.tz_dx = q.th0[0] || q.th0[1] || q.th0_dx;
+    q.d0_dx = q.tz[0] || q.tz[1] || q.tz_dx || q.enc_any[0];
+    // the decoder, from d_h1 up: d_hk's input gradient is d (output of d_h(k-1)) | d (ctx skip h_(4-k))
+    bool dy = q.d0[0] || q.d0[1] || q.d0_dx;         // d dz has a reader
+    for (int k = 1; k <= 4; ++k) {
+        q.dec_dx[k] = dy || skip_grad[4 - k];
+        dy = q.dec[k][0] || q.dec[k][1] || q.dec_dx[k];
+    }
+    q.pack_dout = q.dec[4][0] || q.dec[4][1] || q.dec_dx[4];
+}
+// the record of a backward that may leave launch groups out: plain backwards only -- a data-parallel step, a bucket callback and a VJP
+// run whole (their readers want every gradient, or gradients the mask knows nothing about)
+const Prune* pruning(const ctx_handle* h) {
+    return h->prune.on && !h->vjp && !h->dp_in_step && !h->dp_comm && !h->bucket_fn ? &h->prune : nullptr;
 }
 
 // ---- guarded Adam (ctx_set_grad_guard) ---------------------------------------------------------------
@@ -361,7 +452,10 @@ int guard_alloc(ctx_handle* h) {
     return CTX_OK;
 }
 void guard_enqueue(ctx_handle* h, int which, float clip, bool skip, bool count) {
-    grad_guard(h->stream, h->arena + h->Ppad, h->gen ? h->gen->pend : h->P, h->guard_part, h->guard_ctl + which, clip, skip, count, GUARD_NT);
+    // under a mask the norm is the trainable tensors': a frozen tensor's gradient (which a pruned backward did not even write) neither
+    // clips nor skips the step
+    if (masked(h)) grad_guard_segmented(h->stream, h->arena + h->Ppad, h->segs, h->gen ? h->gen->pend : h->P, h->guard_part, h->guard_ctl + which, clip, skip, count, GUARD_NT);
+    else grad_guard(h->stream, h->arena + h->Ppad, h->gen ? h->gen->pend : h->P, h->guard_part, h->guard_ctl + which, clip, skip, count, GUARD_NT);
 }
 // [first, end) is final in the order of the CURRENT stream plus (lane >= 0) of that side lane
 void adam_early(ctx_handle* h, int64_t first, int64_t end, int lane) {
@@ -381,7 +475,12 @@ void adam_end(ctx_handle* h) {
     ProfScope ps(h, "adam", "adam", 0.0);
     // under a guard no slice went early (adam_begin): the norm and the control block first, then one guarded launch over the whole arena
     if (guard_on(h)) guard_enqueue(h, 0, h->guard_clip, h->guard_skip, true);
-    for (size_t i = 0; i <= h->adam_done.size(); ++i) {
+    // under a mask no slice went early either: one segmented launch over the trainable runs, each at its own lr_t (adam_begin)
+    if (masked(h)) {
+        float *p = h->arena, *g = p + h->Ppad, *m = g + h->Ppad, *v = m + h->Ppad;
+        adam_segmented(h->stream, p, g, m, v, h->segs, 0.9f, 0.999f, 1e-8f, guard_on(h) ? h->guard_ctl : nullptr);
+    }
+    for (size_t i = 0; !masked(h) && i <= h->adam_done.size(); ++i) {
         const int64_t stop = i < h->adam_done.size() ? h->adam_done[i].first : h->Ppad;
         if (stop > at) adam_launch(h, h->stream, at, stop);
         if (i < h->adam_done.size()) at = h->adam_done[i].second;
@@ -531,15 +630,17 @@ void bias_grad(ctx_handle* h, const std::string& name, const float* dy, int64_t 
 void fc_dw_launch(hipStream_t s, const NmPlain& x, const NmPlain& dy, Epi ep, int K, int N, int nch, SplitWs ws) { gemm_fc_dw(s, x, dy, ep, K, N, nch, ws); }
 void fc_dw_launch(hipStream_t s, const NmPlain2& x, const NmPlain& dy, Epi ep, int K, int N, int nch, SplitWs ws) { gemm_fc_dw2(s, x, dy, ep, K, N, nch, ws); }
 
+// (do_w / do_b: a masked backward leaves out the group whose tensor is frozen -- pruning())
 template <class XL>
-void fc_dw(ctx_handle* h, const std::string& name, const XL& x, int K, const float* dy, int M, int N, float* dw, float* db) {
-    {
+void fc_dw(ctx_handle* h, const std::string& name, const XL& x, int K, const float* dy, int M, int N, float* dw, float* db,
+           bool do_w = true, bool do_b = true) {
+    if (do_w) {
         ProfScope ps(h, name + " dw", K_FCDW, 2.0 * M * K * N);
         Epi ep;
         ep.out1 = dw; ep.ld1 = N;
         fc_dw_launch(h->stream, x, nm(dy, N, N, M), ep, K, N, (M + KC - 1) / KC, ws_of(h));
     }
-    bias_grad(h, name, dy, M, N, db);
+    if (do_b) bias_grad(h, name, dy, M, N, db);
 }
 
 // The conv-type layers of both engines: which kernel runs a launch is decided here and nowhere else, from the layer's geometry, the
@@ -852,6 +953,7 @@ void decoder_fwd(ctx_handle* h, int B, const float* zin, int nd, const float* co
 // d_h4 .. d_h1 backward, both passes at once (2B rows) from h->dout: per layer the filter gradient on the side lane, then the input gradient
 void decoder_bwd(ctx_handle* h, int B, const float* const skip[4], int skip0, bool drop) {
     const DecoderPlan& p = h->dec;
+    const Prune* q = pruning(h);      // a masked plain backward: a group runs iff a trainable tensor's gradient depends on it
     float* G = h->arena + h->Ppad;
     const float* dy = h->dout;
     for (int k = 4; k >= 1; --k) {
@@ -863,8 +965,10 @@ void decoder_bwd(ctx_handle* h, int B, const float* const skip[4], int skip0, bo
         const float* dec_in = k > 1 ? h->e[k - 1] : (drop ? h->dzd : h->dz);
         float* d_dec = k > 1 ? h->dE[k - 1] : h->dDz;
         // filter gradient dw[tap][a = deconv output channel][b = channel of [decoder | skip]]
-        { Side sd(h, LANE_DW);
+        if (!q || q->dec[k][0] || q->dec[k][1]) {
+          Side sd(h, LANE_DW);
           wgrad(h, nm_, p.g[gi], dy, ca, Cat{dec_in, ch, skip[gi] + (int64_t)skip0 * p.g[gi].hs * p.g[gi].ws * ch, ch, B}, 2 * B, G + p.dw[k], G + p.db[k], p.direct[gi]); }
+        if (q && !q->dec_dx[k]) return;      // neither d_h(k-1) .. d_h0_lin and what lies behind them nor the ctx skips' encoder has a trainable tensor
         // input gradient of a conv2d_transpose (any stride) = the SAME conv2d of dy with the filter read [K,K,ca,cb]; cols < ch are the
         // decoder stream (masked by its lrelu), cols >= ch the ctx skip of this pass
         Epi ed;
@@ -883,7 +987,13 @@ void fc_middle_bwd(ctx_handle* h, int B, const float* ctx_z, float* d_ctx_z, boo
     const int F = h->Fp, D0 = (int)h->D0;
     float* d_src_z = h->dZ + 2ll * B * F;
     // d_h0_lin: input Z[0:2B] = [trans_z | tgt_z]; simloss adds +-c(trans_z - tgt_z) to its gradient
-    { Side sd(h, LANE_DW); fc_dw(h, "deconv/d_h0_lin", nm(drop ? h->zd : h->Z, F, F, 2 * B), F, h->dDz, 2 * B, D0, G + p.d0w, G + p.d0b); }
+    // (a masked plain backward: each dw / db group by its own tensor; an input gradient -- and everything behind it -- only while a
+    // trainable tensor lies behind it)
+    const Prune* q = pruning(h);
+    const Prune& Q = h->prune;
+    auto on = [&](const bool t[2], int j) { return !q || t[j]; };
+    if (on(Q.d0, 0) || on(Q.d0, 1)) { Side sd(h, LANE_DW); fc_dw(h, "deconv/d_h0_lin", nm(drop ? h->zd : h->Z, F, F, 2 * B), F, h->dDz, 2 * B, D0, G + p.d0w, G + p.d0b, on(Q.d0, 0), on(Q.d0, 1)); }
+    if (q && !q->d0_dx) { fire_bucket(h, p.th0w); return; }
     Epi ep;
     ep.out1 = h->dZ; ep.ld1 = F;
     if (!drop) { ep.add1 = h->dsim2; ep.lda1 = F; }
@@ -891,16 +1001,18 @@ void fc_middle_bwd(ctx_handle* h, int B, const float* ctx_z, float* d_ctx_z, boo
     // site 5: d z = (d_h0_lin's input gradient) * M5 + the simloss seed, which sees the un-dropped codes
     if (drop) drop_fin(h->stream, h->dZ, h->dZ, h->dM[5], h->dsim2, nullptr, nullptr, 2ll * B * F);
     // translate MLP: d trans_z = dZ[0:B]
-    { Side sd(h, LANE_DW); fc_dw(h, "translate/trans_z", nm(drop ? h->th0d : h->th0, F, F, B), F, h->dZ, B, F, G + p.tzw, G + p.tzb); }
+    if (on(Q.tz, 0) || on(Q.tz, 1)) { Side sd(h, LANE_DW); fc_dw(h, "translate/trans_z", nm(drop ? h->th0d : h->th0, F, F, B), F, h->dZ, B, F, G + p.tzw, G + p.tzb, on(Q.tz, 0), on(Q.tz, 1)); }
+    if (q && !q->tz_dx) { fire_bucket(h, p.th0w); return; }
     Epi e1;
     e1.out1 = h->dth0; e1.ld1 = F; e1.mask = h->th0; e1.ldm = F;
     fc_dx(h, "translate/trans_z", h->dZ, B, F, P + p.tzw, F, e1);
     if (drop) ew_mul(h->stream, h->dth0, F, h->dth0, F, h->dM[4], F, B, F);          // site 4
-    {
+    if (on(Q.th0, 0) || on(Q.th0, 1)) {
         Side sd(h, LANE_DW);
-        if (drop) fc_dw(h, "translate/trans_h0", nm(h->xcat, 2 * F, 2 * F, B), 2 * F, h->dth0, B, F, G + p.th0w, G + p.th0b);
-        else fc_dw(h, "translate/trans_h0", NmPlain2{h->Z + 2ll * B * F, F, ctx_z, F, F, 2 * F, B, g_zeros}, 2 * F, h->dth0, B, F, G + p.th0w, G + p.th0b);
+        if (drop) fc_dw(h, "translate/trans_h0", nm(h->xcat, 2 * F, 2 * F, B), 2 * F, h->dth0, B, F, G + p.th0w, G + p.th0b, on(Q.th0, 0), on(Q.th0, 1));
+        else fc_dw(h, "translate/trans_h0", NmPlain2{h->Z + 2ll * B * F, F, ctx_z, F, F, 2 * F, B, g_zeros}, 2 * F, h->dth0, B, F, G + p.th0w, G + p.th0b, on(Q.th0, 0), on(Q.th0, 1));
     }
+    if (q && !q->th0_dx) { fire_bucket(h, p.th0w); return; }
     Epi e2;   // d concat: cols < F -> d src_z (row block 2 of dZ), cols >= F -> d ctx_z
     e2.out1 = d_src_z; e2.ld1 = F; e2.nsplit = F; e2.out2 = d_ctx_z; e2.ld2 = F;
     fc_dx(h, "translate/trans_h0", h->dth0, B, F, P + p.th0w, 2 * F, e2);
@@ -970,21 +1082,28 @@ void backward(ctx_handle* h, int B, int sim_batch) {
     const int d = h->d, F = h->F;
     const int64_t npi = h->npi;
     float* tgt_z = h->Z + (int64_t)B * F;
+    // a masked plain backward runs a launch group iff a trainable tensor's gradient depends on one of its results (Prune, ctx_internal.h)
+    const Prune* q = pruning(h);
     seed_grads(h, B, sim_batch, h->dsim2, F, 0);
-    if (!h->rt.direct3) pack_c4(h, h->dout, 2ll * B * h->H * h->W);
+    if (!h->rt.direct3 && (!q || q->pack_dout)) pack_c4(h, h->dout, 2ll * B * h->H * h->W);
 
     // ---- decoder (both passes at once, batch 2B) and FC middle
     decoder_bwd(h, B, h->c, 0, false);
     fc_middle_bwd(h, B, h->cz, h->dcz, false);
     // ---- encoders
     auto encoder_bwd = [&](const std::string& scn, const Scope& sc, const float* x, int nimg, float* const act[5], float* dzp, float* const dA[5],
-                           bool with_skips, int dw_lane, int slot0) {
+                           bool with_skips, int dw_lane, int slot0, int e) {
         const int K3 = h->hh[4] * h->ww[4] * 8 * d;
-        { Side sd(h, dw_lane); fc_dw(h, scn + "/hz_lin", nm(act[4], F, F, nimg), F, dzp, nimg, F, sc.gwz, sc.gbz); }
+        // layer l = h0..h3_conv, h4_lin, hz_lin of encoder e: its own gradients [0] filter / Matrix, [1] bias; its input gradient
+        auto on = [&](int l, int j) { return !q || q->enc[e][l][j]; };
+        auto dx = [&](int l) { return !q || q->enc_dx[e][l]; };
+        if (on(5, 0) || on(5, 1)) { Side sd(h, dw_lane); fc_dw(h, scn + "/hz_lin", nm(act[4], F, F, nimg), F, dzp, nimg, F, sc.gwz, sc.gbz, on(5, 0), on(5, 1)); }
+        if (!dx(5)) return;          // (no trainable tensor in front of this layer: nothing reads its input gradient)
         Epi e4;
         e4.out1 = dA[4]; e4.ld1 = F; e4.mask = act[4]; e4.ldm = F;
         fc_dx(h, scn + "/hz_lin", dzp, nimg, F, sc.wz, F, e4);
-        { Side sd(h, dw_lane); fc_dw(h, scn + "/h4_lin", nm(act[3], K3, K3, nimg), K3, dA[4], nimg, F, sc.gw4, sc.gb4); }
+        if (on(4, 0) || on(4, 1)) { Side sd(h, dw_lane); fc_dw(h, scn + "/h4_lin", nm(act[3], K3, K3, nimg), K3, dA[4], nimg, F, sc.gw4, sc.gb4, on(4, 0), on(4, 1)); }
+        if (!dx(4)) return;
         Epi e3;
         e3.out1 = dA[3]; e3.ld1 = K3; e3.mask = act[3]; e3.ldm = K3;
         if (with_skips) { e3.add1 = h->dSk[3]; e3.lda1 = K3; e3.add2 = h->dSk[3] + (int64_t)B * K3; e3.lda2 = K3; }
@@ -998,12 +1117,14 @@ void backward(ctx_handle* h, int B, int sim_batch) {
             const Geo g = h->dec.g[k];
             const int ca = k ? d << (k - 1) : 3, cb = d << k;
             const std::string ln = scn + "/h" + std::to_string(k) + "_conv";
-            { Side sd(h, dw_lane);
+            if (on(k, 0) || on(k, 1)) {
+              Side sd(h, dw_lane);
               wgrad(h, ln, g, k ? act[k - 1] : x, ca, Cat{dA[k], cb}, nimg, sc.gw[k], sc.gb[k], ca == 3 && h->rt.direct3); }
             if (k == 0) {
                 if (h->vjp) frame_grads3(h, dA[0], cb, slot0, nimg, g.hs, g.ws, 2, sc.w[0]);   // (the training step has no frame gradient)
                 break;
             }
+            if (!dx(k)) return;
             // input gradient = conv2d_transpose of dA[k] with the same filter read as [5,5,ca,cb]
             Epi ed;
             ed.out1 = dA[k - 1]; ed.ld1 = ca; ed.mask = act[k - 1]; ed.ldm = ca;
@@ -1017,17 +1138,20 @@ void backward(ctx_handle* h, int B, int sim_batch) {
     // `conv` on [tgt | src]: code gradients are rows [B, 3B) of dZ; hz_lin has an lrelu
     float* dSz = h->dZ + (int64_t)B * F;
     const bool lanes = use_lanes(h);
-    if (lanes) {
+    const bool do_conv = !q || q->enc_any[0], do_ctx = !q || q->enc_any[1];     // (an encoder without a trainable tensor is not entered)
+    if (lanes && do_ctx) {
         // `conv_context` (linear hz_lin; its h0..h3 also fed both decoder passes as skips) on the second lane:
         // everything it reads (dcz, dSk[*], c[*]) was produced before this point
         fork(h, LANE_CTX);
         LaneSwap sw(h, LANE_CTX);
-        encoder_bwd("conv_context", h->enc_ctx, h->img + 2 * B * npi, B, h->c, h->dcz, h->dC, true, -1, 2);
+        encoder_bwd("conv_context", h->enc_ctx, h->img + 2 * B * npi, B, h->c, h->dcz, h->dC, true, -1, 2, 1);
     }
-    { ProfScope ps(h, "conv/hz_lin lrelu'", K_EW, 0.0); lrelu_mask(h->stream, dSz, tgt_z, 2ll * B * F); }
-    encoder_bwd("conv", h->enc_conv, h->img, 2 * B, h->s, dSz, h->dS, false, LANE_DW, 0);
-    if (lanes) { join(h, LANE_CTX); join(h, LANE_DW); }
-    else encoder_bwd("conv_context", h->enc_ctx, h->img + 2 * B * npi, B, h->c, h->dcz, h->dC, true, -1, 2);
+    if (do_conv) {
+        { ProfScope ps(h, "conv/hz_lin lrelu'", K_EW, 0.0); lrelu_mask(h->stream, dSz, tgt_z, 2ll * B * F); }
+        encoder_bwd("conv", h->enc_conv, h->img, 2 * B, h->s, dSz, h->dS, false, LANE_DW, 0, 0);
+    }
+    if (lanes) { if (do_ctx) join(h, LANE_CTX); join(h, LANE_DW); }
+    else if (do_ctx) encoder_bwd("conv_context", h->enc_ctx, h->img + 2 * B * npi, B, h->c, h->dcz, h->dC, true, -1, 2, 1);
     h->have_grads = true;
 
 }

@@ -110,6 +110,19 @@ struct DecoderPlan {
     int64_t th0w, th0b, tzw, tzb, d0w, d0b, dw[5], db[5];   // arena offsets (floats) of translate/*, deconv/d_h0_lin/*, deconv/d_hK/{w,biases}
 };
 
+// Which launch groups of a PLAIN backward a parameter mask (ctx_set_param_lr_scale) leaves: a group runs iff one of its results
+// reaches the gradient of a trainable tensor (plan_mask, ctx_engine.cpp).  [0] = Matrix / filter, [1] = bias of a layer.
+// The encoder records hold ContextSkipNew's two encoders (0 = conv, 1 = conv_context), layers h0..h3_conv, h4_lin, hz_lin = 0..5;
+// the table-driven engine's encoder loop stays whole, so for it every input gradient below is set.
+struct Prune {
+    bool on = false;                 // a mask is set
+    bool dec[5][2] = {}, d0[2] = {}, tz[2] = {}, th0[2] = {};   // own gradients of deconv/d_h1..4, d_h0_lin, translate/*
+    bool enc[2][6][2] = {};
+    bool dec_dx[5] = {}, d0_dx = false, tz_dx = false, th0_dx = false;      // the layer's input-gradient launch
+    bool enc_any[2] = {}, enc_dx[2][6] = {};
+    bool pack_dout = false;          // someone reads the 4-channel copy of d loss / d out
+};
+
 // one ContextSkipNew encoder's parameters and their gradients in the arena (resolved once at create)
 struct Scope {
     float *w[4], *b[4], *w4, *b4, *wz, *bz;
@@ -242,6 +255,14 @@ struct ctx_handle {
     bool guard_skip = false;
     double* guard_part = nullptr;     // [GUARD_BLOCKS] block partials of the sum of squares
     GuardCtl* guard_ctl = nullptr;    // [2]
+    // per-tensor learning-rate scales (ctx_set_param_lr_scale; lr_scale empty = no mask: every launch is the one without this feature).
+    // span[i] = tensor i's floats [first, end) of the arena, end = the next tensor's first: 16-byte groups never straddle two tensors
+    // (checked at create).  segs = the trainable tensors as runs of equal scale (seg_scale), their lr_t written by adam_begin.
+    std::vector<float> lr_scale;
+    std::vector<std::pair<int64_t, int64_t>> span;
+    AdamSegs segs;
+    float seg_scale[ADAM_SEG_MAX] = {};
+    ctxi::Prune prune;
     // tf.nn.dropout (CTX_VARIANT_REAL with keep_prob < 1): on only while a TRAINING step (forward + backward) is being enqueued
     bool drop_on = false;
     uint64_t drop_seed = 0;
@@ -308,6 +329,9 @@ void adam_end(ctx_handle* h);
 inline bool guard_on(const ctx_handle* h) { return h->guard_clip > 0.f || h->guard_skip; }
 int guard_alloc(ctx_handle* h);
 void guard_enqueue(ctx_handle* h, int which, float clip, bool skip, bool count);   // norm of the gradient arena -> guard_ctl[which]
+inline bool masked(const ctx_handle* h) { return !h->lr_scale.empty(); }
+int tensor_spans(ctx_handle* h);   // fill h->span at create; CTX_E_INVALID if a tensor does not start on a 16-byte group
+void plan_mask(ctx_handle* h);     // h->lr_scale -> h->segs / seg_scale / prune
 bool d_h4_direct(const ctx_handle* h, int c1, int c2, int hs, int ws, int stride);
 void join(ctx_handle* h, int lane);
 void fork(ctx_handle* h, int lane);

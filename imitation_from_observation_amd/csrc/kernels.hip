@@ -1537,4 +1537,122 @@ void adam_guarded(hipStream_t s, float* p, const float* g, float* m, float* v, i
     hipLaunchKernelGGL(adam_guarded_kernel, dim3(ew_blocks(n / 4)), dim3(NTHREADS), 0, s, p, g, m, v, n, lr_t, b1, b2, eps, ctl);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Adam and the guard's sum over the trainable runs of the arena (ctx_set_param_lr_scale; launch.h: AdamSegs).  Both kernels walk the
+// TRAINABLE 16-byte groups c = 0 .. pre[n) grid-strided, so a frozen tensor costs neither traffic nor iterations; a thread's c only
+// grows, so it finds the run of c by stepping `run` forward from where its last group was (at most n steps per thread in all).  The
+// table comes in as a kernel argument and is copied to LDS once per block: lanes of a wave that straddles two runs index it apart.
+// ------------------------------------------------------------------------------------------------
+struct SegTable {
+    uint32_t pre[ADAM_SEG_MAX + 1], first[ADAM_SEG_MAX];
+    float lr_t[ADAM_SEG_MAX];
+};
+__device__ inline void seg_table_load(SegTable& L, const AdamSegs& T) {
+    for (int i = threadIdx.x; i < ADAM_SEG_MAX; i += NTHREADS) {
+        // (past the runs in use: pre = the total, so no search ever steps beyond run n - 1)
+        L.pre[i] = i <= T.n ? T.pre[i] : T.pre[T.n];
+        L.first[i] = T.first[i];
+        L.lr_t[i] = T.lr_t[i];
+    }
+    if (threadIdx.x == 0) L.pre[ADAM_SEG_MAX] = T.pre[T.n];
+    __syncthreads();
+}
+
+// Per element adam_guarded_kernel's arithmetic (GUARD) or adam_kernel's (no factor: the same two contractions spelled out, see the
+// remark in adam_guarded_kernel), with the run's lr_t in place of the launch's: a tensor at scale s is updated exactly as the
+// unmasked kernels update it at the learning rate lr * s.
+template <bool GUARD>
+__global__ __launch_bounds__(NTHREADS) void adam_seg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                            float* __restrict__ v, const AdamSegs T, float b1, float b2, float eps,
+                                                            const GuardCtl* __restrict__ ctl) {
+    if (GUARD && ctl->apply == 0) return;      // (uniform) a skipped step reads and writes nothing
+    __shared__ SegTable L;
+    seg_table_load(L, T);
+    float factor = 1.f;
+    if (GUARD) factor = ctl->factor;
+    const float c1 = 1.f - b1, c2 = 1.f - b2;
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const uint32_t total = L.pre[ADAM_SEG_MAX];
+    int run = 0;
+    for (uint32_t c = blockIdx.x * NTHREADS + threadIdx.x; c < total; c += gridDim.x * NTHREADS) {
+        while (c >= L.pre[run + 1]) ++run;
+        const int64_t i = ((int64_t)L.first[run] + (c - L.pre[run])) * 4;
+        const float lr_t = L.lr_t[run];
+        f4 gg = __builtin_nontemporal_load(reinterpret_cast<const f4*>(g + i));
+        if (GUARD) gg = gg * factor;
+        f4 mm = __builtin_nontemporal_load(reinterpret_cast<const f4*>(m + i));
+        f4 vv = __builtin_nontemporal_load(reinterpret_cast<const f4*>(v + i));
+        f4 pp = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p + i));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            mm[k] = __builtin_fmaf(b1, mm[k], c1 * gg[k]);
+            vv[k] = __builtin_fmaf(b2, vv[k], c2 * (gg[k] * gg[k]));
+            pp[k] = pp[k] - lr_t * mm[k] / (sqrtf(vv[k]) + eps);
+        }
+        __builtin_nontemporal_store(mm, reinterpret_cast<f4*>(m + i));
+        __builtin_nontemporal_store(vv, reinterpret_cast<f4*>(v + i));
+        __builtin_nontemporal_store(pp, reinterpret_cast<f4*>(p + i));
+    }
+}
+
+// grad_sumsq_kernel's contract on the trainable groups: f64 squares and sums, the constant GUARD_BLOCKS grid, a thread adds its
+// grid-strided groups in index order (four loads in flight), the same wave tree and block partial -- the bits of the norm depend on the
+// mask and the gradient, not on the device.  No atomics.
+template <bool NT>
+__global__ __launch_bounds__(NTHREADS) void grad_sumsq_seg_kernel(const float* __restrict__ g, const AdamSegs T, int64_t n_end,
+                                                                  double* __restrict__ part) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    __shared__ SegTable L;
+    seg_table_load(L, T);
+    const uint32_t total = L.pre[ADAM_SEG_MAX], stride = GUARD_BLOCKS * NTHREADS;
+    int run = 0;
+    auto at = [&](uint32_t c) {                          // arena float index of trainable group c (calls with growing c)
+        while (c >= L.pre[run + 1]) ++run;
+        return ((int64_t)L.first[run] + (c - L.pre[run])) * 4;
+    };
+    auto ld = [&](int64_t i) {                           // floats at and past n_end belong to no tensor: read as 0
+        if (i + 4 <= n_end) return NT ? __builtin_nontemporal_load(reinterpret_cast<const f4*>(g + i)) : *reinterpret_cast<const f4*>(g + i);
+        f4 a;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a[j] = i + j < n_end ? g[i + j] : 0.f;
+        return a;
+    };
+    double acc = 0.0;
+    uint32_t c = blockIdx.x * NTHREADS + threadIdx.x;
+    for (; (uint64_t)c + 3ull * stride < total; c += 4 * stride) {
+        f4 a[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a[k] = ld(at(c + k * stride));
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { const double x = (double)a[k][j]; acc = fma(x, x, acc); }
+    }
+    for (; c < total; c += stride) {
+        const f4 a = ld(at(c));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const double x = (double)a[j]; acc = fma(x, x, acc); }
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    __shared__ double ws[NTHREADS / 64];
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+}
+
+void adam_segmented(hipStream_t s, float* p, const float* g, float* m, float* v, const AdamSegs& T, float b1, float b2, float eps,
+                    const GuardCtl* ctl) {
+    const uint32_t total = T.pre[T.n];
+    if (!total) return;
+    if (ctl) hipLaunchKernelGGL((adam_seg_kernel<true>), dim3(ew_blocks(total)), dim3(NTHREADS), 0, s, p, g, m, v, T, b1, b2, eps, ctl);
+    else hipLaunchKernelGGL((adam_seg_kernel<false>), dim3(ew_blocks(total)), dim3(NTHREADS), 0, s, p, g, m, v, T, b1, b2, eps, ctl);
+}
+
+void grad_guard_segmented(hipStream_t s, const float* g, const AdamSegs& T, int64_t n_end, double* part, GuardCtl* ctl, float clip,
+                          int skip_nonfinite, int count, bool nontemporal) {
+    if (nontemporal) hipLaunchKernelGGL((grad_sumsq_seg_kernel<true>), dim3(GUARD_BLOCKS), dim3(NTHREADS), 0, s, g, T, n_end, part);
+    else hipLaunchKernelGGL((grad_sumsq_seg_kernel<false>), dim3(GUARD_BLOCKS), dim3(NTHREADS), 0, s, g, T, n_end, part);
+    hipLaunchKernelGGL(grad_guard_final_kernel, dim3(1), dim3(NTHREADS), 0, s, part, ctl, clip, skip_nonfinite, count);
+}
+
 }  // namespace ctx

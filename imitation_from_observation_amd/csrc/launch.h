@@ -276,4 +276,22 @@ void grad_guard(hipStream_t s, const float* g, int64_t n, double* part, GuardCtl
 void adam_guarded(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float b1, float b2, float eps,
                   const GuardCtl* ctl);
 
+// Adam and the guard's sum on a SUBSET of the arena (ctx_set_param_lr_scale): the trainable tensors as runs of 16-byte groups in arena
+// order, each with its own lr_t.  The table is a kernel argument (488 B), so a step's values reach the device with the launch itself.
+// A kernel numbers the trainable groups 0 .. pre[n) and finds group c in run s with pre[s] <= c < pre[s + 1] at arena group
+// first[s] + c - pre[s]: what lies between the runs (frozen tensors) is neither read nor written.
+constexpr int ADAM_SEG_MAX = 40;     // >= the tensors of any model (38)
+struct AdamSegs {
+    int32_t n = 0;                       // runs in use
+    uint32_t pre[ADAM_SEG_MAX + 1] = {}; // trainable groups in front of run s; pre[n] = all of them
+    uint32_t first[ADAM_SEG_MAX] = {};   // first arena group of run s
+    float lr_t[ADAM_SEG_MAX] = {};
+};
+// adam() / adam_guarded() (ctl != nullptr) on the runs of T: one launch whatever the mask; nothing is launched for an empty table
+void adam_segmented(hipStream_t s, float* p, const float* g, float* m, float* v, const AdamSegs& T, float b1, float b2, float eps,
+                    const GuardCtl* ctl);
+// grad_guard() over the runs of T; of a group that reaches past float n_end (the end of the last tensor) only the floats in front of it
+void grad_guard_segmented(hipStream_t s, const float* g, const AdamSegs& T, int64_t n_end, double* part, GuardCtl* ctl, float clip,
+                          int skip_nonfinite, int count, bool nontemporal);
+
 }  // namespace ctx

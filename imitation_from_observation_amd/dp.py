@@ -159,10 +159,14 @@ class RcclTrainer:
     torch.distributed group is initialised it is broadcast through that group (any backend)."""
 
     def __init__(self, H=64, W=64, df_dim=64, featsize=1024, max_batch=256, device=0, seed=1234, rank=None, world=None,
-                 unique_id=None, precision=None, grad_clip=None, skip_nonfinite=False):
+                 unique_id=None, precision=None, grad_clip=None, skip_nonfinite=False, var_list=None, lr_scales=None):
         """precision: "f32" | "bf16x3" | "fp16x3" | "fp16x3d" (Translator.__init__); None = the translator's default.
         grad_clip / skip_nonfinite: Translator.set_grad_guard -- clip by the global norm of the REDUCED gradient, skip a step whose
-        reduced gradient is non-finite; every rank takes the same decision on the device.  Defaults: no guard."""
+        reduced gradient is non-finite; every rank takes the same decision on the device.  Defaults: no guard.
+        var_list / lr_scales: Translator.set_trainable / set_lr_scales (one of the two) -- Adam and the guard's norm of the reduced
+        gradient cover the trainable tensors only; the backward and the all-reduce stay whole.  Defaults: every variable."""
+        if var_list is not None and lr_scales is not None:
+            raise ValueError("var_list and lr_scales are two spellings of one mask: give one")
         if rank is None:
             rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
         if world is None:
@@ -180,6 +184,10 @@ class RcclTrainer:
         self.translator.dp_init(unique_id, rank, world)
         if grad_clip is not None or skip_nonfinite:
             self.translator.set_grad_guard(grad_clip, skip_nonfinite)
+        if var_list is not None:
+            self.translator.set_trainable(var_list)
+        elif lr_scales is not None:
+            self.translator.set_lr_scales(lr_scales)
 
     def step(self, src, ctx, tgt, lr=1e-4, scalars=False):
         """src / ctx / tgt: contiguous float32 cuda tensors [B,H,W,3] of this rank's shard (ready on the device: the library's

@@ -102,7 +102,7 @@ class ModelTrainer:
     def __init__(self, idims, nvideos, ntrain, batch_size, model, nitr, save_every, nlen, nskip, rescale=True, inception=False,
                  strides=None, kernels=None, filters=None, *, vdata=None, basedir="model/", device=0, seed=0, translator=None,
                  precision=None, log=print, rank=0, world=1, dp_unique_id=None, videos=None, device_resize=False,
-                 grad_clip=None, skip_nonfinite=False):
+                 grad_clip=None, skip_nonfinite=False, var_list=None, lr_scales=None):
         """The reference's 14 positional arguments (train_script.py:29-30; the launchers omit the last five, SURVEY.md 3.4-b,
         hence the defaults), then: vdata (array or .npy path of the demo tensor), basedir (logger._snapshot_dir), device,
         seed of the parameter initialiser, an optional ready-made translator (tests), the arithmetic (precision: "f32" | "bf16x3" | "fp16x3" | "fp16x3d",
@@ -114,7 +114,10 @@ class ModelTrainer:
         host resize, one call per video) instead of on the host.
         grad_clip / skip_nonfinite: Translator.set_grad_guard -- clip every step's gradient by its global norm (data parallel: of the
         reduced gradient), leave parameters and Adam moments untouched on a step whose gradient is non-finite (one extra log line
-        then).  Defaults: no guard, logs and checkpoints as without these keywords."""
+        then).  Defaults: no guard, logs and checkpoints as without these keywords.
+        var_list / lr_scales: which variables Adam trains (`minimize(loss, var_list=...)`, train_script.py:126-128).  var_list: fnmatch
+        patterns on the TF variable names ("deconv/*") -- Translator.set_trainable, everything else is frozen; lr_scales: {pattern:
+        scale} -- Translator.set_lr_scales.  One of the two; set once before the first step.  Defaults: every variable, as before."""
         if model not in self.MODELS:
             raise ValueError(f"model must be one of {sorted(self.MODELS)}")
         self.idims, self.nvideos, self.ntrain, self.batch_size = tuple(idims), nvideos, ntrain, batch_size
@@ -124,6 +127,9 @@ class ModelTrainer:
         self.vdata, self.basedir, self.device, self.seed = vdata, basedir, device, seed
         self.device_resize = bool(device_resize)
         self.grad_clip, self.skip_nonfinite = grad_clip, bool(skip_nonfinite)
+        if var_list is not None and lr_scales is not None:
+            raise ValueError("var_list and lr_scales are two spellings of one mask: give one")
+        self.var_list, self.lr_scales = var_list, lr_scales
         self.videos = videos       # decoded demo videos (arrays [51, H, W, 3] uint8 or callables returning them): train_script.py:59-96
         self.translator, self.precision, self.log = translator, precision, log
         self.rank, self.world, self.dp_unique_id = int(rank), int(world), dp_unique_id
@@ -274,6 +280,10 @@ class ModelTrainer:
         guarded = self.grad_clip is not None or self.skip_nonfinite
         if guarded:
             core.set_grad_guard(self.grad_clip, self.skip_nonfinite)
+        if self.var_list is not None:
+            core.set_trainable(self.var_list)
+        elif self.lr_scales is not None:
+            core.set_lr_scales(self.lr_scales)
         skipped = 0
         rows = []
         for itr in range(1, self.nitr):

@@ -80,6 +80,25 @@ def _up(a):
     return a.ctypes.data_as(_UP)
 
 
+def resolve_lr_scales(names, spec):
+    """One learning-rate scale per TF variable name, in the order of `names`: `spec` maps fnmatch patterns ("deconv/*", "*/biases",
+    "conv/h0_conv/w") to scales and is applied IN ORDER -- a later pattern overrides an earlier one on the tensors both match;
+    tensors no pattern matches are 1.  0 freezes a tensor.  ValueError: a pattern that matches no name (a typo would silently train
+    everything), a negative or non-finite scale."""
+    import fnmatch
+    names = list(names)
+    out = np.ones(len(names), np.float32)
+    for pat, sc in dict(spec).items():
+        sc = float(sc)
+        if not (np.isfinite(sc) and sc >= 0.0):
+            raise ValueError(f"lr scale of {pat!r} must be finite and >= 0, got {sc}")
+        hit = [i for i, n in enumerate(names) if fnmatch.fnmatchcase(n, pat)]
+        if not hit:
+            raise ValueError(f"pattern {pat!r} matches none of the {len(names)} variables")
+        out[hit] = sc
+    return out
+
+
 class Translator:
     """One ContextSkipNew model (gym/envs/mujoco/arm_shaping.py:1260-1354) resident on one MI355X.
 
@@ -665,6 +684,35 @@ class Translator:
         n, f, sk, cl = ctypes.c_double(), ctypes.c_float(), ctypes.c_int64(), ctypes.c_int64()
         self._ck(self._lib.ctx_grad_guard_stats(self._h, ctypes.byref(n), ctypes.byref(f), ctypes.byref(sk), ctypes.byref(cl)))
         return dict(last_norm=float(n.value), last_factor=float(f.value), steps_skipped=int(sk.value), steps_clipped=int(cl.value))
+
+    # ------------------------------------------------------------------ training a subset (include/ctxtrans.h: ctx_set_param_lr_scale)
+    def set_lr_scales(self, spec):
+        """Per-tensor learning-rate scales for every later Adam update of this handle: `spec` = {fnmatch pattern on the TF variable
+        name: scale}, applied in order, unmatched tensors 1 (resolve_lr_scales); 0 freezes a tensor -- parameter and both moments keep
+        every bit, and a plain backward leaves out the launches only frozen tensors need.  None (or every scale 1) = no mask, the
+        default.  A tensor unfrozen later continues from its stale moments (the step count is global).  Not saved in checkpoints."""
+        if spec is None:
+            self._ck(self._lib.ctx_set_param_lr_scale(self._h, None, 0))
+            return
+        sc = resolve_lr_scales([n for n, _, _ in self.param_info()], spec)
+        self._ck(self._lib.ctx_set_param_lr_scale(self._h, _fp(sc), sc.size))
+
+    def set_trainable(self, var_list):
+        """The trainer's `minimize(loss, var_list=...)` (train_script.py:126-128): the tensors matching one of the patterns of
+        `var_list` train at scale 1, every other tensor is frozen.  None = all of them."""
+        if var_list is None:
+            return self.set_lr_scales(None)
+        pats = [var_list] if isinstance(var_list, str) else list(var_list)
+        spec = OrderedDict([("*", 0.0)])
+        spec.update((p, 1.0) for p in pats)
+        self.set_lr_scales(spec)
+
+    def get_lr_scales(self):
+        """OrderedDict name -> scale (1.0 everywhere without a mask)."""
+        names = [n for n, _, _ in self.param_info()]
+        sc = np.empty(len(names), np.float32)
+        self._ck(self._lib.ctx_get_param_lr_scale(self._h, _fp(sc), sc.size))
+        return OrderedDict((n, float(s)) for n, s in zip(names, sc))
 
     def dev_scalars(self):
         sc = np.empty(4, np.float32)

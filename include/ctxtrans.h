@@ -435,6 +435,29 @@ int ctx_grad_norm(ctx_handle* h, double* norm);
 /* norm and factor of the last guarded step and the counts of skipped / clipped steps since ctx_set_grad_guard (zeros before the
  * first).  Synchronises the stream.  Any pointer may be NULL. */
 int ctx_grad_guard_stats(ctx_handle* h, double* last_norm, float* last_factor, int64_t* steps_skipped, int64_t* steps_clipped);
+/* ---- training a subset of the parameters: one learning-rate scale per tensor (the trainer's var_list, train_script.py:126-128) ----
+ * scale[i] multiplies lr for tensor i of ctx_param_info (n == ctx_param_count(h)); 0 = frozen.  scale == NULL (n ignored) or every
+ * scale 1 = no mask, the default: every launch is then the one of a handle that never called this.  CTX_E_INVALID: NULL handle, wrong
+ * n, a negative or non-finite scale.  The mask is handle state; checkpoints do not hold it.  It covers every Adam update of the handle
+ * (ctx_train_step*, ctx_dev_train_step, ctx_dev_adam, ctx_dp_train_step*), in ONE launch per step whatever the mask:
+ *   - scaled tensor: today's Adam at lr_i = lr * scale[i], the product taken in f32 and lr_t formed from lr_i as it is from lr --
+ *     bit for bit the update of an unmasked handle stepped at (float)(lr * scale[i]) from the same state and gradient.
+ *   - frozen tensor: parameter, m and v keep every bit; no kernel of the update touches their memory.  The step counter is global and
+ *     advances: a tensor unfrozen later continues from its stale moments with the current bias correction (a TensorFlow graph with a
+ *     fixed var_list cannot unfreeze at all).
+ *   - guard (ctx_set_grad_guard, ctx_grad_norm): the norm, and with it the clip factor and the skip decision, is taken over the
+ *     trainable tensors only -- a NaN in a gradient no trainable tensor uses does not skip the step.
+ *   - ctx_get_grads returns exact zeros for a frozen tensor.  What ctx_dev_grads points at inside a frozen tensor's range is
+ *     UNSPECIFIED: a plain backward (ctx_dev_forward_backward, the fused steps, ctx_profile_step) leaves out every launch whose
+ *     results reach no trainable tensor's gradient -- filter / bias gradients of frozen tensors, input-gradient chains that end in
+ *     frozen tensors only -- so that range may hold an older step's values.  The launches that do run are the unmasked step's and the
+ *     trainable gradients are bit-identical.
+ *   - under a mask the early Adam slices are not used, as under a guard.
+ *   - data parallel (ctx_dp_train_step*, a handle after ctx_dp_init) and under ctx_set_grad_bucket_callback the backward stays whole
+ *     and the buckets are unchanged; the mask applies to Adam and to the norm of the reduced gradient.
+ *   - ctx_dev_backward_vjp ignores the mask: frame and code gradients need the whole chain. */
+int ctx_set_param_lr_scale(ctx_handle* h, const float* scale, int n);
+int ctx_get_param_lr_scale(const ctx_handle* h, float* scale, int n);
 /* Synchronises and copies {loss, simloss, recon1, recon2} of the last forward. */
 int ctx_dev_scalars(ctx_handle* h, float scalars[4]);
 /* Device pointer to the parameters (flat, ctx_param_info order).  WRITABLE: a caller may update the weights through it (its own
@@ -442,7 +465,7 @@ int ctx_dev_scalars(ctx_handle* h, float scalars[4]);
  * on it stops trusting filters it packed earlier for the direct kernels (ContextAEReal / the front end): they are re-packed in front of
  * every launch, and inference graphs captured before the call are dropped.  Handles that never call it keep the packed-filter cache. */
 void* ctx_dev_params(ctx_handle* h);
-void* ctx_dev_grads(ctx_handle* h);
+void* ctx_dev_grads(ctx_handle* h);      /* (inside a frozen tensor's range the contents are unspecified: ctx_set_param_lr_scale) */
 void* ctx_dev_scalar_buf(ctx_handle* h); /* device f32[4] written by the last forward */
 void* ctx_stream(ctx_handle* h);         /* hipStream_t the kernels are enqueued on */
 int ctx_sync(ctx_handle* h);
