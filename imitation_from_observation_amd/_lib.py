@@ -159,6 +159,15 @@ SIGNATURES = {
     "ctx_dp_eval_sampled": (_c.c_int, [_P, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32), _c.c_int, _F, _F, _F]),
     "ctx_dp_allreduce_host_f64": (_c.c_int, [_P, _c.POINTER(_c.c_double), _c.c_size_t]),
     "ctx_dp_nn_err": (_c.c_int, [_P, _c.c_int, _c.POINTER(_c.c_int64)]),
+    "ctx_accum_begin": (_c.c_int, [_P, _c.c_int]),
+    "ctx_accum_dev_forward_backward": (_c.c_int, [_P, _P, _P, _P, _c.c_int]),
+    "ctx_accum_adam": (_c.c_int, [_P, _c.c_float, _F]),
+    "ctx_dp_accum_adam": (_c.c_int, [_P, _c.c_float, _F]),
+    "ctx_accum_state": (_c.c_int, [_P, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "ctx_accum_train_step_sampled": (_c.c_int, [_P, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32), _c.c_int, _c.c_int, _c.c_float, _F,
+                                                _c.c_int, _c.POINTER(_c.c_int64)]),
+    "ctx_dp_accum_train_step_sampled": (_c.c_int, [_P, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32), _c.c_int, _c.c_int, _c.c_float, _F,
+                                                   _c.c_int, _c.POINTER(_c.c_int64)]),
     "ctx_profile_step": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_float, _c.c_int, _c.POINTER(CtxProfEntry), _c.c_int,
                                     _c.POINTER(_c.c_int)]),
     "ctx_debug_read": (_c.c_int, [_P, _c.c_char_p, _F, _c.c_size_t]),

@@ -905,9 +905,105 @@ int ctx_set_grad_bucket_callback(ctx_handle* h, ctx_bucket_fn fn, void* user) {
 
 int ctx_dev_adam(ctx_handle* h, float lr) {
     if (!h) return CTX_E_INVALID;
+    if (accum_open(h)) return accum_refuse(h, "ctx_dev_adam");
     HIP_TRY(h, hipSetDevice(h->device));
     TRY(adam_step(h, lr));
     HIP_TRY(h, hipGetLastError());
+    return CTX_OK;
+}
+
+// ---- gradient accumulation (include/ctxtrans.h; the launches: ctx_engine.cpp accum_*) -----------------------------------------------
+int ctx_accum_begin(ctx_handle* h, int total_batch) {
+    if (!h) return CTX_E_INVALID;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return accum_begin(h, total_batch);
+}
+
+int ctx_accum_state(const ctx_handle* h, int* rows_seen, int* total_batch) {
+    if (!h) return CTX_E_INVALID;
+    if (rows_seen) *rows_seen = h->accum_rows;
+    if (total_batch) *total_batch = h->accum_total;
+    return CTX_OK;
+}
+
+int ctx_accum_dev_forward_backward(ctx_handle* h, const float* d_src, const float* d_ctx, const float* d_tgt, int B) {
+    TRY(check_B(h, B));
+    if (!d_src || !d_ctx || !d_tgt) return fail(h, CTX_E_INVALID, "NULL input");
+    if (!accum_open(h)) return fail(h, CTX_E_STATE, "ctx_accum_begin first");
+    if (h->accum_rows + B > h->accum_share)      // (before the frames are staged: a refused call leaves the handle as it was)
+        return fail(h, CTX_E_STATE, "micro-batch of %d rows after %d of %d: more rows than ctx_accum_begin announced", B, h->accum_rows, h->accum_share);
+    HIP_TRY(h, hipSetDevice(h->device));
+    TRY(stage_frames(h, d_src, d_ctx, d_tgt, B));
+    return accum_micro_on_img(h, B, 0, 0);
+}
+
+int ctx_accum_adam(ctx_handle* h, float lr, float scalars[4]) {
+    if (!h) return CTX_E_INVALID;
+    if (h->dp_comm) return fail(h, CTX_E_STATE, "a handle after ctx_dp_init closes its accumulation with ctx_dp_accum_adam");
+    HIP_TRY(h, hipSetDevice(h->device));
+    TRY(accum_fold(h));
+    accum_close(h);
+    TRY(adam_step(h, lr));
+    HIP_TRY(h, hipGetLastError());
+    if (!scalars) return CTX_OK;
+    HIP_TRY(h, hipMemcpyAsync(scalars, h->scalars, 4 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    return finish(h);
+}
+}  // extern "C"
+namespace ctxi {
+// tgt rows of the WHOLE batch -> h->nn_tgt [B_total, npi], in pieces of max_batch rows (h->choice holds that many indices): what every
+// micro-batch's nn_err share is taken against (ctx_dp_nn_err's gathered slots without the collective)
+int accum_gather_tgt(ctx_handle* h, const int32_t* choicetgt, int B_total) {
+    const size_t n = (size_t)B_total * h->npi;
+    if (n > h->nn_tgt_cap) {
+        if (h->nn_tgt) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->nn_tgt); h->nn_tgt = nullptr; h->nn_tgt_cap = 0; }
+        if (hipMalloc((void**)&h->nn_tgt, n * sizeof(float)) != hipSuccess) return fail(h, CTX_E_NOMEM, "hipMalloc(%zu bytes) for the batch's tgt rows", n * sizeof(float));
+        h->nn_tgt_cap = n;
+    }
+    for (int b0 = 0; b0 < B_total; b0 += h->Bm) {
+        const int B = std::min(h->Bm, B_total - b0);
+        HIP_TRY(h, hipMemcpyAsync(h->choice + h->Bm, choicetgt + b0, (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        gather_tgt(h->stream, h->vdata, h->vT, h->vN, h->npi, h->choice + h->Bm, B, b0, h->lut, h->nn_tgt + (size_t)b0 * h->npi);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return CTX_OK;
+}
+}  // namespace ctxi
+extern "C" {
+
+int ctx_accum_train_step_sampled(ctx_handle* h, const int32_t* choicesrc, const int32_t* choicetgt, int B_total, int micro_B, float lr,
+                                 float scalars[4], int nlen, int64_t* nn_err) {
+    TRY(check_B(h, micro_B));
+    if (h->dp_comm) return fail(h, CTX_E_STATE, "a handle after ctx_dp_init steps with ctx_dp_accum_train_step_sampled");
+    if (!h->vdata) return fail(h, CTX_E_STATE, "ctx_demos_upload first");
+    if (!choicesrc || !choicetgt) return fail(h, CTX_E_INVALID, "NULL index array");
+    if (B_total <= 0) return fail(h, CTX_E_INVALID, "B_total=%d", B_total);
+    if (nn_err && nlen <= 0) return fail(h, CTX_E_INVALID, "nn_err: need nlen > 0");
+    for (int b = 0; b < B_total; ++b)
+        if (choicesrc[b] < 0 || choicesrc[b] >= h->vN || choicetgt[b] < 0 || choicetgt[b] >= h->vN)
+            return fail(h, CTX_E_INVALID, "video index out of range [0,%d)", h->vN);
+    HIP_TRY(h, hipSetDevice(h->device));
+    TRY(accum_begin(h, B_total));
+    int rc = nn_err ? accum_gather_tgt(h, choicetgt, B_total) : CTX_OK;
+    for (int b0 = 0; rc == CTX_OK && b0 < B_total; b0 += micro_B) {
+        const int B = std::min(micro_B, B_total - b0);
+        if (hipMemcpyAsync(h->choice, choicesrc + b0, (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+            hipMemcpyAsync(h->choice + h->Bm, choicetgt + b0, (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+            rc = fail(h, CTX_E_DEVICE, "index upload failed");
+            break;
+        }
+        gather_triples(h->stream, h->vdata, h->vT, h->vN, h->npi, h->choice, h->choice + h->Bm, B, b0, h->lut, h->img);
+        rc = accum_micro_on_img(h, B, nn_err ? nlen : 0, b0);
+    }
+    if (rc == CTX_OK) rc = accum_fold(h);
+    accum_close(h);                   // (a failed step leaves no accumulation open)
+    TRY(rc);
+    TRY(adam_step(h, lr));
+    if (scalars) HIP_TRY(h, hipMemcpyAsync(scalars, h->scalars, 4 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    double e = 0.0;
+    if (nn_err) HIP_TRY(h, hipMemcpyAsync(&e, h->accum_slots + 4, sizeof e, hipMemcpyDeviceToHost, h->stream));
+    TRY(finish(h));
+    if (nn_err) *nn_err = (int64_t)e;
     return CTX_OK;
 }
 
@@ -1042,6 +1138,7 @@ int ctx_profile_step(ctx_handle* h, const float* d_src, const float* d_ctx, cons
                      ctx_prof_entry* entries, int max_entries, int* n_entries) {
     TRY(check_B(h, B));
     if (!d_src || !d_ctx || !d_tgt || iters <= 0 || !n_entries) return fail(h, CTX_E_INVALID, "bad argument");
+    if (accum_open(h)) return accum_refuse(h, "ctx_profile_step");
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t bytes = (size_t)B * h->npi * sizeof(float);
     for (auto& m : h->prof_ms) m = 0.0;

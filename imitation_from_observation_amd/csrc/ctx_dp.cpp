@@ -163,6 +163,7 @@ int ctx_dp_allreduce_grads(ctx_handle* h) {
 // the data-parallel step on the shard already in h->img = [tgt | src | ctx] (B triples): forward, backward with the simloss mean over the
 // GLOBAL batch, the gradient buckets sent from inside backward, the rest after it, Adam
 static int dp_step_on_img(ctx_handle* h, int B, float lr, float scalars[4]) {
+    if (accum_open(h)) return accum_refuse(h, "a data-parallel training step");
     h->drop_on = true;
     forward(h, B, MODE_TRAIN);
     // two buckets: [split, Ppad) = translate/* + deconv/* leaves from inside backward (fire_bucket) and travels while the
@@ -320,6 +321,78 @@ int ctx_dp_scalars(ctx_handle* h, float scalars[4]) {
                        (terms & CTX_LOSS_RECON2 ? (double)s[3] : 0.0));
     }
     memcpy(scalars, s, sizeof s);
+    return CTX_OK;
+}
+
+// ---- gradient accumulation under data parallelism: k local micro-batches, ONE all-reduce -------------------------------------------
+// the tail of an accumulated data-parallel step: fold, one SUM all-reduce of the whole gradient arena, Adam on the reduced sum; then
+// (scalars) the global scalars -- every rank's finished slots hold its recon sums and its simloss share weighted rows / GLOBAL total,
+// so their plain sum over the ranks is the global batch's, and `loss` is formed from it as in ctx_dp_scalars
+static int dp_accum_tail(ctx_handle* h, float lr, float scalars[4]) {
+    TRY(accum_fold(h));
+    accum_close(h);
+    TRY(dp_reduce_range(h, 0, h->Ppad));
+    TRY(dp_wait(h));
+    TRY(adam_step(h, lr));
+    { char msg[256]; if (take_launch_error(msg, sizeof msg)) return fail(h, CTX_E_DEVICE, "%s", msg); }
+    HIP_TRY(h, hipGetLastError());
+    if (!scalars) return CTX_OK;
+    HIP_TRY(h, hipEventRecord(h->dp_ev_ready, h->stream));
+    HIP_TRY(h, hipStreamWaitEvent(h->dp_stream, h->dp_ev_ready, 0));
+    RCCL_TRY(h, rccl().AllReduce(h->scalars, h->dp_scal, 4, ncclFloat, ncclSum, h->dp_comm, h->dp_stream));
+    float s[4];
+    HIP_TRY(h, hipMemcpyAsync(s, h->dp_scal, sizeof s, hipMemcpyDeviceToHost, h->dp_stream));
+    HIP_TRY(h, hipStreamSynchronize(h->dp_stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const int terms = loss_terms_of(h);
+    s[0] = (float)((terms & CTX_LOSS_SIM ? (double)s[1] : 0.0) + (terms & CTX_LOSS_RECON1 ? (double)s[2] : 0.0) +
+                   (terms & CTX_LOSS_RECON2 ? (double)s[3] : 0.0));
+    memcpy(scalars, s, sizeof s);
+    return CTX_OK;
+}
+
+int ctx_dp_accum_adam(ctx_handle* h, float lr, float scalars[4]) {
+    if (!h) return CTX_E_INVALID;
+    if (!h->dp_comm) return fail(h, CTX_E_STATE, "ctx_dp_init first");
+    HIP_TRY(h, hipSetDevice(h->device));
+    return dp_accum_tail(h, lr, scalars);
+}
+
+int ctx_dp_accum_train_step_sampled(ctx_handle* h, const int32_t* choicesrc, const int32_t* choicetgt, int B_total, int micro_B, float lr,
+                                    float scalars[4], int nlen, int64_t* nn_err) {
+    TRY(check_B(h, micro_B));
+    if (!h->dp_comm) return fail(h, CTX_E_STATE, "ctx_dp_init first");
+    if (!h->vdata) return fail(h, CTX_E_STATE, "ctx_demos_upload first");
+    if (!choicesrc || !choicetgt) return fail(h, CTX_E_INVALID, "NULL index array");
+    if (B_total <= 0 || B_total % h->dp_world) return fail(h, CTX_E_INVALID, "global batch %d is not a multiple of the %d ranks", B_total, h->dp_world);
+    if (nn_err && nlen <= 0) return fail(h, CTX_E_INVALID, "nn_err: need nlen > 0");
+    for (int b = 0; b < B_total; ++b)      // (the whole array: every rank refuses the same bad call, so no rank is left waiting in a collective)
+        if (choicesrc[b] < 0 || choicesrc[b] >= h->vN || choicetgt[b] < 0 || choicetgt[b] >= h->vN)
+            return fail(h, CTX_E_INVALID, "video index out of range [0,%d)", h->vN);
+    HIP_TRY(h, hipSetDevice(h->device));
+    TRY(accum_begin(h, B_total));
+    const int share = B_total / h->dp_world, r0 = h->dp_rank * share;
+    // nn_err: every rank holds the index arrays and the demo tensor, so it gathers ALL tgt rows itself (no all-gather)
+    int rc = nn_err ? accum_gather_tgt(h, choicetgt, B_total) : CTX_OK;
+    for (int o = 0; rc == CTX_OK && o < share; o += micro_B) {
+        const int B = std::min(micro_B, share - o), b0 = r0 + o;      // b0: the micro-batch's first row of the GLOBAL batch
+        if (hipMemcpyAsync(h->choice, choicesrc + b0, (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+            hipMemcpyAsync(h->choice + h->Bm, choicetgt + b0, (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+            rc = fail(h, CTX_E_DEVICE, "index upload failed");
+            break;
+        }
+        gather_triples(h->stream, h->vdata, h->vT, h->vN, h->npi, h->choice, h->choice + h->Bm, B, b0, h->lut, h->img);
+        rc = accum_micro_on_img(h, B, nn_err ? nlen : 0, b0);
+    }
+    if (rc != CTX_OK) { accum_close(h); return rc; }
+    TRY(dp_accum_tail(h, lr, scalars));
+    if (nn_err) {                      // the ranks' shares -> the global number, the same on every rank (f64: exact for counts below 2^53)
+        TRY(dp_allreduce_dev_f64(h, h->accum_slots + 4, 1));
+        double e = 0.0;
+        HIP_TRY(h, hipMemcpyAsync(&e, h->accum_slots + 4, sizeof e, hipMemcpyDeviceToHost, h->stream));
+        TRY(finish(h));
+        *nn_err = (int64_t)e;
+    }
     return CTX_OK;
 }
 }  // extern "C"

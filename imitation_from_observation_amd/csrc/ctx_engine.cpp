@@ -1236,12 +1236,97 @@ int adam_step(ctx_handle* h, float lr) {
 
 // forward + backward + Adam on the frames in h->img, Adam sliced beside the backward (adam_early)
 int fused_step(ctx_handle* h, int B, float lr) {
+    if (accum_open(h)) return accum_refuse(h, "a fused training step");
     h->drop_on = true;      // (dropout belongs to the training graph only)
     forward(h, B, MODE_TRAIN);
     adam_begin(h, lr);
     backward(h, B, B);
     h->drop_on = false;
     adam_end(h);
+    return CTX_OK;
+}
+
+// ---- gradient accumulation (ctx_accum_*): one Adam step from several micro-batches ------------------------------------------------
+// A data-parallel step is a SUM of shard gradients with the simloss mean over the global batch (ctx_dp.cpp: dp_step_on_img); the same
+// arithmetic in micro-batches on ONE handle: micro-batch j runs a plain backward(h, B_j, total) and its gradient is added into `accum`,
+// a Ppad-float buffer beside the arena -- SET for the first, ADD for the later ones, and the LAST is not added at all: accum_fold
+// writes  g = accum + g  into the gradient arena, which then holds ((g1 + g2) + ...) + gk, one f32 add per element and micro-batch, and
+// the EXISTING tail runs on it unchanged (guard_enqueue, adam_launch / adam_segmented, dp_reduce_range, ctx_get_grads, ctx_grad_norm).
+// The fold costs three arena passes per accumulated step (read accum, read g, write g: 0.57 GB for ContextSkipNew); an Adam reading two
+// gradient sources would save one and add a third instantiation of every Adam kernel.  An accumulation of ONE micro-batch launches
+// nothing beyond the plain forward_backward + adam: it is that step bit for bit.
+// Under an lr-scale mask every pass runs over the trainable runs only (the segmented kernels' table): frozen floats of the accumulator
+// and of the gradient arena are never read or written, so a pruned backward's stale ranges stay out of the sum.
+// Early Adam slices never run in a micro-batch (no adam_begin in front of its backward), and pack.version does not move between
+// micro-batches: packed filters are reused across them.
+// The loads of FOLD are PLAIN, as the guard's (above): its output is read next by the guard or by Adam.  MEASURED
+// (profiles/grad_accum.txt): at k = 4 the accumulated step's median is the same to 0.1 % with plain and with nontemporal loads, each
+// inside the other's interquartile range -- no reason to differ from the guard's form.  The other form is a build with
+// EXTRA=-DCTX_ACCUM_NT=1, which tools/bench_grad_accum.py --other-lib measures.
+#ifndef CTX_ACCUM_NT
+#define CTX_ACCUM_NT 0
+#endif
+constexpr bool ACCUM_NT = CTX_ACCUM_NT != 0;
+int accum_refuse(ctx_handle* h, const char* what) {
+    return fail(h, CTX_E_STATE, "%s while a gradient accumulation is open (%d of %d rows seen): ctx_accum_adam closes it, ctx_accum_begin(h, 0) cancels it",
+                what, h->accum_rows, h->accum_share);
+}
+void accum_close(ctx_handle* h) { h->accum_total = h->accum_share = h->accum_rows = h->accum_micro = 0; }
+int accum_begin(ctx_handle* h, int total_batch) {
+    if (total_batch < 0) return fail(h, CTX_E_INVALID, "total_batch < 0");
+    if (total_batch == 0) { accum_close(h); return CTX_OK; }
+    const int world = h->dp_comm ? h->dp_world : 1;
+    if (total_batch % world) return fail(h, CTX_E_INVALID, "total batch %d is not a multiple of the %d ranks", total_batch, world);
+    if (!h->accum) {
+        TRY(dev_alloc(h, &h->accum_slots, ACCUM_SLOTS));
+        TRY(dev_alloc(h, &h->accum, h->Ppad, false));
+    }
+    accum_close(h);
+    h->accum_total = total_batch;
+    h->accum_share = total_batch / world;
+    return CTX_OK;
+}
+static void accum_enqueue(ctx_handle* h, int mode) {
+    float* g = h->arena + h->Ppad;
+    if (masked(h)) grad_accum_segmented(h->stream, h->accum, g, h->segs, mode, ACCUM_NT);
+    else grad_accum(h->stream, h->accum, g, h->gen ? h->gen->pend : h->P, mode, ACCUM_NT);      // the range the guard's sum covers
+}
+int accum_micro_on_img(ctx_handle* h, int B, int nn_nlen, int nn_j0) {
+    if (!accum_open(h)) return fail(h, CTX_E_STATE, "ctx_accum_begin first");
+    if (h->accum_rows + B > h->accum_share)
+        return fail(h, CTX_E_STATE, "micro-batch of %d rows after %d of %d: more rows than ctx_accum_begin announced", B, h->accum_rows, h->accum_share);
+    const bool first = h->accum_micro == 0, last = h->accum_rows + B == h->accum_share;
+    // a plain backward: pruned where a mask allows it, and no bucket leaves from inside it (the sum is reduced once, at the end)
+    const ctx_bucket_fn fn = h->bucket_fn;
+    h->bucket_fn = nullptr;
+    h->drop_on = true;
+    h->accum_mix = (uint32_t)h->accum_micro;      // micro-batch j draws masks of its own; j = 0: the plain step's
+    forward(h, B, MODE_TRAIN);
+    h->last_B = B;
+    if (nn_nlen > 0) {
+        const int rc = nn_err_enqueue(h, h->nn_tgt, h->accum_total, nn_nlen, nn_j0);
+        if (rc != CTX_OK) { h->drop_on = false; h->accum_mix = 0; h->bucket_fn = fn; return rc; }
+    }
+    backward(h, B, h->accum_total);
+    h->drop_on = false;
+    h->accum_mix = 0;
+    h->bucket_fn = fn;
+    if (!last) accum_enqueue(h, first ? ACCUM_SET : ACCUM_ADD);
+    // (one micro-batch on one device: h->scalars already holds the step's scalars -- no launch at all)
+    const bool solo = first && last && !h->dp_comm;
+    if (!solo || nn_nlen > 0) scalars_accum(h->stream, h->scalars, h->accum_slots, B, h->accum_total, first, nn_nlen > 0 ? h->nn_res : nullptr);
+    h->accum_rows += B;
+    h->accum_micro += 1;
+    { char msg[256]; if (take_launch_error(msg, sizeof msg)) return fail(h, CTX_E_DEVICE, "%s", msg); }
+    HIP_TRY(h, hipGetLastError());
+    return CTX_OK;
+}
+int accum_fold(ctx_handle* h) {
+    if (!accum_open(h)) return fail(h, CTX_E_STATE, "ctx_accum_begin first");
+    if (h->accum_rows != h->accum_share)
+        return fail(h, CTX_E_STATE, "%d of %d rows seen: the accumulation is not complete", h->accum_rows, h->accum_share);
+    if (h->accum_micro > 1) accum_enqueue(h, ACCUM_FOLD);
+    if (h->accum_micro > 1 || h->dp_comm) scalars_finish(h->stream, h->accum_slots, h->scalars, loss_terms_of(h));
     return CTX_OK;
 }
 

@@ -263,6 +263,14 @@ struct ctx_handle {
     AdamSegs segs;
     float seg_scale[ADAM_SEG_MAX] = {};
     ctxi::Prune prune;
+    // gradient accumulation (ctx_accum_*): `accum` = the sum of the micro-batches' gradients so far, Ppad floats BESIDE the arena
+    // (allocated at the first ctx_accum_begin); accum_slots = ACCUM_SLOTS doubles, the scalars' sums and the nn_err sum.  Open while
+    // accum_total > 0: accum_share = the rows this handle adds (total / world under ctx_dp_init), accum_rows of them seen in
+    // accum_micro micro-batches.  The LAST micro-batch's gradient stays in the gradient arena and accum_fold adds the sum to it there.
+    float* accum = nullptr;
+    double* accum_slots = nullptr;
+    int accum_total = 0, accum_share = 0, accum_rows = 0, accum_micro = 0;
+    uint32_t accum_mix = 0;       // ordinal of the micro-batch whose forward is being enqueued: mixed into the dropout seed (0 = not at all)
     // tf.nn.dropout (CTX_VARIANT_REAL with keep_prob < 1): on only while a TRAINING step (forward + backward) is being enqueued
     bool drop_on = false;
     uint64_t drop_seed = 0;
@@ -339,6 +347,16 @@ void fire_bucket(ctx_handle* h, int64_t first);
 int dp_reduce_range(ctx_handle* h, int64_t first, int64_t count);    // ctx_dp.cpp
 void dp_teardown(ctx_handle* h);                                      // ctx_dp.cpp
 int dp_allreduce_dev_f64(ctx_handle* h, double* d, size_t n);         // ctx_dp.cpp: in place, ordered behind and in front of h->stream
+// gradient accumulation (ctx_engine.cpp): open / cancel | one micro-batch on the frames in h->img (nn_nlen > 0: its nn_err share against
+// h->nn_tgt [accum_total rows], outputs from global row nn_j0) | the fold into the gradient arena and the finished scalars | close
+inline bool accum_open(const ctx_handle* h) { return h->accum_total > 0; }
+int accum_refuse(ctx_handle* h, const char* what);                   // CTX_E_STATE for an Adam update while an accumulation is open
+int accum_begin(ctx_handle* h, int total_batch);
+int accum_micro_on_img(ctx_handle* h, int B, int nn_nlen, int nn_j0);
+int accum_fold(ctx_handle* h);
+void accum_close(ctx_handle* h);
+int accum_gather_tgt(ctx_handle* h, const int32_t* choicetgt, int B_total);      // ctx_abi.cpp: the whole batch's tgt rows -> h->nn_tgt
+int dp_wait(ctx_handle* h);                                           // ctx_dp.cpp
 int stage_frames(ctx_handle* h, const float* d_src, const float* d_ctx, const float* d_tgt, int B);   // ctx_abi.cpp
 int nn_err_enqueue(ctx_handle* h, const float* tgt, int Bt, int nlen, int j0);                       // ctx_abi.cpp: h->nn_res[0]
 

@@ -260,7 +260,10 @@ void gen_forward(ctx_handle* h, int B, Mode mode) {
         const float kp = h->cfg.keep_prob;
         // data parallel: every rank draws its OWN masks (rank mixed into the seed; rank 0 = the single-device stream), so the global
         // batch sees B * world distinct masks instead of the same B on every shard
-        const uint32_t seed = (uint32_t)h->drop_seed ^ (h->dp_comm ? 0x9E3779B9u * (uint32_t)h->dp_rank : 0u), step = (uint32_t)(h->drop_step >= 0 ? h->drop_step : h->adam_t);
+        // gradient accumulation: adam_t does not move between micro-batches, so micro-batch j mixes its ordinal in the same way (another
+        // odd constant: rank r's micro-batch j is no other rank's); j = 0 = the plain step's stream
+        const uint32_t seed = (uint32_t)h->drop_seed ^ (h->dp_comm ? 0x9E3779B9u * (uint32_t)h->dp_rank : 0u) ^ 0x85EBCA6Bu * h->accum_mix,
+                       step = (uint32_t)(h->drop_step >= 0 ? h->drop_step : h->adam_t);
         const int F = h->F, f3 = r.nf[3], c3 = r.cp[3], D0 = r.gh[3] * r.gw[3] * f3;
         drop_factors(h->stream, h->dM[1], 3 * B, D0p, c3, f3, D0, kp, seed, step, 1);
         drop_factors(h->stream, h->dM[2], 3 * B, Fp, Fp, F, F, kp, seed, step, 2);

@@ -1655,4 +1655,112 @@ void grad_guard_segmented(hipStream_t s, const float* g, const AdamSegs& T, int6
     hipLaunchKernelGGL(grad_guard_final_kernel, dim3(1), dim3(NTHREADS), 0, s, part, ctl, clip, skip_nonfinite, count);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Gradient accumulation (ctx_accum_*): the sum of several micro-batches' gradients beside the arena.  One elementwise pass over 16-byte
+// groups in three modes -- SET acc = g, ADD acc = acc + g, FOLD g = acc + g -- so an accumulation of k micro-batches leaves
+// ((g1 + g2) + ...) + gk in the gradient arena: one f32 add per element and micro-batch, nothing a compiler could contract, the same
+// bits on every device.  SEG: the trainable runs of an lr-scale mask only (adam_seg_kernel's walk); what lies between them is neither
+// read nor written, in the accumulator or in g.  NT: the loads of FOLD as nontemporal ones (its output is read next by the guard or
+// by Adam; which form is faster is measured, ctx_engine.cpp: ACCUM_NT).
+// ------------------------------------------------------------------------------------------------
+template <int MODE, bool NT>
+__device__ __forceinline__ void grad_accum_group(float* __restrict__ acc, float* __restrict__ g, int64_t i) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    f4* a4 = reinterpret_cast<f4*>(acc + i);
+    f4* g4 = reinterpret_cast<f4*>(g + i);
+    if (MODE == ACCUM_SET) { *a4 = *g4; return; }
+    const f4 a = NT ? __builtin_nontemporal_load(a4) : *a4;
+    const f4 x = NT ? __builtin_nontemporal_load(g4) : *g4;
+    const f4 sum = a + x;
+    if (MODE == ACCUM_ADD) *a4 = sum;
+    else *g4 = sum;
+}
+
+template <int MODE, bool NT>
+__global__ __launch_bounds__(NTHREADS) void grad_accum_kernel(float* __restrict__ acc, float* __restrict__ g, int64_t n4) {
+    for (int64_t c = (int64_t)blockIdx.x * NTHREADS + threadIdx.x; c < n4; c += (int64_t)gridDim.x * NTHREADS)
+        grad_accum_group<MODE, NT>(acc, g, c * 4);
+}
+
+template <int MODE, bool NT>
+__global__ __launch_bounds__(NTHREADS) void grad_accum_seg_kernel(float* __restrict__ acc, float* __restrict__ g, const AdamSegs T) {
+    __shared__ SegTable L;
+    seg_table_load(L, T);
+    const uint32_t total = L.pre[ADAM_SEG_MAX];
+    int run = 0;
+    for (uint32_t c = blockIdx.x * NTHREADS + threadIdx.x; c < total; c += gridDim.x * NTHREADS) {
+        while (c >= L.pre[run + 1]) ++run;
+        grad_accum_group<MODE, NT>(acc, g, ((int64_t)L.first[run] + (c - L.pre[run])) * 4);
+    }
+}
+
+void grad_accum(hipStream_t s, float* acc, float* g, int64_t n, int mode, bool nontemporal) {
+    const int64_t n4 = (n + 3) / 4;      // whole 16-byte groups: the caller's buffers reach the next multiple of 4 (the arena's slots are padded to 64)
+    if (n4 <= 0) return;
+    const dim3 grid(ew_blocks(n4)), block(NTHREADS);
+    if (mode == ACCUM_SET) hipLaunchKernelGGL((grad_accum_kernel<ACCUM_SET, false>), grid, block, 0, s, acc, g, n4);
+    else if (mode == ACCUM_ADD) hipLaunchKernelGGL((grad_accum_kernel<ACCUM_ADD, false>), grid, block, 0, s, acc, g, n4);
+    else if (nontemporal) hipLaunchKernelGGL((grad_accum_kernel<ACCUM_FOLD, true>), grid, block, 0, s, acc, g, n4);
+    else hipLaunchKernelGGL((grad_accum_kernel<ACCUM_FOLD, false>), grid, block, 0, s, acc, g, n4);
+}
+
+void grad_accum_segmented(hipStream_t s, float* acc, float* g, const AdamSegs& T, int mode, bool nontemporal) {
+    const uint32_t total = T.pre[T.n];
+    if (!total) return;
+    const dim3 grid(ew_blocks(total)), block(NTHREADS);
+    if (mode == ACCUM_SET) hipLaunchKernelGGL((grad_accum_seg_kernel<ACCUM_SET, false>), grid, block, 0, s, acc, g, T);
+    else if (mode == ACCUM_ADD) hipLaunchKernelGGL((grad_accum_seg_kernel<ACCUM_ADD, false>), grid, block, 0, s, acc, g, T);
+    else if (nontemporal) hipLaunchKernelGGL((grad_accum_seg_kernel<ACCUM_FOLD, true>), grid, block, 0, s, acc, g, T);
+    else hipLaunchKernelGGL((grad_accum_seg_kernel<ACCUM_FOLD, false>), grid, block, 0, s, acc, g, T);
+}
+
+// {loss, simloss, recon1, recon2} of a micro-batch into the accumulation's f64 slots: the recon sums add, simloss -- a mean over the
+// micro-batch's rows -- enters with the weight rows / total; slot 0 stays unused (`loss` is formed from the other three at the end).
+// nn (nullable): a micro-batch's nn_err share, added into slot 4.  One thread; the host never waits for it.
+__global__ void scalars_accum_kernel(const float* __restrict__ scalars, double* __restrict__ slots, double w, int first,
+                                     const double* __restrict__ nn) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const double sim = w * (double)scalars[1], r1 = (double)scalars[2], r2 = (double)scalars[3], e = nn ? nn[0] : 0.0;
+    slots[0] = 0.0;
+    slots[1] = first ? sim : slots[1] + sim;
+    slots[2] = first ? r1 : slots[2] + r1;
+    slots[3] = first ? r2 : slots[3] + r2;
+    slots[4] = first ? e : slots[4] + e;
+}
+// ... and the accumulated step's f32 scalars from them, `loss` from the terms the handle keeps (loss_final_kernel's masking)
+__global__ void scalars_finish_kernel(const double* __restrict__ slots, float* __restrict__ scalars, int terms) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const double sim = slots[1], r1 = slots[2], r2 = slots[3];
+    scalars[0] = (float)((terms & 1 ? r1 : 0.0) + (terms & 2 ? r2 : 0.0) + (terms & 4 ? sim : 0.0));
+    scalars[1] = (float)sim;
+    scalars[2] = (float)r1;
+    scalars[3] = (float)r2;
+}
+void scalars_accum(hipStream_t s, const float* scalars, double* slots, int rows, int total, bool first, const double* nn) {
+    hipLaunchKernelGGL(scalars_accum_kernel, dim3(1), dim3(64), 0, s, scalars, slots, (double)rows / (double)total, first ? 1 : 0, nn);
+}
+void scalars_finish(hipStream_t s, const double* slots, float* scalars, int terms) {
+    hipLaunchKernelGGL(scalars_finish_kernel, dim3(1), dim3(64), 0, s, slots, scalars, terms);
+}
+
+// tgt[b] = vdata[(b0 + b) % T][ctgt[b]] for b < B, scaled through the table: gather_triples' tgt slot alone, written to rows [0, B) of `out`
+__global__ __launch_bounds__(NTHREADS) void gather_tgt_kernel(const uint8_t* __restrict__ vdata, int T, int N, int64_t npi,
+                                                              const int* __restrict__ ctgt, int B, int b0, const float* __restrict__ lut,
+                                                              float* __restrict__ out) {
+    __shared__ float sl[256];
+    sl[threadIdx.x] = lut[threadIdx.x];
+    __syncthreads();
+    const int64_t per = npi / 4, total = (int64_t)B * per;
+    for (int64_t idx = (int64_t)blockIdx.x * NTHREADS + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * NTHREADS) {
+        const int64_t e4 = idx % per;
+        const int b = (int)(idx / per);
+        const int t = (b0 + b) % T;
+        const uchar4 u = *reinterpret_cast<const uchar4*>(vdata + ((int64_t)t * N + ctgt[b]) * npi + e4 * 4);
+        *reinterpret_cast<float4*>(out + (int64_t)b * npi + e4 * 4) = make_float4(sl[u.x], sl[u.y], sl[u.z], sl[u.w]);
+    }
+}
+void gather_tgt(hipStream_t s, const uint8_t* vdata, int T, int N, int64_t npi, const int* ctgt, int B, int b0, const float* lut, float* out) {
+    hipLaunchKernelGGL(gather_tgt_kernel, dim3(ew_blocks((int64_t)B * npi / 4)), dim3(NTHREADS), 0, s, vdata, T, N, npi, ctgt, B, b0, lut, out);
+}
+
 }  // namespace ctx

@@ -294,4 +294,18 @@ void adam_segmented(hipStream_t s, float* p, const float* g, float* m, float* v,
 void grad_guard_segmented(hipStream_t s, const float* g, const AdamSegs& T, int64_t n_end, double* part, GuardCtl* ctl, float clip,
                           int skip_nonfinite, int count, bool nontemporal);
 
+// Gradient accumulation (ctx_accum_*).  grad_accum: one elementwise pass over the 16-byte groups of acc / g [0, n) (n rounded up to 4:
+// both buffers reach that far) -- SET acc = g, ADD acc = acc + g, FOLD g = acc + g, plain f32 adds; _segmented: over the runs of T
+// only, nothing between them read or written.  nontemporal: the load form of FOLD.
+// scalars_accum: a micro-batch's f32 {loss, simloss, recon1, recon2} into slots[5] (f64: [1] += simloss * rows / total, [2], [3] +=
+// the recon sums, [4] += *nn when given; first: = in place of +=); scalars_finish: the f32 scalars of the sum, `loss` from `terms`.
+enum { ACCUM_SET = 0, ACCUM_ADD = 1, ACCUM_FOLD = 2 };
+constexpr int ACCUM_SLOTS = 5;
+void grad_accum(hipStream_t s, float* acc, float* g, int64_t n, int mode, bool nontemporal);
+void grad_accum_segmented(hipStream_t s, float* acc, float* g, const AdamSegs& T, int mode, bool nontemporal);
+void scalars_accum(hipStream_t s, const float* scalars, double* slots, int rows, int total, bool first, const double* nn);
+void scalars_finish(hipStream_t s, const double* slots, float* scalars, int terms);
+// the tgt slot of gather_triples alone: out[b] = vdata[(b0 + b) % T][ctgt[b]], b < B (the whole batch's tgt rows for nn_err)
+void gather_tgt(hipStream_t s, const uint8_t* vdata, int T, int N, int64_t npi, const int* ctgt, int B, int b0, const float* lut, float* out);
+
 }  // namespace ctx

@@ -159,8 +159,11 @@ class RcclTrainer:
     torch.distributed group is initialised it is broadcast through that group (any backend)."""
 
     def __init__(self, H=64, W=64, df_dim=64, featsize=1024, max_batch=256, device=0, seed=1234, rank=None, world=None,
-                 unique_id=None, precision=None, grad_clip=None, skip_nonfinite=False, var_list=None, lr_scales=None):
+                 unique_id=None, precision=None, grad_clip=None, skip_nonfinite=False, var_list=None, lr_scales=None, accum_steps=1):
         """precision: "f32" | "bf16x3" | "fp16x3" | "fp16x3d" (Translator.__init__); None = the translator's default.
+        accum_steps: k > 1 -- step() takes a shard of up to `max_batch` rows and runs it in k micro-batches (trainer.micro_slices) with
+        ONE all-reduce and one Adam update on the summed gradient (Translator.accum_begin .. dp_accum_adam); the handle is created
+        with max_batch = ceil(max_batch / k).  Default 1: the code path as before.
         grad_clip / skip_nonfinite: Translator.set_grad_guard -- clip by the global norm of the REDUCED gradient, skip a step whose
         reduced gradient is non-finite; every rank takes the same decision on the device.  Defaults: no guard.
         var_list / lr_scales: Translator.set_trainable / set_lr_scales (one of the two) -- Adam and the guard's norm of the reduced
@@ -172,7 +175,10 @@ class RcclTrainer:
         if world is None:
             world = _world()
         self.rank, self.world = rank, world
-        self.translator = Translator(H, W, df_dim, featsize, max_batch, device=device, precision=precision)
+        self.accum_steps = int(accum_steps)
+        if self.accum_steps < 1:
+            raise ValueError(f"accum_steps = {accum_steps}")
+        self.translator = Translator(H, W, df_dim, featsize, -(-max_batch // self.accum_steps), device=device, precision=precision)
         self.translator.init_params(seed)
         self.n_params = self.translator.n_params
         if unique_id is None:
@@ -191,7 +197,14 @@ class RcclTrainer:
 
     def step(self, src, ctx, tgt, lr=1e-4, scalars=False):
         """src / ctx / tgt: contiguous float32 cuda tensors [B,H,W,3] of this rank's shard (ready on the device: the library's
-        stream does not wait for torch's)."""
+        stream does not wait for torch's).  accum_steps > 1: the shard runs in micro-batches, one all-reduce and one Adam update."""
+        if self.accum_steps > 1:
+            from .trainer import micro_slices
+            t, B = self.translator, src.shape[0]
+            t.accum_begin(B * self.world)
+            for a, b in micro_slices(B, self.accum_steps):
+                t.accum_dev_forward_backward(HipEngine._ptr(src[a:b]), HipEngine._ptr(ctx[a:b]), HipEngine._ptr(tgt[a:b]), b - a)
+            return t.dp_accum_adam(lr, scalars)
         return self.translator.dp_train_step(HipEngine._ptr(src), HipEngine._ptr(ctx), HipEngine._ptr(tgt), src.shape[0], lr, scalars)
 
     def scalars(self):

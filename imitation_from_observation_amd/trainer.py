@@ -44,6 +44,12 @@ The Inception variant (`inception=True`) does the same with its uint8 frames res
 into the front end on the device (ctx_cnn_forward_sampled_dev), runs Inception on them per step as the reference graph does, and
 trains the translator with ctx_dp_train_step on the maps; `nn_err` is ctx_dp_nn_err (the tgt maps are all-gathered on the devices,
 never brought to the host).  On one GPU it keeps the host gather (train_step_u8 / evaluate_u8).
+
+Gradient accumulation (`accum_steps=k`; new): the batch of every step is run in k micro-batches with ONE Adam update on the summed
+gradient (`ctx_accum_train_step_sampled`, data parallel `ctx_dp_accum_train_step_sampled`: one all-reduce per step), so `batch_size`
+may exceed what one launch sequence carries -- the model is created with max_batch = ceil(batch_size / world / k).  The draws, the
+log, the CSV, checkpoints and clips are those of the same `batch_size` without accumulation, up to f32 summation order; `nn_err` of a
+training batch is summed on the device.  Not for `inception=True`.
 """
 from __future__ import annotations
 
@@ -81,6 +87,17 @@ def nn_err(tgt, out, nlen, j0=0):
     return int(np.abs(np.argmin(d, axis=0) - (j0 + np.arange(len(out))) % nlen).sum())
 
 
+def micro_slices(rows, accum_steps, first=0):
+    """The micro-batches of an accumulated step: `rows` consecutive rows from `first` on in at most `accum_steps` slices [a, b) of
+    ceil(rows / accum_steps) rows each -- the last may be short, and fewer slices come out when they cover the rows already.  Every
+    row lies in exactly one slice."""
+    if rows < 0 or accum_steps < 1:
+        raise ValueError(f"rows = {rows}, accum_steps = {accum_steps}")
+    micro = -(-rows // accum_steps)
+    for a in range(0, rows, micro or 1):
+        yield first + a, first + min(a + micro, rows)
+
+
 def on_u8_lattice(vdata):
     """(uint8 tensor, True) when the float demo tensor is exactly what transform() makes of uint8 frames
     (k / 127.5 - 1, train_script.py:16-19), else (None, False)."""
@@ -102,7 +119,7 @@ class ModelTrainer:
     def __init__(self, idims, nvideos, ntrain, batch_size, model, nitr, save_every, nlen, nskip, rescale=True, inception=False,
                  strides=None, kernels=None, filters=None, *, vdata=None, basedir="model/", device=0, seed=0, translator=None,
                  precision=None, log=print, rank=0, world=1, dp_unique_id=None, videos=None, device_resize=False,
-                 grad_clip=None, skip_nonfinite=False, var_list=None, lr_scales=None):
+                 grad_clip=None, skip_nonfinite=False, var_list=None, lr_scales=None, accum_steps=1):
         """The reference's 14 positional arguments (train_script.py:29-30; the launchers omit the last five, SURVEY.md 3.4-b,
         hence the defaults), then: vdata (array or .npy path of the demo tensor), basedir (logger._snapshot_dir), device,
         seed of the parameter initialiser, an optional ready-made translator (tests), the arithmetic (precision: "f32" | "bf16x3" | "fp16x3" | "fp16x3d",
@@ -117,7 +134,14 @@ class ModelTrainer:
         then).  Defaults: no guard, logs and checkpoints as without these keywords.
         var_list / lr_scales: which variables Adam trains (`minimize(loss, var_list=...)`, train_script.py:126-128).  var_list: fnmatch
         patterns on the TF variable names ("deconv/*") -- Translator.set_trainable, everything else is frozen; lr_scales: {pattern:
-        scale} -- Translator.set_lr_scales.  One of the two; set once before the first step.  Defaults: every variable, as before."""
+        scale} -- Translator.set_lr_scales.  One of the two; set once before the first step.  Defaults: every variable, as before.
+        accum_steps: k > 1 steps every batch in k micro-batches with ONE Adam update on the summed gradient
+        (Translator.train_step_sampled_accum; data parallel: dp_train_step_sampled_accum, one all-reduce per step).  `batch_size` stays
+        the GLOBAL batch and the draws from np.random are those of a trainer with that batch_size; the model is created with
+        max_batch = ceil(batch_size / world / k), so the batch no longer has to fit one launch sequence.  Logs, progress.csv,
+        checkpoints and clips are as before (validation batches are evaluated in the same slices and their scalars combined).
+        Needs the device-resident sampler (a demo tensor on the uint8 lattice).  Out of scope: inception=True -- the front end would
+        have to run on every tgt frame first for the global nn_err -- which raises ValueError.  Default 1: the code path as before."""
         if model not in self.MODELS:
             raise ValueError(f"model must be one of {sorted(self.MODELS)}")
         self.idims, self.nvideos, self.ntrain, self.batch_size = tuple(idims), nvideos, ntrain, batch_size
@@ -137,6 +161,12 @@ class ModelTrainer:
             raise ValueError(f"rank {rank} / world {world}")
         if self.world > 1 and batch_size % self.world:
             raise ValueError(f"batch_size {batch_size} (the GLOBAL batch) must be a multiple of world = {world}")
+        self.accum_steps = int(accum_steps)
+        if self.accum_steps < 1:
+            raise ValueError(f"accum_steps = {accum_steps}")
+        if self.accum_steps > 1 and inception:
+            raise ValueError("accum_steps > 1 is not available with inception=True: its front end would have to run on every tgt frame "
+                             "of the batch first (Translator.accum_begin .. accum_adam work on device maps)")
         self.allloss, self.validloss = [], []
 
     # ------------------------------------------------------------------ the model behind the four sess.run sites
@@ -152,8 +182,8 @@ class ModelTrainer:
             tr.tr.init_params(self.seed)
             return tr
         variant = self.MODELS[self.model]
-        tr = Translator(H, W, featsize=100 if variant == "real" else 1024, max_batch=self.batch_size // self.world, device=self.device,
-                        variant=variant, precision=self.precision)
+        tr = Translator(H, W, featsize=100 if variant == "real" else 1024, max_batch=-(-(self.batch_size // self.world) // self.accum_steps),
+                        device=self.device, variant=variant, precision=self.precision)
         tr.init_params(self.seed)                                  # tf.global_variables_initializer, train_script.py:129
         return tr
 
@@ -249,8 +279,16 @@ class ModelTrainer:
                                      f"and it does not fit on the device ({e}): fewer videos, or one GPU (host gather)") from e
                 raise
         dp_incep = dp and self.inception                           # nn_err of the global batch on the device (ctx_dp_nn_err)
+        accum = self.accum_steps > 1
+        if accum and not resident:
+            raise ValueError("accum_steps > 1 steps through the device-resident sampler: the demo tensor must lie on the uint8 lattice "
+                             "(k / 127.5 - 1, what train_script.py:16-19 makes of video frames)")
+        micro = -(-Bl // self.accum_steps)                         # rows of a micro-batch (the last may be short: micro_slices)
 
-        def train_step(cs, ct):
+        def train_step(cs, ct, want_err=False):
+            if accum:                                              # GLOBAL scalars, and nn_err of the whole batch from the device
+                step = tr.dp_train_step_sampled_accum if dp else tr.train_step_sampled_accum
+                return step(cs, ct, micro, lr=LEARNING_RATE, nlen=nlen if want_err else None)
             if dp:
                 return tr.dp_train_step_sampled(cs, ct, lr=LEARNING_RATE)          # GLOBAL scalars
             if resident:
@@ -265,6 +303,15 @@ class ModelTrainer:
             if dp_incep:                                       # GLOBAL scalars; nn_err is taken on the device (dp_nn_err)
                 return tr.dp_eval_sampled(np.asarray(cs) + ntrain, np.asarray(ct) + ntrain, outputs=False), None
             src, ctx, tgt = self._batch(validdata, cs, ct)
+            if accum:                                          # the batch does not fit the handle: this rank's rows in the step's slices
+                parts = [(b - a, tr.evaluate(src[a:b], ctx[a:b], tgt[a:b])) for a, b in micro_slices(Bl, self.accum_steps, j0)]
+                # recon sums add, simloss is the mean over the GLOBAL batch, `loss` the terms the model keeps (as ctx_dp_scalars)
+                sim, r1, r2 = allsum([sum(p["simloss"] * n for n, p in parts) / B, sum(p["recon1"] for _, p in parts),
+                                      sum(p["recon2"] for _, p in parts)])
+                terms = int(getattr(getattr(tr, "cfg", None), "loss_terms", 0) or 0) or 7
+                loss = (r1 if terms & 1 else 0.0) + (r2 if terms & 2 else 0.0) + (sim if terms & 4 else 0.0)
+                return dict(loss=float(loss), simloss=float(sim), recon1=float(r1), recon2=float(r2),
+                            out=np.concatenate([p["out"] for _, p in parts]), out2=np.concatenate([p["out2"] for _, p in parts])), tgt
             if dp:                                             # GLOBAL scalars; out / out2 = this rank's rows
                 ev = tr.dp_eval_sampled(np.asarray(cs) + ntrain, np.asarray(ct) + ntrain)
             elif resident:
@@ -289,14 +336,16 @@ class ModelTrainer:
         for itr in range(1, self.nitr):
             choicesrc = np.random.choice(ntrain, B)
             choicetgt = np.random.choice(ntrain, B)
-            sc = train_step(choicesrc, choicetgt)
+            sc = train_step(choicesrc, choicetgt, want_err=itr % 4 == 0)
             if guarded and self.skip_nonfinite:                # (the step has synchronised for its scalars: the counters are final)
                 now = core.guard_stats()["steps_skipped"]
                 if now > skipped:
                     skipped = now
                     log("%s skipped: non-finite gradient, parameters and Adam moments unchanged (%s so far)" % (itr, skipped))
             if itr % 4 == 0:
-                if dp_incep:                                   # the tgt maps exist only on the device, one shard per rank
+                if accum:                                      # summed over the micro-batches on the device
+                    err = sc["nn_err"]
+                elif dp_incep:                                 # the tgt maps exist only on the device, one shard per rank
                     err = int(tr.dp_nn_err(nlen))
                 else:
                     out, _, tgt = core.last_outputs(out=True, tgt=True)

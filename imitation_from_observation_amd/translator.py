@@ -665,6 +665,70 @@ class Translator:
     def dev_adam(self, lr=1e-4):
         self._ck(self._lib.ctx_dev_adam(self._h, float(lr)))
 
+    # ------------------------------------------------------------------ gradient accumulation (include/ctxtrans.h: ctx_accum_*)
+    def accum_begin(self, total_batch):
+        """Open an accumulation of `total_batch` triples: ONE Adam step from several micro-batches of at most max_batch rows each
+        (after dp_init: the GLOBAL batch over all ranks, a multiple of the world size).  0 cancels an open one.  While one is open
+        every other Adam update of the handle raises CtxError (CTX_E_STATE); inference, evaluate and the VJP calls stay allowed."""
+        self._ck(self._lib.ctx_accum_begin(self._h, int(total_batch)))
+
+    def accum_dev_forward_backward(self, d_src, d_ctx, d_tgt, B):
+        """One micro-batch (integer device addresses of f32 [B,H,W,3]): dev_forward_backward(sim_batch = the accumulation's total)
+        whose gradient joins the sum.  Micro-batch j > 0 of a dropout model draws masks of its own.  Asynchronous."""
+        self._ck(self._lib.ctx_accum_dev_forward_backward(self._h, ctypes.c_void_p(d_src), ctypes.c_void_p(d_ctx), ctypes.c_void_p(d_tgt),
+                                                           int(B)))
+
+    def _accum_close(self, fn, lr, scalars):
+        sc = np.empty(4, np.float32) if scalars else None
+        self._ck(fn(self._h, float(lr), _fp(sc) if scalars else None))
+        if scalars:
+            return dict(loss=float(sc[0]), simloss=float(sc[1]), recon1=float(sc[2]), recon2=float(sc[3]))
+
+    def accum_adam(self, lr=1e-4, scalars=True):
+        """Close the accumulation: the gradient arena receives the f32 sum ((g1 + g2) + ...) + gk of the micro-batches' gradients and
+        ONE Adam update (guard and mask as set, acting on the sum) runs on it; the step count advances by one.  CtxError
+        (CTX_E_STATE) unless every announced row has been seen.  scalars=True synchronises and returns the whole batch's
+        dict(loss, simloss, recon1, recon2).  get_grads() afterwards returns the gradient Adam consumed."""
+        return self._accum_close(self._lib.ctx_accum_adam, lr, scalars)
+
+    def dp_accum_adam(self, lr=1e-4, scalars=True):
+        """accum_adam on a handle after dp_init (collective): ONE all-reduce of the summed gradient, then Adam; GLOBAL scalars."""
+        return self._accum_close(self._lib.ctx_dp_accum_adam, lr, scalars)
+
+    def accum_state(self):
+        """(rows this handle has added, announced total batch); (0, 0) when no accumulation is open."""
+        r, t = ctypes.c_int(0), ctypes.c_int(0)
+        self._ck(self._lib.ctx_accum_state(self._h, ctypes.byref(r), ctypes.byref(t)))
+        return int(r.value), int(t.value)
+
+    def _sampled_accum(self, fn, choicesrc, choicetgt, micro_batch, lr, nlen):
+        cs = np.ascontiguousarray(choicesrc, dtype=np.int32)
+        ct = np.ascontiguousarray(choicetgt, dtype=np.int32)
+        if cs.shape != ct.shape or cs.ndim != 1:
+            raise ValueError("choicesrc / choicetgt must be 1-D and equally long")
+        sc = np.empty(4, np.float32)
+        err = ctypes.c_int64()
+        ip = ctypes.POINTER(ctypes.c_int32)
+        self._ck(fn(self._h, cs.ctypes.data_as(ip), ct.ctypes.data_as(ip), cs.size, int(micro_batch), float(lr), _fp(sc),
+                    int(nlen or 0), ctypes.byref(err) if nlen else None))
+        res = dict(loss=float(sc[0]), simloss=float(sc[1]), recon1=float(sc[2]), recon2=float(sc[3]))
+        if nlen:
+            res["nn_err"] = int(err.value)
+        return res
+
+    def train_step_sampled_accum(self, choicesrc, choicetgt, micro_batch, lr=1e-4, nlen=None):
+        """train_step_sampled on a batch larger than max_batch (ctx_accum_train_step_sampled): the rows are gathered from the resident
+        demo tensor and stepped in micro-batches of `micro_batch` <= max_batch rows (the last may be short), one Adam update on the
+        summed gradient.  Returns the whole batch's dict(loss, simloss, recon1, recon2), plus nn_err -- the trainer's nn_err of the
+        whole batch, taken on the device -- when `nlen` is given.  Not for InceptionTranslator (its front end would have to run on
+        every tgt frame first) and not for host frames (train_step / train_step_u8): use accum_begin .. accum_adam there."""
+        return self._sampled_accum(self._lib.ctx_accum_train_step_sampled, choicesrc, choicetgt, micro_batch, lr, nlen)
+
+    def dp_train_step_sampled_accum(self, choicesrc, choicetgt, micro_batch, lr=1e-4, nlen=None):
+        """The same on N GPUs (ctx_dp_accum_train_step_sampled; collective): every rank passes the SAME global index arrays and steps
+        its rows [rank B/world, ...) in micro-batches, ONE all-reduce per step.  Scalars and nn_err are global."""
+        return self._sampled_accum(self._lib.ctx_dp_accum_train_step_sampled, choicesrc, choicetgt, micro_batch, lr, nlen)
+
     # ------------------------------------------------------------------ guarded Adam (include/ctxtrans.h: ctx_set_grad_guard)
     def set_grad_guard(self, clip_norm=None, skip_nonfinite=True):
         """Guard every later Adam update of this handle, on the device: clip the gradient by its global norm (clip_norm; None / 0 =

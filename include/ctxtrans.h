@@ -51,7 +51,7 @@ extern "C" {
                                ctx_reward_get_cache, ctx_reward_stats, option reward_split; ctx_resize_*; the device-uint8 forms
                                ctx_resize_u8_dev / _v, ctx_cnn_*_dev_u8, ctx_disc_stream / _data_begin / _reward_paths_dev;
                                ctx_reconstruct / _f32 / _dev, ctx_reward_costs_recon / _dev;
-                               ctx_set_grad_guard, ctx_grad_norm, ctx_grad_guard_stats */
+                               ctx_set_grad_guard, ctx_grad_norm, ctx_grad_guard_stats; ctx_accum_* / ctx_dp_accum_* */
 
 enum {
     CTX_OK = 0,
@@ -560,6 +560,61 @@ int ctx_dp_allreduce_host_f64(ctx_handle* h, double* buf, size_t n);
  * in which each rank wrote its own rows (exact: one non-zero contributor per element), rank r's share is taken with j0 = r * B, and
  * the shares are summed.  *err is the same on every rank. */
 int ctx_dp_nn_err(ctx_handle* h, int nlen, int64_t* err);
+
+/* ---- gradient accumulation: ONE Adam step from several micro-batches (new: the reference steps on what one feed carries) ----------
+ * A step whose batch is larger than max_batch.  A data-parallel step is a sum of shard gradients with the simloss mean over the
+ * global batch; the same arithmetic in micro-batches on one handle:
+ *   ctx_accum_begin(h, total)                      opens an accumulation of `total` triples (resets the rows seen, the scalar sums and
+ *                                                  the micro-batch ordinal); total = 0 cancels an open one.  Under ctx_dp_init `total`
+ *                                                  is the GLOBAL batch over all ranks (a multiple of the world size) and this handle
+ *                                                  adds total / world rows.  The first call allocates the accumulator, one more
+ *                                                  buffer of the parameters' size BESIDE the arena (caller-supplied arenas and
+ *                                                  ctx_arena_bytes are unchanged); it is freed with the handle.
+ *   ctx_accum_dev_forward_backward(h, s, c, t, B)  one micro-batch, B <= max_batch, sizes may differ: the training-mode forward and
+ *                                                  the backward of ctx_dev_forward_backward(sim_batch = total) -- pruned under a mask
+ *                                                  as a plain backward is, no bucket callback -- and its gradient joins the sum.
+ *                                                  CTX_E_STATE when the rows seen would exceed the handle's share.  Asynchronous.
+ *   ctx_accum_adam(h, lr, scalars)                 CTX_E_STATE unless every row has been seen.  Writes the sum into the gradient arena
+ *                                                  and runs the Adam update of ctx_dev_adam on it; the step count advances by ONE and
+ *                                                  the accumulation is closed.  scalars (nullable; non-NULL synchronises): {loss,
+ *                                                  simloss, recon1, recon2} of the whole batch -- recon sums add, simloss is the
+ *                                                  mean weighted by rows / total, loss is formed from the handle's loss_terms; they
+ *                                                  are also what ctx_dev_scalars returns afterwards.
+ *   ctx_dp_accum_adam(h, lr, scalars)              the same on a handle after ctx_dp_init, with ONE SUM all-reduce of the gradient
+ *                                                  arena between the sum and Adam (collective); scalars: the GLOBAL ones.
+ *   ctx_accum_state(h, &rows_seen, &total)         rows this handle has added and the announced total (0 = none open).
+ * The sum: the gradient arena ends up holding ((g1 + g2) + ...) + gk, g_j the gradient ctx_dev_forward_backward(sim_batch = total)
+ * gives for micro-batch j -- one plain f32 add per element and micro-batch in that order, the same bits on every run.  The last
+ * micro-batch's gradient is not copied: it waits in the gradient arena, where ctx_accum_adam adds the sum of the others to it, so
+ * nothing may overwrite the gradient arena between the last micro-batch and ctx_accum_adam.  An accumulation of ONE micro-batch is
+ * ctx_dev_forward_backward + ctx_dev_adam bit for bit and launch for launch.  Afterwards ctx_get_grads / ctx_grad_norm see the
+ * gradient Adam consumed.
+ *   - guard (ctx_set_grad_guard): the norm, the clip and the non-finite skip act on the SUM; one NaN micro-batch skips the whole step
+ *     and leaves parameters and moments untouched.
+ *   - mask (ctx_set_param_lr_scale): the sum runs over the trainable tensors only; frozen floats of the accumulator and of the
+ *     gradient arena are neither read nor written.
+ *   - dropout (CTX_VARIANT_REAL, keep_prob < 1): the Adam step count does not move between micro-batches, so micro-batch j mixes its
+ *     ordinal j into the mask seed (as a data-parallel rank is mixed in); j = 0 leaves the seed alone.  Later micro-batches draw
+ *     masks of their own -- a host loop over ctx_dev_forward_backward would draw the SAME masks k times.
+ *   - while an accumulation is open every other Adam update (ctx_dev_adam, ctx_train_step*, ctx_dev_train_step, ctx_dp_train_step*,
+ *     ctx_profile_step) returns CTX_E_STATE; inference, ctx_eval* and the VJP calls stay allowed (a VJP backward overwrites the
+ *     gradient arena: not behind the last micro-batch).
+ * The trainer's entry: ctx_accum_train_step_sampled is ctx_train_step_sampled on a batch of B_total rows in micro-batches of micro_B
+ * (<= max_batch; the last may be short).  Indices are checked over all B_total rows first; micro-batch j gathers rows [j micro_B, ...)
+ * with t = b % T taken on the row b of the WHOLE batch, so the frames are those of one B_total-row gather.  nn_err (nullable; nlen > 0):
+ * the trainer's nn_err of the whole batch -- every micro-batch's outputs against the tgt rows of ALL B_total rows -- summed on the
+ * device.  ctx_dp_accum_train_step_sampled: rank r takes rows [r B_total / world, ...) of the same global arrays in micro-batches,
+ * one all-reduce per step; scalars and nn_err are global and the same on every rank (collective: every rank must call it).
+ * Synchronous like ctx_train_step_sampled. */
+int ctx_accum_begin(ctx_handle* h, int total_batch);
+int ctx_accum_dev_forward_backward(ctx_handle* h, const float* d_src, const float* d_ctx, const float* d_tgt, int B);
+int ctx_accum_adam(ctx_handle* h, float lr, float scalars[4]);
+int ctx_dp_accum_adam(ctx_handle* h, float lr, float scalars[4]);
+int ctx_accum_state(const ctx_handle* h, int* rows_seen, int* total_batch);
+int ctx_accum_train_step_sampled(ctx_handle* h, const int32_t* choicesrc, const int32_t* choicetgt, int B_total, int micro_B, float lr,
+                                 float scalars[4], int nlen, int64_t* nn_err);
+int ctx_dp_accum_train_step_sampled(ctx_handle* h, const int32_t* choicesrc, const int32_t* choicetgt, int B_total, int micro_B,
+                                    float lr, float scalars[4], int nlen, int64_t* nn_err);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* One entry per launch group of a train step (a layer's forward, input gradient, filter gradient,
