@@ -349,6 +349,8 @@ void adam_begin(ctx_handle* h, float lr) {
 // pads every tensor to one.  The segmented kernels work on whole 16-byte groups, so no group may belong to two tensors.
 int tensor_spans(ctx_handle* h) {
     const size_t n = h->params.size();
+    // (plan_mask gives every tensor a run of its own at worst: the run table must hold them all)
+    if (n > (size_t)ADAM_SEG_MAX) return fail(h, CTX_E_INVALID, "%zu parameter tensors: the run table of the segmented kernels holds %d", n, ADAM_SEG_MAX);
     h->span.resize(n);
     for (size_t i = 0; i < n; ++i) h->span[i].first = h->gen ? h->gen->segs[i].poff : h->params[i].offset;
     for (size_t i = 0; i < n; ++i) {

@@ -18,7 +18,11 @@ Bars (derived, not measured):
   pruned backward           trainable gradients bit-identical to the unmasked backward's (the launches that run are its launches).
 
 ContextAEReal has no `conv_context` scope (one encoder serves frames and context), so the mask "conv_context/* trainable" exists for
-ContextSkipNew and ContextAEInception2 only; ContextAEReal runs "translate/* trainable" in its place."""
+ContextSkipNew and ContextAEInception2 only; ContextAEReal runs "translate/* trainable" in its place.
+
+The masks here are hand-picked scopes on fresh handles.  tests/test_gpu_mask_sweep.py runs the rest of the mask space -- every tensor
+alone, every all-but-one, random masks, checkerboards, run tables with one run per tensor, masks that change on a live handle -- against
+tests/_prune_ref.py's statement of the dependency plan."""
 import os
 import subprocess
 import sys
