@@ -168,6 +168,14 @@ SIGNATURES = {
                                                 _c.c_int, _c.POINTER(_c.c_int64)]),
     "ctx_dp_accum_train_step_sampled": (_c.c_int, [_P, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32), _c.c_int, _c.c_int, _c.c_float, _F,
                                                    _c.c_int, _c.POINTER(_c.c_int64)]),
+    "ctx_ema_enable": (_c.c_int, [_P, _c.c_float, _c.c_int]),
+    "ctx_ema_disable": (_c.c_int, [_P]),
+    "ctx_ema_reset": (_c.c_int, [_P]),
+    "ctx_ema_update": (_c.c_int, [_P]),
+    "ctx_ema_swap": (_c.c_int, [_P]),
+    "ctx_ema_state": (_c.c_int, [_P, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _F, _c.POINTER(_c.c_int64)]),
+    "ctx_get_ema": (_c.c_int, [_P, _F, _c.c_int64, _c.POINTER(_c.c_int64)]),
+    "ctx_set_ema": (_c.c_int, [_P, _F, _c.c_int64, _c.c_int64]),
     "ctx_profile_step": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_float, _c.c_int, _c.POINTER(CtxProfEntry), _c.c_int,
                                     _c.POINTER(_c.c_int)]),
     "ctx_debug_read": (_c.c_int, [_P, _c.c_char_p, _F, _c.c_size_t]),

@@ -154,6 +154,7 @@ void ctx_destroy(ctx_handle* h) {
     if (h->dp_host_buf) (void)hipFree(h->dp_host_buf);
     if (h->nn_dist) (void)hipFree(h->nn_dist);
     if (h->nn_tgt) (void)hipFree(h->nn_tgt);
+    if (h->ema) (void)hipFree(h->ema);
     for (auto& kv : h->graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
     delete h->gen;
     dp_teardown(h);
@@ -183,12 +184,14 @@ int ctx_param_info(const ctx_handle* h, int index, const char** name, int* ndim,
     return CTX_OK;
 }
 
+// slot 0..3: a section of the arena; SLOT_EMA: the averaged copy (ctx_get_ema / ctx_set_ema), which has the parameter section's layout
+constexpr int SLOT_EMA = -1;
 static int arena_io(ctx_handle* h, int slot, float* host, const float* chost, size_t n) {
     if (!h) return CTX_E_INVALID;
     if (chost && slot == 0) h->pack.version++;
     if ((int64_t)n != h->P) return fail(h, CTX_E_INVALID, "expected %lld floats, got %zu", (long long)h->P, n);
     HIP_TRY(h, hipSetDevice(h->device));
-    float* dev = h->arena + slot * h->Ppad;
+    float* dev = slot == SLOT_EMA ? h->ema : h->arena + slot * h->Ppad;
     if (h->gen) {   // scatter / gather between the TF-shaped vector and the (possibly zero-padded) arena
         std::vector<float> padded((size_t)h->Ppad, 0.f);
         const std::vector<int32_t>& map = h->gen->real2pad;
@@ -217,7 +220,12 @@ static int arena_io(ctx_handle* h, int slot, float* host, const float* chost, si
     return finish(h);
 }
 
-int ctx_set_params(ctx_handle* h, const float* flat, size_t n) { return flat ? arena_io(h, 0, nullptr, flat, n) : CTX_E_INVALID; }
+int ctx_set_params(ctx_handle* h, const float* flat, size_t n) {
+    if (!h || !flat) return CTX_E_INVALID;
+    if (h->ema_swapped) return ema_refuse(h, "ctx_set_params");
+    TRY(arena_io(h, 0, nullptr, flat, n));
+    return ema_reset(h);             // all parameters replaced from outside a step: the averaged copy starts again from them
+}
 int ctx_get_params(ctx_handle* h, float* flat, size_t n) { return flat ? arena_io(h, 0, flat, nullptr, n) : CTX_E_INVALID; }
 int ctx_get_grads(ctx_handle* h, float* flat, size_t n) {
     if (!flat) return CTX_E_INVALID;
@@ -270,6 +278,7 @@ int ctx_get_adam_state(ctx_handle* h, float* m, float* v, size_t n, int64_t* ste
 
 int ctx_init_params(ctx_handle* h, uint64_t seed) {
     if (!h) return CTX_E_INVALID;
+    if (h->ema_swapped) return ema_refuse(h, "ctx_init_params");
     std::vector<float> host((size_t)h->P, 0.f);
     std::mt19937_64 rng(seed);
     std::normal_distribution<double> nd(0.0, 1.0);
@@ -1007,6 +1016,98 @@ int ctx_accum_train_step_sampled(ctx_handle* h, const int32_t* choicesrc, const 
     return CTX_OK;
 }
 
+// ---- exponential moving average of the parameters (include/ctxtrans.h; the launch: ctx_engine.cpp ema_enqueue, from adam_end) -------
+static int ema_need(ctx_handle* h, const char* what) {
+    return ema_on(h) ? CTX_OK : fail(h, CTX_E_STATE, "%s on a handle without an averaged copy: ctx_ema_enable first", what);
+}
+
+int ctx_ema_enable(ctx_handle* h, float decay, int warmup) {
+    if (!h) return CTX_E_INVALID;
+    if (!(decay >= 0.f && decay <= 1.f)) return fail(h, CTX_E_INVALID, "decay must lie in [0, 1]");      // (NaN fails the comparison)
+    if (h->ema_swapped) return ema_refuse(h, "ctx_ema_enable");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (!h->ema) {
+        void* q = nullptr;
+        const hipError_t e = hipMalloc(&q, (size_t)h->Ppad * sizeof(float));
+        if (e != hipSuccess) return fail(h, CTX_E_NOMEM, "hipMalloc(%lld bytes) for the averaged copy: %s", (long long)(h->Ppad * sizeof(float)), hipGetErrorString(e));
+        h->ema = (float*)q;
+        const int rc = ema_reset(h);
+        if (rc != CTX_OK) { (void)hipFree(q); h->ema = nullptr; return rc; }
+    }
+    h->ema_decay = decay;
+    h->ema_warm = warmup != 0;
+    return CTX_OK;
+}
+
+int ctx_ema_disable(ctx_handle* h) {
+    if (!h) return CTX_E_INVALID;
+    TRY(ema_need(h, "ctx_ema_disable"));
+    if (h->ema_swapped) return ema_refuse(h, "ctx_ema_disable");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));      // updates in flight still write the shadow
+    (void)hipFree(h->ema);
+    h->ema = nullptr;
+    h->ema_decay = 0.f; h->ema_warm = false; h->ema_t = 0;
+    return CTX_OK;
+}
+
+int ctx_ema_reset(ctx_handle* h) {
+    if (!h) return CTX_E_INVALID;
+    TRY(ema_need(h, "ctx_ema_reset"));
+    if (h->ema_swapped) return ema_refuse(h, "ctx_ema_reset");
+    HIP_TRY(h, hipSetDevice(h->device));
+    return ema_reset(h);
+}
+
+int ctx_ema_update(ctx_handle* h) {
+    if (!h) return CTX_E_INVALID;
+    TRY(ema_need(h, "ctx_ema_update"));
+    if (h->ema_swapped) return ema_refuse(h, "ctx_ema_update");
+    HIP_TRY(h, hipSetDevice(h->device));
+    ema_enqueue(h, false);           // the caller's own optimiser stepped: the mask holds, the guard has no say
+    HIP_TRY(h, hipGetLastError());
+    return CTX_OK;
+}
+
+int ctx_ema_swap(ctx_handle* h) {
+    if (!h) return CTX_E_INVALID;
+    TRY(ema_need(h, "ctx_ema_swap"));
+    if (accum_open(h)) return accum_refuse(h, "ctx_ema_swap");
+    HIP_TRY(h, hipSetDevice(h->device));
+    ema_swap(h->stream, h->arena, h->ema, h->Ppad);
+    HIP_TRY(h, hipGetLastError());
+    h->ema_swapped = !h->ema_swapped;
+    h->pack.version++;               // the parameters changed: packed filters go stale, graphs captured on them are dropped at their next call
+    return CTX_OK;
+}
+
+int ctx_ema_state(ctx_handle* h, int* enabled, int* swapped, float* decay, int64_t* updates) {
+    if (!h) return CTX_E_INVALID;
+    if (enabled) *enabled = ema_on(h) ? 1 : 0;
+    if (swapped) *swapped = h->ema_swapped ? 1 : 0;
+    if (decay) *decay = h->ema_decay;
+    if (updates) *updates = h->ema_t;
+    return CTX_OK;
+}
+
+int ctx_get_ema(ctx_handle* h, float* out, int64_t n, int64_t* updates) {
+    if (!h || !out || n < 0) return CTX_E_INVALID;
+    TRY(ema_need(h, "ctx_get_ema"));
+    if (h->ema_swapped) return ema_refuse(h, "ctx_get_ema");
+    TRY(arena_io(h, SLOT_EMA, out, nullptr, (size_t)n));
+    if (updates) *updates = h->ema_t;
+    return CTX_OK;
+}
+
+int ctx_set_ema(ctx_handle* h, const float* in, int64_t n, int64_t updates) {
+    if (!h || !in || n < 0 || updates < 0) return CTX_E_INVALID;
+    TRY(ema_need(h, "ctx_set_ema"));
+    if (h->ema_swapped) return ema_refuse(h, "ctx_set_ema");
+    TRY(arena_io(h, SLOT_EMA, nullptr, in, (size_t)n));
+    h->ema_t = updates;
+    return CTX_OK;
+}
+
 // ---- guarded Adam (include/ctxtrans.h; the launches: ctx_engine.cpp adam_end) ----------------------------------------------------
 int ctx_set_grad_guard(ctx_handle* h, float clip_norm, int skip_nonfinite) {
     if (!h) return CTX_E_INVALID;
@@ -1139,6 +1240,7 @@ int ctx_profile_step(ctx_handle* h, const float* d_src, const float* d_ctx, cons
     TRY(check_B(h, B));
     if (!d_src || !d_ctx || !d_tgt || iters <= 0 || !n_entries) return fail(h, CTX_E_INVALID, "bad argument");
     if (accum_open(h)) return accum_refuse(h, "ctx_profile_step");
+    if (h->ema_swapped) return ema_refuse(h, "ctx_profile_step");
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t bytes = (size_t)B * h->npi * sizeof(float);
     for (auto& m : h->prof_ms) m = 0.0;

@@ -109,6 +109,7 @@ int ctx_dp_init(ctx_handle* h, const uint8_t id[CTX_DP_UNIQUE_ID_BYTES], int ran
     if (!h) return CTX_E_INVALID;
     if (!id || world < 1 || rank < 0 || rank >= world) return fail(h, CTX_E_INVALID, "bad rank %d / world %d", rank, world);
     if (h->dp_comm) return fail(h, CTX_E_STATE, "ctx_dp_init was already called on this handle");
+    if (h->ema_swapped) return ema_refuse(h, "ctx_dp_init");
     if (!rccl_load()) return fail(h, CTX_E_DEVICE, "librccl could not be loaded: %s", rccl().err.c_str());
     HIP_TRY(h, hipSetDevice(h->device));
     ncclUniqueId u;
@@ -139,6 +140,8 @@ int ctx_dp_init(ctx_handle* h, const uint8_t id[CTX_DP_UNIQUE_ID_BYTES], int ran
         h->adam_t = (int64_t)t2[0] + ((int64_t)t2[1] << 24);
     }
     HIP_TRY(h, hipStreamSynchronize(h->dp_stream));
+    // every parameter was replaced from outside a step: the averaged copy (ctx_ema_enable) starts again from rank 0's parameters
+    TRY(ema_reset(h));
     return CTX_OK;
 }
 
@@ -164,6 +167,7 @@ int ctx_dp_allreduce_grads(ctx_handle* h) {
 // GLOBAL batch, the gradient buckets sent from inside backward, the rest after it, Adam
 static int dp_step_on_img(ctx_handle* h, int B, float lr, float scalars[4]) {
     if (accum_open(h)) return accum_refuse(h, "a data-parallel training step");
+    if (h->ema_swapped) return ema_refuse(h, "a data-parallel training step");
     h->drop_on = true;
     forward(h, B, MODE_TRAIN);
     // two buckets: [split, Ppad) = translate/* + deconv/* leaves from inside backward (fire_bucket) and travels while the

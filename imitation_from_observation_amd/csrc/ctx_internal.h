@@ -271,6 +271,14 @@ struct ctx_handle {
     double* accum_slots = nullptr;
     int accum_total = 0, accum_share = 0, accum_rows = 0, accum_micro = 0;
     uint32_t accum_mix = 0;       // ordinal of the micro-batch whose forward is being enqueued: mixed into the dropout seed (0 = not at all)
+    // exponential moving average of the parameters (ctx_ema_*; ema == nullptr = off: no extra launch): `ema` = the shadow, Ppad floats
+    // in the layout of the arena's parameter section, the library's OWN allocation (also beside a caller's arena; not in `allocs`:
+    // ctx_ema_disable frees it).  adam_end enqueues one update as its last launch.  ema_t = updates ISSUED (a step the guard skips on
+    // the device counts, as adam_t does) and the t of the warm-up schedule; ema_swapped: parameters and shadow have changed places.
+    float* ema = nullptr;
+    float ema_decay = 0.f;
+    bool ema_warm = false, ema_swapped = false;
+    int64_t ema_t = 0;
     // tf.nn.dropout (CTX_VARIANT_REAL with keep_prob < 1): on only while a TRAINING step (forward + backward) is being enqueued
     bool drop_on = false;
     uint64_t drop_seed = 0;
@@ -356,6 +364,12 @@ int accum_micro_on_img(ctx_handle* h, int B, int nn_nlen, int nn_j0);
 int accum_fold(ctx_handle* h);
 void accum_close(ctx_handle* h);
 int accum_gather_tgt(ctx_handle* h, const int32_t* choicetgt, int B_total);      // ctx_abi.cpp: the whole batch's tgt rows -> h->nn_tgt
+// exponential moving average of the parameters (ctx_engine.cpp): CTX_E_STATE for a write of parameters or shadow while they are
+// swapped | one update enqueued on h->stream (guarded: under the guard's skip decision) | shadow = parameters, ema_t = 0 (no-op when off)
+inline bool ema_on(const ctx_handle* h) { return h->ema != nullptr; }
+int ema_refuse(ctx_handle* h, const char* what);
+void ema_enqueue(ctx_handle* h, bool guarded);
+int ema_reset(ctx_handle* h);
 int dp_wait(ctx_handle* h);                                           // ctx_dp.cpp
 int stage_frames(ctx_handle* h, const float* d_src, const float* d_ctx, const float* d_tgt, int B);   // ctx_abi.cpp
 int nn_err_enqueue(ctx_handle* h, const float* tgt, int Bt, int nlen, int j0);                       // ctx_abi.cpp: h->nn_res[0]

@@ -1714,6 +1714,71 @@ void grad_accum_segmented(hipStream_t s, float* acc, float* g, const AdamSegs& T
     else hipLaunchKernelGGL((grad_accum_seg_kernel<ACCUM_FOLD, false>), grid, block, 0, s, acc, g, T);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Exponential moving average of the parameters (ctx_ema_*): the shadow e beside the arena, one elementwise pass over 16-byte groups
+// after Adam.  e = fmaf(c, p - e, e) with c = 1 - decay from the host -- TF's  shadow -= (1 - decay) * (shadow - var)  with the one
+// contraction spelled out, so no compiler picks another: e == p stays e exactly (p - e = 0), c == 0 leaves e exactly.  Streaming
+// like Adam (nontemporal 16-byte loads and stores, no atomics); ctl (nullable): a step the guard skipped (apply == 0) returns at
+// once, uniformly, as adam_guarded_kernel does.  SEG walk: adam_seg_kernel's, so a frozen tensor costs no traffic and keeps its bits.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void ema_group(float* __restrict__ e, const float* __restrict__ p, int64_t i, float c) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const f4 pp = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p + i));
+    f4 ee = __builtin_nontemporal_load(reinterpret_cast<const f4*>(e + i));
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ee[k] = __builtin_fmaf(c, pp[k] - ee[k], ee[k]);
+    __builtin_nontemporal_store(ee, reinterpret_cast<f4*>(e + i));
+}
+
+__global__ __launch_bounds__(NTHREADS) void ema_update_kernel(float* __restrict__ e, const float* __restrict__ p, int64_t n4, float c,
+                                                              const GuardCtl* __restrict__ ctl) {
+    if (ctl && ctl->apply == 0) return;        // (uniform) a skipped step leaves the shadow untouched too
+    for (int64_t g = (int64_t)blockIdx.x * NTHREADS + threadIdx.x; g < n4; g += (int64_t)gridDim.x * NTHREADS) ema_group(e, p, g * 4, c);
+}
+
+__global__ __launch_bounds__(NTHREADS) void ema_update_seg_kernel(float* __restrict__ e, const float* __restrict__ p, const AdamSegs T,
+                                                                  float c, const GuardCtl* __restrict__ ctl) {
+    if (ctl && ctl->apply == 0) return;        // (uniform)
+    __shared__ SegTable L;
+    seg_table_load(L, T);
+    const uint32_t total = L.pre[ADAM_SEG_MAX];
+    int run = 0;
+    for (uint32_t g = blockIdx.x * NTHREADS + threadIdx.x; g < total; g += gridDim.x * NTHREADS) {
+        while (g >= L.pre[run + 1]) ++run;
+        ema_group(e, p, ((int64_t)L.first[run] + (g - L.pre[run])) * 4, c);
+    }
+}
+
+// p <-> e over whole 16-byte groups: pure moves, so two swaps restore every bit
+__global__ __launch_bounds__(NTHREADS) void ema_swap_kernel(float* __restrict__ p, float* __restrict__ e, int64_t n4) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    for (int64_t g = (int64_t)blockIdx.x * NTHREADS + threadIdx.x; g < n4; g += (int64_t)gridDim.x * NTHREADS) {
+        f4* p4 = reinterpret_cast<f4*>(p) + g;
+        f4* e4 = reinterpret_cast<f4*>(e) + g;
+        const f4 pp = __builtin_nontemporal_load(p4), ee = __builtin_nontemporal_load(e4);
+        __builtin_nontemporal_store(ee, p4);
+        __builtin_nontemporal_store(pp, e4);
+    }
+}
+
+void ema_update(hipStream_t s, float* e, const float* p, int64_t n, float c, const GuardCtl* ctl) {
+    const int64_t n4 = n / 4;                  // n = Ppad, a multiple of 64
+    if (n4 <= 0) return;
+    hipLaunchKernelGGL(ema_update_kernel, dim3(ew_blocks(n4)), dim3(NTHREADS), 0, s, e, p, n4, c, ctl);
+}
+
+void ema_update_segmented(hipStream_t s, float* e, const float* p, const AdamSegs& T, float c, const GuardCtl* ctl) {
+    const uint32_t total = T.pre[T.n];
+    if (!total) return;
+    hipLaunchKernelGGL(ema_update_seg_kernel, dim3(ew_blocks(total)), dim3(NTHREADS), 0, s, e, p, T, c, ctl);
+}
+
+void ema_swap(hipStream_t s, float* p, float* e, int64_t n) {
+    const int64_t n4 = n / 4;
+    if (n4 <= 0) return;
+    hipLaunchKernelGGL(ema_swap_kernel, dim3(ew_blocks(n4)), dim3(NTHREADS), 0, s, p, e, n4);
+}
+
 // {loss, simloss, recon1, recon2} of a micro-batch into the accumulation's f64 slots: the recon sums add, simloss -- a mean over the
 // micro-batch's rows -- enters with the weight rows / total; slot 0 stays unused (`loss` is formed from the other three at the end).
 // nn (nullable): a micro-batch's nn_err share, added into slot 4.  One thread; the host never waits for it.

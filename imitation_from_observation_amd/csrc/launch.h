@@ -308,4 +308,11 @@ void scalars_finish(hipStream_t s, const double* slots, float* scalars, int term
 // the tgt slot of gather_triples alone: out[b] = vdata[(b0 + b) % T][ctgt[b]], b < B (the whole batch's tgt rows for nn_err)
 void gather_tgt(hipStream_t s, const uint8_t* vdata, int T, int N, int64_t npi, const int* ctgt, int B, int b0, const float* lut, float* out);
 
+// Exponential moving average of the parameters (ctx_ema_*).  ema_update: e = fmaf(c, p - e, e) over the 16-byte groups of [0, n)
+// (n a multiple of 4), c = 1 - decay; _segmented: over the runs of T only, nothing between them read or written.  ctl (nullable):
+// nothing at all when ctl->apply == 0 (a step the guard skipped).  ema_swap: p <-> e over [0, n), pure moves.
+void ema_update(hipStream_t s, float* e, const float* p, int64_t n, float c, const GuardCtl* ctl);
+void ema_update_segmented(hipStream_t s, float* e, const float* p, const AdamSegs& T, float c, const GuardCtl* ctl);
+void ema_swap(hipStream_t s, float* p, float* e, int64_t n);
+
 }  // namespace ctx

@@ -185,8 +185,8 @@ class InceptionTranslator:
     def last_outputs(self, out=True, out2=False, tgt=False):
         return self.tr.last_outputs(out=out, out2=out2, tgt=tgt)
 
-    def save(self, path, with_adam=True, prefix=""):
-        return self.tr.save(path, with_adam=with_adam, prefix=prefix)
+    def save(self, path, with_adam=True, prefix="", weights="params"):
+        return self.tr.save(path, with_adam=with_adam, prefix=prefix, weights=weights)
 
     def load(self, path, prefix=""):
         self.tr.load(path, prefix=prefix)

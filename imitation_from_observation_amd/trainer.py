@@ -53,6 +53,7 @@ training batch is summed on the device.  Not for `inception=True`.
 """
 from __future__ import annotations
 
+import contextlib
 import csv
 import os
 
@@ -119,7 +120,7 @@ class ModelTrainer:
     def __init__(self, idims, nvideos, ntrain, batch_size, model, nitr, save_every, nlen, nskip, rescale=True, inception=False,
                  strides=None, kernels=None, filters=None, *, vdata=None, basedir="model/", device=0, seed=0, translator=None,
                  precision=None, log=print, rank=0, world=1, dp_unique_id=None, videos=None, device_resize=False,
-                 grad_clip=None, skip_nonfinite=False, var_list=None, lr_scales=None, accum_steps=1):
+                 grad_clip=None, skip_nonfinite=False, var_list=None, lr_scales=None, ema_decay=None, ema_eval=False, accum_steps=1):
         """The reference's 14 positional arguments (train_script.py:29-30; the launchers omit the last five, SURVEY.md 3.4-b,
         hence the defaults), then: vdata (array or .npy path of the demo tensor), basedir (logger._snapshot_dir), device,
         seed of the parameter initialiser, an optional ready-made translator (tests), the arithmetic (precision: "f32" | "bf16x3" | "fp16x3" | "fp16x3d",
@@ -135,6 +136,11 @@ class ModelTrainer:
         var_list / lr_scales: which variables Adam trains (`minimize(loss, var_list=...)`, train_script.py:126-128).  var_list: fnmatch
         patterns on the TF variable names ("deconv/*") -- Translator.set_trainable, everything else is frozen; lr_scales: {pattern:
         scale} -- Translator.set_lr_scales.  One of the two; set once before the first step.  Defaults: every variable, as before.
+        ema_decay: a decay in [0, 1) keeps an exponential moving average of the parameters on the device (Translator.set_ema with the
+        warm-up schedule, one extra launch per Adam update) and writes, at every `save_every`, a second file `model_ema_<itr>` beside
+        the usual checkpoint: the AVERAGED weights under the variable names (Translator.save(weights="ema")), which the reward hook
+        loads like any checkpoint.  ema_eval=True (needs ema_decay) runs the validation batch and the clips of a `save_every`
+        iteration on the averaged weights (one extra log line then).  Defaults: no average; logs, CSV, checkpoints and draws as before.
         accum_steps: k > 1 steps every batch in k micro-batches with ONE Adam update on the summed gradient
         (Translator.train_step_sampled_accum; data parallel: dp_train_step_sampled_accum, one all-reduce per step).  `batch_size` stays
         the GLOBAL batch and the draws from np.random are those of a trainer with that batch_size; the model is created with
@@ -161,6 +167,11 @@ class ModelTrainer:
             raise ValueError(f"rank {rank} / world {world}")
         if self.world > 1 and batch_size % self.world:
             raise ValueError(f"batch_size {batch_size} (the GLOBAL batch) must be a multiple of world = {world}")
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay = {ema_decay} must lie in [0, 1)")
+        if ema_eval and ema_decay is None:
+            raise ValueError("ema_eval=True evaluates on the averaged weights: give ema_decay")
+        self.ema_decay, self.ema_eval = (None if ema_decay is None else float(ema_decay)), bool(ema_eval)
         self.accum_steps = int(accum_steps)
         if self.accum_steps < 1:
             raise ValueError(f"accum_steps = {accum_steps}")
@@ -331,6 +342,8 @@ class ModelTrainer:
             core.set_trainable(self.var_list)
         elif self.lr_scales is not None:
             core.set_lr_scales(self.lr_scales)
+        if self.ema_decay is not None:
+            core.set_ema(self.ema_decay)
         skipped = 0
         rows = []
         for itr in range(1, self.nitr):
@@ -357,7 +370,11 @@ class ModelTrainer:
             if itr % 40 == 0 or itr % self.save_every == 0:
                 choicesrc = np.random.choice(nvalid, B)
                 choicetgt = np.random.choice(nvalid, B)
-                ev, tgt = evaluate(choicesrc, choicetgt)
+                on_ema = self.ema_eval and itr % self.save_every == 0      # this iteration's validation and clips on the averaged weights
+                if on_ema:
+                    log("%s validation and clips on the averaged weights (decay %s, %s updates)" % (itr, self.ema_decay, core.ema_state()["updates"]))
+                with core.ema_weights() if on_ema else contextlib.nullcontext():
+                    ev, tgt = evaluate(choicesrc, choicetgt)
                 loss, sim, r1, r2 = ev["loss"], ev["simloss"], ev["recon1"], ev["recon2"]
                 err = int(tr.dp_nn_err(nlen)) if dp_incep else int(allsum([nn_err(tgt, ev["out"], nlen, j0)])[0])
                 log("%s %s %s %s %s %s E" % (itr, loss, sim, r1, r2, err))
@@ -366,25 +383,28 @@ class ModelTrainer:
                     if rank == 0:
                         os.mkdir(basedir + str(itr))
                         core.save("%s%d/model_%d_%.2f_%.2f_%.2f_%d" % (basedir, itr, itr, loss, r1, r2, err), prefix="contextmodel/")
+                        if self.ema_decay is not None:         # the inference checkpoint of the averaged weights, beside it
+                            core.save("%s%d/model_ema_%d" % (basedir, itr, itr), prefix="contextmodel/", weights="ema")
                         np.save("%s%d/validloss" % (basedir, itr), self.validloss)
                     if not self.inception:
-                        for kk in range(10):
-                            choicesrc = [np.random.randint(nvalid)] * B
-                            choicetgt = [np.random.randint(nvalid)] * B
-                            clip, _ = evaluate(choicesrc, choicetgt)
-                            r1, r2 = clip["recon1"], clip["recon2"]           # the reference's clip fetch overwrites r1 / r2 (:192-193): the
-                                                                              # tabular R1 / R2 of a save iteration are the last clip's
-                            for tag, frames in (("trans", clip["out"]), ("recon", clip["out2"])):
-                                if dp:                         # the clip is rows 0 .. nlen-1 of the GLOBAL batch: every rank adds the rows it holds
-                                    head = np.zeros((nlen,) + frames.shape[1:], np.float64)
-                                    lo, hi = max(j0, 0), min(j0 + Bl, nlen)
-                                    if hi > lo:
-                                        head[lo:hi] = frames[lo - j0:hi - j0]
-                                    # (the group sums in float64; the quantisation below is the single-GPU path's and the reference's float32 arithmetic)
-                                    frames = allsum(head.ravel()).reshape(head.shape).astype(np.float32)
-                                u = (np.clip((frames[:nlen] + 1.0) / 2.0, 0, 1) * 255).astype(np.uint8)     # savegif's frames (:23-26)
-                                if rank == 0:
-                                    save_clip("%s%d/__%d%s" % (basedir, itr, kk, tag), u)
+                        with core.ema_weights() if on_ema else contextlib.nullcontext():
+                            for kk in range(10):
+                                choicesrc = [np.random.randint(nvalid)] * B
+                                choicetgt = [np.random.randint(nvalid)] * B
+                                clip, _ = evaluate(choicesrc, choicetgt)
+                                r1, r2 = clip["recon1"], clip["recon2"]           # the reference's clip fetch overwrites r1 / r2 (:192-193): the
+                                                                                  # tabular R1 / R2 of a save iteration are the last clip's
+                                for tag, frames in (("trans", clip["out"]), ("recon", clip["out2"])):
+                                    if dp:                         # the clip is rows 0 .. nlen-1 of the GLOBAL batch: every rank adds the rows it holds
+                                        head = np.zeros((nlen,) + frames.shape[1:], np.float64)
+                                        lo, hi = max(j0, 0), min(j0 + Bl, nlen)
+                                        if hi > lo:
+                                            head[lo:hi] = frames[lo - j0:hi - j0]
+                                        # (the group sums in float64; the quantisation below is the single-GPU path's and the reference's float32 arithmetic)
+                                        frames = allsum(head.ravel()).reshape(head.shape).astype(np.float32)
+                                    u = (np.clip((frames[:nlen] + 1.0) / 2.0, 0, 1) * 255).astype(np.uint8)     # savegif's frames (:23-26)
+                                    if rank == 0:
+                                        save_clip("%s%d/__%d%s" % (basedir, itr, kk, tag), u)
                 if itr >= self.save_every and rank == 0:
                     rows.append(dict(Iteration=itr, Loss=loss, Sim=sim, R1=r1, R2=r2, NNErr=err))
                     with open(basedir + "progress.csv", "w", newline="") as f:

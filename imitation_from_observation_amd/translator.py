@@ -8,6 +8,7 @@ happens in the HIP kernels; this file only moves numpy buffers across the C ABI.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from collections import OrderedDict
@@ -149,6 +150,7 @@ class Translator:
             raise CtxError(rc, msg.decode() if msg else "")
         self.n_params = int(self._lib.ctx_param_total(self._h))
         self._pool = _ResultPool()
+        self._ema_warmup = False
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
@@ -280,12 +282,27 @@ class Translator:
         path = os.fspath(path)
         return path if path.endswith(".npz") else path + ".npz"
 
-    def save(self, path, with_adam=True, prefix=""):
-        """Checkpoint keyed by the TF variable names (the Saver's, train_script.py:181).  Returns the file written."""
-        tree = {prefix + k: v for k, v in self.get_params().items()}
-        if with_adam:
-            m, v, step = self.get_adam_state()
-            tree["__adam_m__"], tree["__adam_v__"], tree["__adam_step__"] = m, v, np.int64(step)
+    def save(self, path, with_adam=True, prefix="", weights="params"):
+        """Checkpoint keyed by the TF variable names (the Saver's, train_script.py:181).  Returns the file written.
+        With an averaged copy (set_ema) the file also carries __ema__, __ema_updates__, __ema_decay__ and __ema_warmup__, which load()
+        restores into a handle that has one and which older readers skip.  weights="ema" writes the AVERAGED weights under the variable
+        names and nothing else (no Adam state, no __*__ keys): the inference checkpoint a reward hook reads with the plain load().
+        ValueError while the averaged weights are swapped in (ema_swap)."""
+        if weights not in ("params", "ema"):
+            raise ValueError('weights must be "params" or "ema"')
+        st = self.ema_state()
+        if st["swapped"]:
+            raise ValueError("save while the averaged weights are swapped in: ema_swap() back first")
+        if weights == "ema":
+            tree = {prefix + k: v for k, v in self.get_ema().items()}
+        else:
+            tree = {prefix + k: v for k, v in self.get_params().items()}
+            if with_adam:
+                m, v, step = self.get_adam_state()
+                tree["__adam_m__"], tree["__adam_v__"], tree["__adam_step__"] = m, v, np.int64(step)
+            if st["enabled"]:
+                tree["__ema__"], tree["__ema_updates__"] = self.get_ema_flat(), np.int64(self.ema_state()["updates"])
+                tree["__ema_decay__"], tree["__ema_warmup__"] = np.float32(st["decay"]), np.int64(bool(self._ema_warmup))
         fn = self.checkpoint_file(path)
         with open(fn, "wb") as f:                           # an open handle: numpy does not rename it
             np.savez(f, **tree)
@@ -304,6 +321,8 @@ class Translator:
             self.set_params({k: z[k] for k in keys if not k.startswith("__")}, prefix=prefix)
             if "__adam_m__" in keys:
                 self.set_adam_state(z["__adam_m__"], z["__adam_v__"], int(z["__adam_step__"]))
+            if "__ema__" in keys and self.ema_state()["enabled"]:      # (after the parameters: set_params resets the average)
+                self.set_ema_flat(z["__ema__"], int(z["__ema_updates__"]))
 
     # ------------------------------------------------------------------ inference (reward hook)
     def translate(self, obs_src, obs_tgt0):
@@ -728,6 +747,63 @@ class Translator:
         """The same on N GPUs (ctx_dp_accum_train_step_sampled; collective): every rank passes the SAME global index arrays and steps
         its rows [rank B/world, ...) in micro-batches, ONE all-reduce per step.  Scalars and nn_err are global."""
         return self._sampled_accum(self._lib.ctx_dp_accum_train_step_sampled, choicesrc, choicetgt, micro_batch, lr, nlen)
+
+    # ------------------------------------------------------------------ averaged parameters (include/ctxtrans.h: ctx_ema_*)
+    def set_ema(self, decay, warmup=True):
+        """Keep an exponential moving average of the parameters on the device (tf.train.ExponentialMovingAverage): one extra launch
+        behind every later Adam update of this handle, shadow = fma(1 - d_t, param - shadow, shadow) with d_t = decay, or with
+        `warmup` min(decay, (1 + t) / (10 + t)) for update t = 0, 1, ...  The first call starts the average at the current parameters;
+        a later call changes decay / warmup only.  set_params / init_params / dp_init start it again; a step the guard skips leaves it
+        untouched, a frozen tensor's average keeps every bit.  decay outside [0, 1]: CtxError (CTX_E_INVALID)."""
+        self._ck(self._lib.ctx_ema_enable(self._h, float(decay), int(bool(warmup))))
+        self._ema_warmup = bool(warmup)
+
+    def ema_off(self):
+        """Drop the averaged copy: the handle then behaves as if set_ema had never been called."""
+        self._ck(self._lib.ctx_ema_disable(self._h))
+
+    def ema_reset(self):
+        """Average = current parameters, update count = 0."""
+        self._ck(self._lib.ctx_ema_reset(self._h))
+
+    def ema_update(self):
+        """One update from the parameters as they are now -- for an optimiser outside the library (TranslatorModule with a torch
+        optimiser, dp.HipEngine): call it after params_written().  Honours the mask, ignores the guard.  Asynchronous."""
+        self._ck(self._lib.ctx_ema_update(self._h))
+
+    def ema_swap(self):
+        """Exchange parameters and average on the device; a second call restores every bit.  While swapped, translate / encode /
+        reward_costs / evaluate run on the averaged weights and everything that writes parameters or the average raises CtxError
+        (CTX_E_STATE).  See ema_weights()."""
+        self._ck(self._lib.ctx_ema_swap(self._h))
+
+    def ema_state(self):
+        """dict(enabled, swapped, decay, updates); works without an averaged copy (enabled False)."""
+        en, sw, d, n = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_float(0), ctypes.c_int64(0)
+        self._ck(self._lib.ctx_ema_state(self._h, ctypes.byref(en), ctypes.byref(sw), ctypes.byref(d), ctypes.byref(n)))
+        return dict(enabled=bool(en.value), swapped=bool(sw.value), decay=float(d.value), updates=int(n.value))
+
+    def get_ema_flat(self):
+        flat = np.empty(self.n_params, np.float32)
+        self._ck(self._lib.ctx_get_ema(self._h, _fp(flat), flat.size, None))
+        return flat
+
+    def get_ema(self):
+        """The averaged weights as {tf_variable_name: array}, like get_params()."""
+        return self._split(self.get_ema_flat())
+
+    def set_ema_flat(self, flat, updates=0):
+        flat = _f32(flat, (self.n_params,))
+        self._ck(self._lib.ctx_set_ema(self._h, _fp(flat), flat.size, int(updates)))
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """with tr.ema_weights(): ...  -- the body runs on the averaged weights (ema_swap in, ema_swap back, also on an exception)."""
+        self.ema_swap()
+        try:
+            yield self
+        finally:
+            self.ema_swap()
 
     # ------------------------------------------------------------------ guarded Adam (include/ctxtrans.h: ctx_set_grad_guard)
     def set_grad_guard(self, clip_norm=None, skip_nonfinite=True):

@@ -51,7 +51,8 @@ extern "C" {
                                ctx_reward_get_cache, ctx_reward_stats, option reward_split; ctx_resize_*; the device-uint8 forms
                                ctx_resize_u8_dev / _v, ctx_cnn_*_dev_u8, ctx_disc_stream / _data_begin / _reward_paths_dev;
                                ctx_reconstruct / _f32 / _dev, ctx_reward_costs_recon / _dev;
-                               ctx_set_grad_guard, ctx_grad_norm, ctx_grad_guard_stats; ctx_accum_* / ctx_dp_accum_* */
+                               ctx_set_grad_guard, ctx_grad_norm, ctx_grad_guard_stats; ctx_accum_* / ctx_dp_accum_*;
+                               ctx_ema_*, ctx_get_ema, ctx_set_ema */
 
 enum {
     CTX_OK = 0,
@@ -615,6 +616,49 @@ int ctx_accum_train_step_sampled(ctx_handle* h, const int32_t* choicesrc, const 
                                  float scalars[4], int nlen, int64_t* nn_err);
 int ctx_dp_accum_train_step_sampled(ctx_handle* h, const int32_t* choicesrc, const int32_t* choicetgt, int B_total, int micro_B,
                                     float lr, float scalars[4], int nlen, int64_t* nn_err);
+
+/* ---- exponential moving average of the parameters, kept on the device (new here; tf.train.ExponentialMovingAverage) ---------------
+ * An averaged copy ("shadow") of the parameters beside the arena, updated by ONE launch behind every Adam update of the handle --
+ * ctx_train_step*, ctx_dev_train_step, ctx_dev_adam, ctx_dp_train_step*, ctx_accum_adam / ctx_dp_accum_adam and the accumulated
+ * sampled steps (once per Adam update, not per micro-batch).  Off by default: a handle that never enables it runs exactly the
+ * launches of one that has never heard of it.
+ *   ctx_ema_enable(h, decay, warmup)   decay in [0, 1], else (NaN included) CTX_E_INVALID.  The first call allocates the shadow -- one
+ *                                      buffer of the parameters' size, the library's own also beside a caller-supplied arena
+ *                                      (ctx_arena_bytes is unchanged) -- and sets it to the parameters; a later call changes only
+ *                                      decay and warmup.
+ *   ctx_ema_disable(h)                 frees the shadow; the handle then behaves as if it had never been enabled.
+ *   ctx_ema_reset(h)                   shadow = parameters, update count = 0.
+ *   ctx_ema_update(h)                  one update from the parameters as they are now, for callers whose optimiser lives outside the
+ *                                      library (they write through ctx_dev_params and call ctx_params_written): honours the mask,
+ *                                      ignores the guard.  Asynchronous.
+ *   ctx_ema_swap(h)                    exchanges parameters and shadow on the device (two swaps restore every bit), so that every
+ *                                      inference entry runs on the averaged weights; packed filters and captured graphs follow as
+ *                                      after any parameter change.  CTX_E_STATE while an accumulation is open.  Asynchronous.
+ *   ctx_ema_state(h, &enabled, &swapped, &decay, &updates)   every out-pointer nullable; works on a handle without a shadow.
+ *   ctx_get_ema(h, out, n, &updates) / ctx_set_ema(h, in, n, updates)   the shadow in the flat order and length of ctx_get_params /
+ *                                      ctx_set_params, and the update count (nullable on get; < 0 on set: CTX_E_INVALID).
+ * The update: e = fmaf(c, p - e, e) per element with c = (float)(1 - d_t), d_t formed in double: update number t, counted from 0,
+ * runs at d_t = decay, or with warmup != 0 at min(decay, (1 + t) / (10 + t)).  e == p stays e exactly and decay = 1 leaves e exactly.
+ * The count moves on the host with every update ISSUED -- also for a step the guard then skips on the device, as the Adam step
+ * count does.
+ *   - guard (ctx_set_grad_guard): a step skipped for a non-finite gradient leaves the shadow untouched as well (the count moves).
+ *   - mask (ctx_set_param_lr_scale): the update runs over the trainable tensors only; a frozen tensor's shadow keeps every bit.
+ *   - reset rule: the shadow is set to the new parameters and the count to 0 when ALL parameters are replaced from outside a step:
+ *     ctx_set_params, ctx_init_params and the broadcast of ctx_dp_init.  ctx_params_written does NOT reset.
+ *   - while swapped, every entry that writes parameters or shadow returns CTX_E_STATE: the training steps, ctx_dev_adam, ctx_accum_begin
+ *     and with it every accumulation entry, ctx_profile_step, ctx_set_params, ctx_init_params, ctx_dp_init and the entries of this
+ *     section other than ctx_ema_swap and ctx_ema_state.  Inference, ctx_eval*, ctx_get_params (which then returns the averaged
+ *     weights) and the VJP calls stay allowed.
+ * Every entry but ctx_ema_enable and ctx_ema_state returns CTX_E_STATE on a handle without a shadow; a NULL handle is CTX_E_INVALID
+ * and nothing is written through the out-pointers. */
+int ctx_ema_enable(ctx_handle* h, float decay, int warmup);
+int ctx_ema_disable(ctx_handle* h);
+int ctx_ema_reset(ctx_handle* h);
+int ctx_ema_update(ctx_handle* h);
+int ctx_ema_swap(ctx_handle* h);
+int ctx_ema_state(ctx_handle* h, int* enabled, int* swapped, float* decay, int64_t* updates);
+int ctx_get_ema(ctx_handle* h, float* out, int64_t n, int64_t* updates);
+int ctx_set_ema(ctx_handle* h, const float* in, int64_t n, int64_t updates);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* One entry per launch group of a train step (a layer's forward, input gradient, filter gradient,
