@@ -204,7 +204,7 @@ int run(ctx_cnn* h, int n, std::vector<hipEvent_t>* ev = nullptr) {
                        cin <= 32 && op.cout <= 32) {
                 // Conv2d_2a_3x3 (32 -> 32): a 32-column GEMM wastes the implicit GEMM's tiles (57 TF/s); the direct convolution over an LDS
                 // halo tile with the filter resident (dconv.h) runs it at 81 (0.223 -> 0.157 ms at 192 images of 125x125).  Wider layers lose:
-                // 32 -> 64 0.271 -> 0.399 ms, 64 -> 80 1x1 0.076 -> 0.125, 64 -> 96 0.048 -> 0.092 (option value 2 runs them all)
+                // 32 -> 64 0.271 -> 0.399 ms, 64 -> 80 1x1 0.076 -> 0.125, 64 -> 96 0.048 -> 0.092 (option cnn_dconv is on / off: 0 keeps every conv on the GEMM)
                 DcFwd D{};
                 D.x1 = x; D.ld1 = in.c; D.c1 = cin; D.CI = cin; D.hin = in.h; D.win = in.w; D.nimg = n;
                 D.w = w; D.wmode = 0; D.N = op.cout; D.ep = ep; D.wp = h->wpack[L];
@@ -383,6 +383,9 @@ int ctx_cnn_create(const ctx_cnn_buf* bufs, int nbufs, const ctx_cnn_op* ops, in
     h->overlap = h->opt.v[OPT_CNN_LANES] < 0 ? precision != CTX_PREC_F32 : h->opt.v[OPT_CNN_LANES] != 0;
     h->use_graphs = h->opt.v[OPT_GRAPHS] != 0;
     alloc((void**)&h->zeros, 256, true);
+    // hipMemset runs on the null stream, which the handle's non-blocking streams do not wait for: without this a first pass right behind
+    // create could have its weights or outputs zeroed under it (seen as all-zero activations on small graphs)
+    if (ok) ok = hipDeviceSynchronize() == hipSuccess;
     if (!ok) { cfail(nullptr, CTX_E_NOMEM, "device allocation failed"); ctx_cnn_destroy(h); return CTX_E_NOMEM; }
     *out = h;
     return CTX_OK;
@@ -603,6 +606,7 @@ int ctx_cnn_stats_reset(ctx_cnn* h, const int32_t* buffers, const int32_t* chann
             ok = ok && hipMalloc((void**)p, (size_t)sl.n * sizeof(float)) == hipSuccess && hipMemset(*p, 0, (size_t)sl.n * sizeof(float)) == hipSuccess;
         h->stats.push_back(sl);
     }
+    if (ok) ok = hipDeviceSynchronize() == hipSuccess;      // the null-stream memsets above, before the handle's stream accumulates
     if (!ok) { free_stats(h); return cfail(h, CTX_E_NOMEM, "stats_reset: device allocation failed"); }
     h->stats_frames = nframes;
     h->stats_stage = 0;

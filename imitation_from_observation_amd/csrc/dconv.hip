@@ -6,6 +6,7 @@
 #include "dconv2.h"
 #include "launch.h"
 #include "options.h"
+#include "trace.h"
 
 namespace ctx {
 
@@ -252,6 +253,8 @@ static bool dconv_launch2(hipStream_t s, DcFwd P, int span) {
 
 static void dconv_launch(hipStream_t s, DcFwd P, int span) {
     g_dc2_last[0] = 0;
+    trace_launch("dconv | CI %d N %d S %d span %d ncls %d taps %d hin %d win %d hlog %d wlog %d nimg %d fmt %d", P.CI, P.N, P.S, span, P.ncls, P.cls[0].ntaps, P.hin, P.win,
+                 P.hlog, P.wlog, P.nimg, P.fmt);
     const int CIK = cik_of(P.CI), CIP = dc_cip(CIK, P.S);
     // The split form: 8 .. 32 input channels.  A 3-channel input (scalar LDS writes) and the 64-channel instantiations run the exact-f32
     // kernel in every mode (include/ctxtrans.h: inside every mode's contract); the LDS-DMA kernel of dconv2.h cannot convert on landing.

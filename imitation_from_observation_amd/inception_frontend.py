@@ -259,6 +259,37 @@ class _Layout:
         return out
 
 
+def fold_variables(convs, weight_floats, tree):
+    """The host half of InceptionFrontend.set_variables, no handle needed: {tf_variable_name: array} -> the f32 weight blob of a
+    layout's `convs` (_Layout.convs / .woff), the batch norm (inference form) folded into filter and bias."""
+    blob = np.zeros(weight_floats, np.float32)
+    for c in convs:
+        w = np.asarray(tree[c["scope"] + "/weights"], np.float64)
+        if c.get("linear"):
+            b = np.asarray(tree[c["scope"] + "/biases"], np.float64)
+            if w.shape != c["k"] + (c["cin"], c["cout"]) or b.shape != (c["cout"],):
+                raise ValueError(f"{c['scope']}: expected weights {c['k'] + (c['cin'], c['cout'])} and biases {(c['cout'],)}, got {w.shape}, {b.shape}")
+            wp = np.zeros((c["cin_pad"], c["cout_pad"]))
+            wp[:c["cin"], :c["cout"]] = w[0, 0]
+            blob[c["w_off"]:c["w_off"] + wp.size] = wp.reshape(-1)
+            blob[c["b_off"]:c["b_off"] + c["cout"]] = b
+            continue
+        beta, mean, var = (np.asarray(tree[c["scope"] + "/BatchNorm/" + n], np.float64) for n in ("beta", "moving_mean", "moving_variance"))
+        if w.shape != c["k"] + (c["cin"], c["cout"]):
+            raise ValueError(f"{c['scope']}/weights: expected {c['k'] + (c['cin'], c['cout'])}, got {w.shape}")
+        scale = 1.0 / np.sqrt(var + BN_EPS)
+        if "ld" in c:                                     # a 1x1 head inside a merged filter [cin_pad][ld]: columns col0 .. col0 + cout
+            m = blob[c["w_off"]:c["w_off"] + c["cin_pad"] * c["ld"]].reshape(c["cin_pad"], c["ld"])
+            m[:c["cin"], c["col0"]:c["col0"] + c["cout"]] = (w * scale)[0, 0]
+            blob[c["b_off"] + c["col0"]:c["b_off"] + c["col0"] + c["cout"]] = beta - mean * scale
+            continue
+        wp = np.zeros(c["k"] + (c["cin_pad"], c["cout"]))
+        wp[:, :, :c["cin"], :] = w * scale
+        blob[c["w_off"]:c["w_off"] + wp.size] = wp.reshape(-1)
+        blob[c["b_off"]:c["b_off"] + c["cout"]] = beta - mean * scale
+    return blob
+
+
 class InceptionFrontend:
     """frames -> Mixed_7c feature maps on one MI355X.  `max_images` bounds one device pass (larger batches are chunked).
     final: the last end point computed (ENDPOINTS; 'PreLogits' / 'Logits' append the classifier head)."""
@@ -339,31 +370,7 @@ class InceptionFrontend:
     def set_variables(self, tree):
         """tree: {tf_variable_name: array}.  Folds the batch norm (inference form) into filter and bias and uploads.  Keys of parts
         not built (AuxLogits/*, and Logits/* below `final` = 'Logits') are ignored."""
-        blob = np.zeros(self.weight_floats, np.float32)
-        for c in self.convs:
-            w = np.asarray(tree[c["scope"] + "/weights"], np.float64)
-            if c.get("linear"):
-                b = np.asarray(tree[c["scope"] + "/biases"], np.float64)
-                if w.shape != c["k"] + (c["cin"], c["cout"]) or b.shape != (c["cout"],):
-                    raise ValueError(f"{c['scope']}: expected weights {c['k'] + (c['cin'], c['cout'])} and biases {(c['cout'],)}, got {w.shape}, {b.shape}")
-                wp = np.zeros((c["cin_pad"], c["cout_pad"]))
-                wp[:c["cin"], :c["cout"]] = w[0, 0]
-                blob[c["w_off"]:c["w_off"] + wp.size] = wp.reshape(-1)
-                blob[c["b_off"]:c["b_off"] + c["cout"]] = b
-                continue
-            beta, mean, var = (np.asarray(tree[c["scope"] + "/BatchNorm/" + n], np.float64) for n in ("beta", "moving_mean", "moving_variance"))
-            if w.shape != c["k"] + (c["cin"], c["cout"]):
-                raise ValueError(f"{c['scope']}/weights: expected {c['k'] + (c['cin'], c['cout'])}, got {w.shape}")
-            scale = 1.0 / np.sqrt(var + BN_EPS)
-            if "ld" in c:                                     # a 1x1 head inside a merged filter [cin_pad][ld]: columns col0 .. col0 + cout
-                m = blob[c["w_off"]:c["w_off"] + c["cin_pad"] * c["ld"]].reshape(c["cin_pad"], c["ld"])
-                m[:c["cin"], c["col0"]:c["col0"] + c["cout"]] = (w * scale)[0, 0]
-                blob[c["b_off"] + c["col0"]:c["b_off"] + c["col0"] + c["cout"]] = beta - mean * scale
-                continue
-            wp = np.zeros(c["k"] + (c["cin_pad"], c["cout"]))
-            wp[:, :, :c["cin"], :] = w * scale
-            blob[c["w_off"]:c["w_off"] + wp.size] = wp.reshape(-1)
-            blob[c["b_off"]:c["b_off"] + c["cout"]] = beta - mean * scale
+        blob = fold_variables(self.convs, self.weight_floats, tree)
         self._ck(self._lib.ctx_cnn_set_weights(self._h, blob.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), blob.size))
 
     def load(self, path):
