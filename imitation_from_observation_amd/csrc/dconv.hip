@@ -248,13 +248,17 @@ static bool dconv_launch2(hipStream_t s, DcFwd P, int span) {
     else ok = NBT == 1 ? (P.ncls == 1 ? DC2_GO(2, false, 1) : DC2_GO(2, false, 4)) : (P.ncls == 1 ? DC2_GO(2, true, 1) : DC2_GO(2, true, 4));
 #undef DC2_GO
     if (ok) { g_dc2_last[0] = P.TH; g_dc2_last[1] = P.TW; g_dc2_last[2] = best_mi; g_dc2_last[3] = NBT * 10 + best_occ; g_dc2_last[4] = NSL; }
+    // option trace_launch: the launch as dconv_launch states it, then what was chosen (NSL: K slices of 16 channels, NB2: column blocks of 16)
+    if (ok)
+        trace_launch("dconv | CI %d N %d S %d span %d ncls %d taps %d hin %d win %d hlog %d wlog %d nimg %d fmt %d kernel fwd2 TH %d TW %d MI %d NSL %d NB2 %d occ %d "
+                     "slices 1 tiles_y %d tiles_x %d ntiles %d grid %u", P.CI, P.N, P.S, span, P.ncls, P.cls[0].ntaps, P.hin, P.win, P.hlog, P.wlog, P.nimg, P.fmt,
+                     P.TH, P.TW, best_mi, NSL, NBT, best_occ, P.tiles_y, P.tiles_x, ntiles, grid.x);
     return ok;
 }
 
 static void dconv_launch(hipStream_t s, DcFwd P, int span) {
     g_dc2_last[0] = 0;
-    trace_launch("dconv | CI %d N %d S %d span %d ncls %d taps %d hin %d win %d hlog %d wlog %d nimg %d fmt %d", P.CI, P.N, P.S, span, P.ncls, P.cls[0].ntaps, P.hin, P.win,
-                 P.hlog, P.wlog, P.nimg, P.fmt);
+    const int fmt_asked = P.fmt;                              // (option trace_launch prints the mode the caller asked for, below, with the tile choice)
     const int CIK = cik_of(P.CI), CIP = dc_cip(CIK, P.S);
     // The split form: 8 .. 32 input channels.  A 3-channel input (scalar LDS writes) and the 64-channel instantiations run the exact-f32
     // kernel in every mode (include/ctxtrans.h: inside every mode's contract); the LDS-DMA kernel of dconv2.h cannot convert on landing.
@@ -344,6 +348,10 @@ static void dconv_launch(hipStream_t s, DcFwd P, int span) {
     const int slots = NUM_CU * best_occ;
     const int rounds = (ntiles + slots - 1) / slots;
     const dim3 grid((unsigned)((ntiles + rounds - 1) / rounds));
+    // option trace_launch: the launch as stated, then what was chosen (NB: column blocks of 16 per launch; slices: launches over column slices)
+    trace_launch("dconv | CI %d N %d S %d span %d ncls %d taps %d hin %d win %d hlog %d wlog %d nimg %d fmt %d kernel fwd TH %d TW %d MI %d NB %d occ %d "
+                 "slices %d tiles_y %d tiles_x %d ntiles %d grid %u", P.CI, P.N, P.S, span, P.ncls, P.cls[0].ntaps, P.hin, P.win, P.hlog, P.wlog, P.nimg, fmt_asked,
+                 P.TH, P.TW, MI, NB, best_occ, (P.N + NB * 16 - 1) / (NB * 16), P.tiles_y, P.tiles_x, ntiles, grid.x);
     if (!pack_cached(P, CIK, nslots, s)) launch_pack(s, P, CIK, nslots);
     for (int n0 = 0; n0 < P.N; n0 += NB * 16) {
         P.n0 = n0;
@@ -520,6 +528,8 @@ void dconv_wgrad(hipStream_t s, DcWgrad P, float* slab, int64_t slab_floats) {
     P.slab = slab;
     P.dbslab = slab + nblk * (int64_t)P.M * NP;
     const dim3 grid((unsigned)nblk);
+    trace_launch("dconv_wgrad | CA %d CB %d CAK %d NB %d S %d TH %d TW %d two %d nmod2 %d hs %d ws %d tiles_y %d tiles_x %d ntiles %d nblk %d slices %d nimg %d", P.CA, P.CB, CAK,
+                 NB, P.S, P.TH, P.TW, P.s2 ? 1 : 0, P.nmod2, P.hs, P.ws, P.tiles_y, P.tiles_x, P.ntiles, (int)nblk, (P.CB + NP - 1) / NP, P.nimg);
     for (int n0 = 0; n0 < P.CB; n0 += NP) {
         P.n0 = n0;
 #define DC_WG(ss)                                                            \

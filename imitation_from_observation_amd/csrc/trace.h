@@ -1,5 +1,5 @@
 // trace.h -- option "trace_launch" for the launchers outside gemm_launch.h (wconvt.hip, convt3.hip, convt3m.hip, c3conv.hip,
-// c3wgrad.hip, convt_product): one stderr line per distinct launch, in the style of the implicit GEMM's, `family | key value ...`.
+// c3wgrad.hip, dconv.hip, convt_product): one stderr line per distinct launch, in the style of the implicit GEMM's, `family | key value ...`.
 // Host code only.
 #pragma once
 #include <cstdarg>

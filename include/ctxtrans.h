@@ -205,7 +205,10 @@ const char* ctx_last_error(const ctx_handle* h);
  *                      convt3         form valu (S P NT TW ... ntiles grid nimg) or mfma (S KQH ... grid rounds nimg): d_h4's forward
  *                      c3conv         S NB TWB hin win ntiles grid nimg;   c3wgrad  S NB TWB two nmod2 hs ws ntiles nbl ngroups nimg
  *                      convt_product  M N cb ca (the starved inference route; its product is an igemm line as well)
- *                    One set of seen lines per process; the other launchers (dconv.h, rchain.hip, elementwise) print nothing.
+ *                      dconv          CI N S span ncls taps hin win hlog wlog nimg fmt, then the tile choice: kernel fwd (TH TW MI NB occ slices) or
+ *                                     fwd2 (TH TW MI NSL NB2 occ slices), tiles_y tiles_x ntiles grid   (dconv.hip: dconv_launch / dconv_launch2)
+ *                      dconv_wgrad    CA CB CAK NB S TH TW two nmod2 hs ws tiles_y tiles_x ntiles nblk slices nimg
+ *                    One set of seen lines per process; the other launchers (rchain.hip, elementwise) print nothing.
  *   adam_prio    2   HIP priority of the early-Adam stream (1 low: its own hardware queue; 0 normal; -1 high; 2 = low for exact-f32 handles,
  *                    normal for split-bf16 ones, reads back resolved)  [fixed at create]
  *   reward_split -1  the reward hook's image term (ctx_reward_costs / ctx_reward_costs_dev): -1 = the split kernel for frames of >= 32768

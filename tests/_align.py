@@ -96,12 +96,18 @@ def restore_cache(undo):
         flat[idx] = vals
 
 
-def align_gen_cache(tr, c, B):
+def align_gen_cache(tr, c, B, undo=None):
     """The same for the table-driven models (ContextAEInception2 / ContextAEReal without channel padding): device buffers a0..a3 hold
     the conv outputs of the stacked [tgt | src | ctx] images, a4 = h4, Z = [trans_z | tgt_z | src_z | ctx_z], dz / e1..e3 both decoder
     passes (ctx_debug_read's names for these variants).  c: cache of oracle/ctx_oracle_incep.forward (or ctx_oracle_real.forward).
-    The code-wide buffers (a4, th0, Z) are kept at a row stride of featsize rounded up to 32 (ContextAEReal: 100 -> 128)."""
-    return _align_cache(tr, c, "gen", B)
+    The code-wide buffers (a4, th0, Z) are kept at a row stride of featsize rounded up to 32 (ContextAEReal: 100 -> 128).
+    undo: as in align_skipnew_cache."""
+    return _align_cache(tr, c, "gen", B, undo)
+
+
+def examined(c, model, B):
+    """Number of activations _align_cache compares for this cache: the denominator of a cap stated per million."""
+    return sum(int(_cached(c, site).size) for parts in site_map(model, B).values() for site, _, _ in parts)
 
 
 def device_branches(tr, model, B, x, chan=None):

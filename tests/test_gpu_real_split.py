@@ -128,8 +128,9 @@ def f32_errors(T, H, W, B):
 
 # ---------------------------------------------------------------------------------------------- 1. parity
 # (36, 64, 3): the reference size, odd B; (20, 128, 2): two 64-column tiles per row; (40, 64, 2): ragged last row tile;
-# (4, 64, 1): the smallest grid the narrow path accepts, 1 x 16 after two stride-2 layers
-@pytest.mark.parametrize("H,W,B", [(36, 64, 3), (20, 128, 2), (40, 64, 2), (4, 64, 1)])
+# (4, 64, 1): the smallest grid the narrow path accepts, 1 x 16 after two stride-2 layers; (4, 192, 2): tile edges in x inside the 96- and
+# 48-wide grids; (4, 64, 87): 261 / 174 / 87 images per launch (tests/test_gpu_real_routes.py traces what both launch in fp16x3)
+@pytest.mark.parametrize("H,W,B", [(36, 64, 3), (20, 128, 2), (40, 64, 2), (4, 64, 1), (4, 192, 2), (4, 64, 87)])
 @pytest.mark.parametrize("prec", MODES)
 def test_real_split_parity(T, split_on, prec, H, W, B):
     ref = reference(H, W, B)
