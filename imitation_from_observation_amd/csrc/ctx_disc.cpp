@@ -1,7 +1,7 @@
 // ctx_disc.cpp -- the ctx_disc handle of include/ctxtrans.h: the third-person-imitation (TPIL) and GAIL baseline discriminators,
 // trained inside the RL loop (sandbox/bradly/third_person: discriminators/discriminator.py, algos/cyberpunk_trainer.py,
 // algos/cyberpunk_trainer_gail.py).  Launch sequences over the kernels of disc.hip on one stream; the arena is
-// [params | grads | m | v] like the translator's, updated by the same TF-Adam kernel (kernels.hip: adam).
+// [params | grads | m | v] like the translator's, updated by the same TF-Adam kernel (optim.hip: adam).
 //
 // A TPIL step (rows: B pairs = 2B images [x1 | x2]):
 //   conv1+relu+pool, conv2+relu+pool, feats FC (2B rows) | class MLP on [f1 | f2], domain MLP on f1 | both heads, CE, dlogits
@@ -233,7 +233,7 @@ void adam_step(ctx_disc* h, float lr) {
     const double b1 = (double)0.9f, b2 = (double)0.999f;
     h->adam_t += 1;
     const float lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow(b2, (double)h->adam_t)) / (1.0 - std::pow(b1, (double)h->adam_t)));
-    adam(h->stream, h->arena, h->arena + h->Ppad, h->arena + 2 * h->Ppad, h->arena + 3 * h->Ppad, h->Ppad, lr_t, 0.9f, 0.999f, 1e-8f);
+    adam(h->stream, h->arena, h->arena + h->Ppad, h->arena + 2 * h->Ppad, h->arena + 3 * h->Ppad, Span{nullptr, h->Ppad, lr_t}, 0.9f, 0.999f, 1e-8f, nullptr);
 }
 
 // one training step on the batch in the input buffers; the loss (before the update) goes to *loss on the device

@@ -320,10 +320,14 @@ struct Side {
 // slices run beside the dx chain but in turn with the filter gradients.  With GPU_MAX_HW_QUEUES=8 it has its own queue and the step
 // loses another 0.05 ms, but ContextAEReal's small launches then run truly side by side and get slower (2.71 -> 3.11 ms), so the
 // library does not ask for it (profiles/archive/round4_e_early_adam_queues.txt).  ON by default (option "early_adam"; read at every step).
+// What an optimizer pass of this handle covers (launch.h: Span): the trainable runs of its mask, or the dense floats [0, n) of the
+// pointers the pass gets.  Under a mask n is the end of the last tensor, as the guard's sum wants it.
+static int64_t grad_end(const ctx_handle* h) { return h->gen ? h->gen->pend : h->P; }       // the gradient arena a backward writes: [0, here)
+static Span span_of(const ctx_handle* h, int64_t n) { return masked(h) ? Span{&h->segs, grad_end(h), 0.f} : Span{nullptr, n, h->adam_lr_t}; }
+// [first, end): a dense range over offset pointers; a masked handle's one launch (first == 0, adam_end) covers its runs instead
 void adam_launch(ctx_handle* h, hipStream_t s, int64_t first, int64_t end) {
     float *p = h->arena + first, *g = p + h->Ppad, *m = g + h->Ppad, *v = m + h->Ppad;
-    if (guard_on(h)) adam_guarded(s, p, g, m, v, end - first, h->adam_lr_t, 0.9f, 0.999f, 1e-8f, h->guard_ctl);   // (ctx_set_grad_guard, below)
-    else adam(s, p, g, m, v, end - first, h->adam_lr_t, 0.9f, 0.999f, 1e-8f);
+    adam(s, p, g, m, v, span_of(h, end - first), 0.9f, 0.999f, 1e-8f, guard_on(h) ? h->guard_ctl : nullptr);   // (ctx_set_grad_guard, below)
 }
 void adam_begin(ctx_handle* h, float lr) {
     const bool env_on = h->opt.v[OPT_EARLY_ADAM] != 0;
@@ -339,14 +343,14 @@ void adam_begin(ctx_handle* h, float lr) {
     // (only where the update is worth hiding: ContextAEReal's 1.2 M parameters are a 7 us update, and the slices' events and queue hops
     // among its 5-30 us launches cost 0.4 ms of a 2.6 ms step -- bench.py's secondary leg against forward_backward + adam on one box: 3.00 -> 2.58 ms, round 5)
     // (and never under a guard: the clip factor and the skip decision exist only after the last gradient is written; nor under a
-    // mask: its update is ONE segmented launch at the end of the step)
+    // mask: its update is ONE launch over the trainable runs at the end of the step)
     h->adam_early_on = env_on && h->adam_stream && use_lanes(h) && h->P >= (4ll << 20) && !guard_on(h) && !masked(h);
 }
 
 // ---- training a subset of the parameters (ctx_set_param_lr_scale) ------------------------------------------------------------------
 // Tensor i of ctx_param_info owns the arena floats [first, end) up to the next tensor's first (the last: up to the next 16-byte boundary):
 // ContextSkipNew's arena is dense and only its last tensor (deconv/d_h4/biases, 3 floats) is no multiple of 4; the table-driven layout
-// pads every tensor to one.  The segmented kernels work on whole 16-byte groups, so no group may belong to two tensors.
+// pads every tensor to one.  The run-table kernels work on whole 16-byte groups, so no group may belong to two tensors.
 int tensor_spans(ctx_handle* h) {
     const size_t n = h->params.size();
     // (plan_mask gives every tensor a run of its own at worst: the run table must hold them all)
@@ -354,14 +358,14 @@ int tensor_spans(ctx_handle* h) {
     h->span.resize(n);
     for (size_t i = 0; i < n; ++i) h->span[i].first = h->gen ? h->gen->segs[i].poff : h->params[i].offset;
     for (size_t i = 0; i < n; ++i) {
-        h->span[i].second = i + 1 < n ? h->span[i + 1].first : round_up(h->gen ? h->gen->pend : h->P, 4);
+        h->span[i].second = i + 1 < n ? h->span[i + 1].first : round_up(grad_end(h), 4);
         if (h->span[i].first % 4 || h->span[i].second <= h->span[i].first)
             return fail(h, CTX_E_INVALID, "parameter %s does not start on a 16-byte group of the arena", h->params[i].name.c_str());
     }
     return CTX_OK;
 }
 
-// From h->lr_scale: the trainable runs of the segmented kernels (adjacent tensors of equal scale are one run) and which launch groups
+// From h->lr_scale: the trainable runs of the optimizer passes (adjacent tensors of equal scale are one run) and which launch groups
 // a plain backward keeps (Prune, ctx_internal.h).
 void plan_mask(ctx_handle* h) {
     h->segs = AdamSegs{};
@@ -431,7 +435,7 @@ const Prune* pruning(const ctx_handle* h) {
 
 // ---- guarded Adam (ctx_set_grad_guard) ---------------------------------------------------------------
 // One more HBM pass beside Adam's seven: the sum of squares of the gradient arena in f64, then one block that turns it into {norm, clip
-// factor, apply} in device memory, which adam_guarded_kernel reads -- nothing returns to the host.  The sum covers exactly the floats
+// factor, apply} in device memory, which adam_kernel<., true> reads -- nothing returns to the host.  The sum covers exactly the floats
 // Adam updates that a backward writes: ContextSkipNew's arena is dense over [0, P); the table-driven engine's holds channel-padded
 // tensors whose pad gradients are exact zeros (ctxtrans_gen.inc) up to the end of its last tensor, and at most 3 floats between two
 // tensors that stay the zeros of ctx_create.  [that end, Ppad) belongs to no tensor and stays out.
@@ -456,8 +460,7 @@ int guard_alloc(ctx_handle* h) {
 void guard_enqueue(ctx_handle* h, int which, float clip, bool skip, bool count) {
     // under a mask the norm is the trainable tensors': a frozen tensor's gradient (which a pruned backward did not even write) neither
     // clips nor skips the step
-    if (masked(h)) grad_guard_segmented(h->stream, h->arena + h->Ppad, h->segs, h->gen ? h->gen->pend : h->P, h->guard_part, h->guard_ctl + which, clip, skip, count, GUARD_NT);
-    else grad_guard(h->stream, h->arena + h->Ppad, h->gen ? h->gen->pend : h->P, h->guard_part, h->guard_ctl + which, clip, skip, count, GUARD_NT);
+    grad_guard(h->stream, h->arena + h->Ppad, span_of(h, grad_end(h)), h->guard_part, h->guard_ctl + which, clip, skip, count, GUARD_NT);
 }
 // [first, end) is final in the order of the CURRENT stream plus (lane >= 0) of that side lane
 void adam_early(ctx_handle* h, int64_t first, int64_t end, int lane) {
@@ -477,12 +480,8 @@ void adam_end(ctx_handle* h) {
     ProfScope ps(h, "adam", "adam", 0.0);
     // under a guard no slice went early (adam_begin): the norm and the control block first, then one guarded launch over the whole arena
     if (guard_on(h)) guard_enqueue(h, 0, h->guard_clip, h->guard_skip, true);
-    // under a mask no slice went early either: one segmented launch over the trainable runs, each at its own lr_t (adam_begin)
-    if (masked(h)) {
-        float *p = h->arena, *g = p + h->Ppad, *m = g + h->Ppad, *v = m + h->Ppad;
-        adam_segmented(h->stream, p, g, m, v, h->segs, 0.9f, 0.999f, 1e-8f, guard_on(h) ? h->guard_ctl : nullptr);
-    }
-    for (size_t i = 0; !masked(h) && i <= h->adam_done.size(); ++i) {
+    // (under a mask no slice went early either: the loop is one launch [0, Ppad), which covers the trainable runs, each at its own lr_t)
+    for (size_t i = 0; i <= h->adam_done.size(); ++i) {
         const int64_t stop = i < h->adam_done.size() ? h->adam_done[i].first : h->Ppad;
         if (stop > at) adam_launch(h, h->stream, at, stop);
         if (i < h->adam_done.size()) at = h->adam_done[i].second;
@@ -503,7 +502,8 @@ void adam_end(ctx_handle* h) {
 // : decay, formed in double, and the kernel gets c = (float)(1 - d_t).  One launch per Adam update, the last of adam_end: over the
 // trainable runs under a mask (a frozen tensor's shadow keeps every bit), under the guard's control block when a guard is set (a
 // skipped step leaves the shadow alone).  ema_t counts on the host and moves on a skipped step too, as adam_t does.
-// NOT fused into the Adam kernels: the four of them are held against each other bit for bit by the tests, and fusion would save one
+// NOT fused into adam_kernel: its four instantiations (dense | runs, guarded or not) share one body and the tests hold them against
+// each other bit for bit, a fused pass would be a second body, and fusion would save one
 // read of p out of three arena passes -- at Adam's measured 5.8 TB/s an estimated (not measured) 0.03 ms of a 12.8 ms step.
 int ema_refuse(ctx_handle* h, const char* what) {
     return fail(h, CTX_E_STATE, "%s while the averaged weights are swapped in (ctx_ema_swap): the arena holds the average and the shadow the raw parameters; ctx_ema_swap again swaps them back",
@@ -514,8 +514,7 @@ void ema_enqueue(ctx_handle* h, bool guarded) {
     const double d_t = h->ema_warm ? std::min(d, (1.0 + t) / (10.0 + t)) : d;
     const float c = (float)(1.0 - d_t);
     const GuardCtl* ctl = guarded ? h->guard_ctl : nullptr;
-    if (masked(h)) ema_update_segmented(h->stream, h->ema, h->arena, h->segs, c, ctl);
-    else ema_update(h->stream, h->ema, h->arena, h->Ppad, c, ctl);
+    ema_update(h->stream, h->ema, h->arena, span_of(h, h->Ppad), c, ctl);
     h->ema_t += 1;
 }
 int ema_reset(ctx_handle* h) {
@@ -1284,11 +1283,11 @@ int fused_step(ctx_handle* h, int B, float lr) {
 // arithmetic in micro-batches on ONE handle: micro-batch j runs a plain backward(h, B_j, total) and its gradient is added into `accum`,
 // a Ppad-float buffer beside the arena -- SET for the first, ADD for the later ones, and the LAST is not added at all: accum_fold
 // writes  g = accum + g  into the gradient arena, which then holds ((g1 + g2) + ...) + gk, one f32 add per element and micro-batch, and
-// the EXISTING tail runs on it unchanged (guard_enqueue, adam_launch / adam_segmented, dp_reduce_range, ctx_get_grads, ctx_grad_norm).
+// the EXISTING tail runs on it unchanged (guard_enqueue, adam_launch, dp_reduce_range, ctx_get_grads, ctx_grad_norm).
 // The fold costs three arena passes per accumulated step (read accum, read g, write g: 0.57 GB for ContextSkipNew); an Adam reading two
 // gradient sources would save one and add a third instantiation of every Adam kernel.  An accumulation of ONE micro-batch launches
 // nothing beyond the plain forward_backward + adam: it is that step bit for bit.
-// Under an lr-scale mask every pass runs over the trainable runs only (the segmented kernels' table): frozen floats of the accumulator
+// Under an lr-scale mask every pass runs over the trainable runs only (the handle's span): frozen floats of the accumulator
 // and of the gradient arena are never read or written, so a pruned backward's stale ranges stay out of the sum.
 // Early Adam slices never run in a micro-batch (no adam_begin in front of its backward), and pack.version does not move between
 // micro-batches: packed filters are reused across them.
@@ -1321,9 +1320,7 @@ int accum_begin(ctx_handle* h, int total_batch) {
     return CTX_OK;
 }
 static void accum_enqueue(ctx_handle* h, int mode) {
-    float* g = h->arena + h->Ppad;
-    if (masked(h)) grad_accum_segmented(h->stream, h->accum, g, h->segs, mode, ACCUM_NT);
-    else grad_accum(h->stream, h->accum, g, h->gen ? h->gen->pend : h->P, mode, ACCUM_NT);      // the range the guard's sum covers
+    grad_accum(h->stream, h->accum, h->arena + h->Ppad, span_of(h, grad_end(h)), mode, ACCUM_NT);      // the range the guard's sum covers
 }
 int accum_micro_on_img(ctx_handle* h, int B, int nn_nlen, int nn_j0) {
     if (!accum_open(h)) return fail(h, CTX_E_STATE, "ctx_accum_begin first");

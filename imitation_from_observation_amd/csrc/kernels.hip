@@ -1,5 +1,5 @@
 // kernels.hip -- the HBM-bound and small kernels around the implicit GEMMs: split-K combine,
-// conv2d_transpose to 3 channels, input preprocessing, losses, bias gradients, lrelu', Adam.
+// conv2d_transpose to 3 channels, input preprocessing, losses, bias gradients, lrelu'.  (The optimizer's passes: optim.hip.)
 #include <cstdarg>
 #include <map>
 #include <mutex>
@@ -571,11 +571,6 @@ __global__ __launch_bounds__(NTHREADS) void pool3x3_kernel(const float* __restri
 __global__ __launch_bounds__(NTHREADS) void pack3to4_kernel(const float* __restrict__ in, float* __restrict__ out, int64_t npix) {
     for (int64_t p = (int64_t)blockIdx.x * NTHREADS + threadIdx.x; p < npix; p += (int64_t)gridDim.x * NTHREADS)
         *reinterpret_cast<float4*>(out + 4 * p) = make_float4(in[3 * p], in[3 * p + 1], in[3 * p + 2], 0.f);
-}
-
-static unsigned ew_blocks(int64_t work) {
-    int64_t b = (work + NTHREADS - 1) / NTHREADS;
-    return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
 }
 
 void pack3to4(hipStream_t s, const float* in, float* out, int64_t npix) {
@@ -1404,380 +1399,6 @@ void lrelu_mask(hipStream_t s, float* g, const float* act, int64_t n) {
     hipLaunchKernelGGL(lrelu_mask_kernel, dim3(ew_blocks(n / 4)), dim3(NTHREADS), 0, s, g, act, n);
 }
 
-// ------------------------------------------------------------------------------------------------
-// Fused multi-tensor Adam over the flat arena, TF formulation (eps outside the bias correction):
-//   m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; p -= lr_t m / (sqrt(v) + eps)
-// 7 arena passes of HBM traffic (read p,g,m,v; write p,m,v) in one launch.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NTHREADS) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                        float* __restrict__ v, int64_t n, float lr_t, float b1, float b2,
-                                                        float eps) {
-    const float c1 = 1.f - b1, c2 = 1.f - b2;
-    // streaming: every element is touched once per step and the arena (0.76 GB) is larger than any cache -- nontemporal loads and
-    // stores (1.334 GB in 0.231 ms = 5.8 TB/s against 0.245 ms with plain accesses; deeper unrolling measured slower, round 4)
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    for (int64_t i = ((int64_t)blockIdx.x * NTHREADS + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * 256 * 4) {
-        const f4 gg = __builtin_nontemporal_load(reinterpret_cast<const f4*>(g + i));
-        f4 mm = __builtin_nontemporal_load(reinterpret_cast<const f4*>(m + i));
-        f4 vv = __builtin_nontemporal_load(reinterpret_cast<const f4*>(v + i));
-        f4 pp = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p + i));
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            mm[k] = b1 * mm[k] + c1 * gg[k];
-            vv[k] = b2 * vv[k] + c2 * (gg[k] * gg[k]);
-            pp[k] = pp[k] - lr_t * mm[k] / (sqrtf(vv[k]) + eps);
-        }
-        __builtin_nontemporal_store(mm, reinterpret_cast<f4*>(m + i));
-        __builtin_nontemporal_store(vv, reinterpret_cast<f4*>(v + i));
-        __builtin_nontemporal_store(pp, reinterpret_cast<f4*>(p + i));
-    }
-}
-
-void adam(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float b1, float b2,
-          float eps) {
-    hipLaunchKernelGGL(adam_kernel, dim3(ew_blocks(n / 4)), dim3(NTHREADS), 0, s, p, g, m, v, n, lr_t, b1, b2, eps);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Guarded Adam (ctx_set_grad_guard): sum of g^2 -> {norm, clip factor, apply} in device memory -> Adam on g * factor, or nothing.
-// Every square and every sum is f64: the square of an f32 is exact there and a finite f32 gradient cannot overflow the sum, so
-// "the sum is non-finite" <=> "some gradient element is".  The order of the sum is fixed by GUARD_BLOCKS, not by the device: a thread
-// adds its grid-strided floats in index order, a wave64 tree joins the lanes, thread 0 adds the four wave sums in order and stores
-// the block's partial; grad_guard_final_kernel adds the partials in index order.  No atomics, no last-block hand-over.
-// ------------------------------------------------------------------------------------------------
-template <bool NT>
-__global__ __launch_bounds__(NTHREADS) void grad_sumsq_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ part) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    const f4* g4 = reinterpret_cast<const f4*>(g);
-    const int64_t n4 = n >> 2, stride = (int64_t)GUARD_BLOCKS * NTHREADS;
-    auto ld = [&](int64_t i) { return NT ? __builtin_nontemporal_load(g4 + i) : g4[i]; };
-    double acc = 0.0;
-    int64_t i = (int64_t)blockIdx.x * NTHREADS + threadIdx.x;
-    for (; i + 3 * stride < n4; i += 4 * stride) {      // four 16-byte loads in flight per thread, added in index order
-        f4 a[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) a[k] = ld(i + k * stride);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { const double x = (double)a[k][j]; acc = fma(x, x, acc); }
-    }
-    for (; i < n4; i += stride) {
-        const f4 a = ld(i);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const double x = (double)a[j]; acc = fma(x, x, acc); }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)            // n % 4 floats past the last whole 16 bytes
-        for (int64_t j = n4 * 4; j < n; ++j) { const double x = (double)g[j]; acc = fma(x, x, acc); }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    __shared__ double ws[NTHREADS / 64];
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
-}
-
-__global__ __launch_bounds__(NTHREADS) void grad_guard_final_kernel(const double* __restrict__ part, GuardCtl* __restrict__ ctl, float clip,
-                                                                    int skip_nonfinite, int count) {
-    __shared__ double sp[GUARD_BLOCKS];
-    for (int i = threadIdx.x; i < GUARD_BLOCKS; i += NTHREADS) sp[i] = part[i];
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    double s = 0.0;
-    for (int i = 0; i < GUARD_BLOCKS; ++i) s += sp[i];
-    const double norm = sqrt(s), c = (double)clip;
-    const bool finite = isfinite(s);
-    const bool clipped = finite && c > 0.0 && norm > c;         // norm <= clip, or no clip: factor is exactly 1
-    const uint32_t apply = skip_nonfinite && !finite ? 0u : 1u;
-    ctl->sumsq = s;
-    ctl->norm = norm;
-    ctl->factor = clipped ? (float)(c / norm) : 1.f;
-    ctl->apply = apply;
-    if (count) {
-        ctl->steps_skipped += apply ? 0 : 1;
-        ctl->steps_clipped += clipped ? 1 : 0;
-    }
-}
-
-__global__ __launch_bounds__(NTHREADS) void adam_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                                float* __restrict__ v, int64_t n, float lr_t, float b1, float b2,
-                                                                float eps, const GuardCtl* __restrict__ ctl) {
-    if (ctl->apply == 0) return;      // (uniform) a skipped step reads and writes nothing
-    const float factor = ctl->factor, c1 = 1.f - b1, c2 = 1.f - b2;
-    // adam_kernel's accesses and adam_kernel's arithmetic on g * factor.  The two fmaf are the contractions the compiler makes of
-    // adam_kernel's  b1 m + c1 g  and  b2 v + c2 (g g)  (its ISA: v_pk_mul c1 g, v_pk_fma b1 m; v_pk_mul g g, v_pk_mul c2 ., v_pk_fma
-    // b2 v); they are spelled out here because the extra multiply in front changed which product the compiler fused.  With factor = 1
-    // the update equals adam_kernel's bit for bit (tests/test_gpu_grad_guard.py holds the two against each other).
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    for (int64_t i = ((int64_t)blockIdx.x * NTHREADS + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * 256 * 4) {
-        const f4 gg = __builtin_nontemporal_load(reinterpret_cast<const f4*>(g + i)) * factor;
-        f4 mm = __builtin_nontemporal_load(reinterpret_cast<const f4*>(m + i));
-        f4 vv = __builtin_nontemporal_load(reinterpret_cast<const f4*>(v + i));
-        f4 pp = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p + i));
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            mm[k] = __builtin_fmaf(b1, mm[k], c1 * gg[k]);
-            vv[k] = __builtin_fmaf(b2, vv[k], c2 * (gg[k] * gg[k]));
-            pp[k] = pp[k] - lr_t * mm[k] / (sqrtf(vv[k]) + eps);
-        }
-        __builtin_nontemporal_store(mm, reinterpret_cast<f4*>(m + i));
-        __builtin_nontemporal_store(vv, reinterpret_cast<f4*>(v + i));
-        __builtin_nontemporal_store(pp, reinterpret_cast<f4*>(p + i));
-    }
-}
-
-void grad_guard(hipStream_t s, const float* g, int64_t n, double* part, GuardCtl* ctl, float clip, int skip_nonfinite, int count,
-                bool nontemporal) {
-    if (nontemporal) hipLaunchKernelGGL((grad_sumsq_kernel<true>), dim3(GUARD_BLOCKS), dim3(NTHREADS), 0, s, g, n, part);
-    else hipLaunchKernelGGL((grad_sumsq_kernel<false>), dim3(GUARD_BLOCKS), dim3(NTHREADS), 0, s, g, n, part);
-    hipLaunchKernelGGL(grad_guard_final_kernel, dim3(1), dim3(NTHREADS), 0, s, part, ctl, clip, skip_nonfinite, count);
-}
-
-void adam_guarded(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float b1, float b2, float eps,
-                  const GuardCtl* ctl) {
-    hipLaunchKernelGGL(adam_guarded_kernel, dim3(ew_blocks(n / 4)), dim3(NTHREADS), 0, s, p, g, m, v, n, lr_t, b1, b2, eps, ctl);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Adam and the guard's sum over the trainable runs of the arena (ctx_set_param_lr_scale; launch.h: AdamSegs).  Both kernels walk the
-// TRAINABLE 16-byte groups c = 0 .. pre[n) grid-strided, so a frozen tensor costs neither traffic nor iterations; a thread's c only
-// grows, so it finds the run of c by stepping `run` forward from where its last group was (at most n steps per thread in all).  The
-// table comes in as a kernel argument and is copied to LDS once per block: lanes of a wave that straddles two runs index it apart.
-// ------------------------------------------------------------------------------------------------
-struct SegTable {
-    uint32_t pre[ADAM_SEG_MAX + 1], first[ADAM_SEG_MAX];
-    float lr_t[ADAM_SEG_MAX];
-};
-__device__ inline void seg_table_load(SegTable& L, const AdamSegs& T) {
-    for (int i = threadIdx.x; i < ADAM_SEG_MAX; i += NTHREADS) {
-        // (past the runs in use: pre = the total, so no search ever steps beyond run n - 1)
-        L.pre[i] = i <= T.n ? T.pre[i] : T.pre[T.n];
-        L.first[i] = T.first[i];
-        L.lr_t[i] = T.lr_t[i];
-    }
-    if (threadIdx.x == 0) L.pre[ADAM_SEG_MAX] = T.pre[T.n];
-    __syncthreads();
-}
-
-// Per element adam_guarded_kernel's arithmetic (GUARD) or adam_kernel's (no factor: the same two contractions spelled out, see the
-// remark in adam_guarded_kernel), with the run's lr_t in place of the launch's: a tensor at scale s is updated exactly as the
-// unmasked kernels update it at the learning rate lr * s.
-template <bool GUARD>
-__global__ __launch_bounds__(NTHREADS) void adam_seg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                            float* __restrict__ v, const AdamSegs T, float b1, float b2, float eps,
-                                                            const GuardCtl* __restrict__ ctl) {
-    if (GUARD && ctl->apply == 0) return;      // (uniform) a skipped step reads and writes nothing
-    __shared__ SegTable L;
-    seg_table_load(L, T);
-    float factor = 1.f;
-    if (GUARD) factor = ctl->factor;
-    const float c1 = 1.f - b1, c2 = 1.f - b2;
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    const uint32_t total = L.pre[ADAM_SEG_MAX];
-    int run = 0;
-    for (uint32_t c = blockIdx.x * NTHREADS + threadIdx.x; c < total; c += gridDim.x * NTHREADS) {
-        while (c >= L.pre[run + 1]) ++run;
-        const int64_t i = ((int64_t)L.first[run] + (c - L.pre[run])) * 4;
-        const float lr_t = L.lr_t[run];
-        f4 gg = __builtin_nontemporal_load(reinterpret_cast<const f4*>(g + i));
-        if (GUARD) gg = gg * factor;
-        f4 mm = __builtin_nontemporal_load(reinterpret_cast<const f4*>(m + i));
-        f4 vv = __builtin_nontemporal_load(reinterpret_cast<const f4*>(v + i));
-        f4 pp = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p + i));
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            mm[k] = __builtin_fmaf(b1, mm[k], c1 * gg[k]);
-            vv[k] = __builtin_fmaf(b2, vv[k], c2 * (gg[k] * gg[k]));
-            pp[k] = pp[k] - lr_t * mm[k] / (sqrtf(vv[k]) + eps);
-        }
-        __builtin_nontemporal_store(mm, reinterpret_cast<f4*>(m + i));
-        __builtin_nontemporal_store(vv, reinterpret_cast<f4*>(v + i));
-        __builtin_nontemporal_store(pp, reinterpret_cast<f4*>(p + i));
-    }
-}
-
-// grad_sumsq_kernel's contract on the trainable groups: f64 squares and sums, the constant GUARD_BLOCKS grid, a thread adds its
-// grid-strided groups in index order (four loads in flight), the same wave tree and block partial -- the bits of the norm depend on the
-// mask and the gradient, not on the device.  No atomics.
-template <bool NT>
-__global__ __launch_bounds__(NTHREADS) void grad_sumsq_seg_kernel(const float* __restrict__ g, const AdamSegs T, int64_t n_end,
-                                                                  double* __restrict__ part) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    __shared__ SegTable L;
-    seg_table_load(L, T);
-    const uint32_t total = L.pre[ADAM_SEG_MAX], stride = GUARD_BLOCKS * NTHREADS;
-    int run = 0;
-    auto at = [&](uint32_t c) {                          // arena float index of trainable group c (calls with growing c)
-        while (c >= L.pre[run + 1]) ++run;
-        return ((int64_t)L.first[run] + (c - L.pre[run])) * 4;
-    };
-    auto ld = [&](int64_t i) {                           // floats at and past n_end belong to no tensor: read as 0
-        if (i + 4 <= n_end) return NT ? __builtin_nontemporal_load(reinterpret_cast<const f4*>(g + i)) : *reinterpret_cast<const f4*>(g + i);
-        f4 a;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) a[j] = i + j < n_end ? g[i + j] : 0.f;
-        return a;
-    };
-    double acc = 0.0;
-    uint32_t c = blockIdx.x * NTHREADS + threadIdx.x;
-    for (; (uint64_t)c + 3ull * stride < total; c += 4 * stride) {
-        f4 a[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) a[k] = ld(at(c + k * stride));
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { const double x = (double)a[k][j]; acc = fma(x, x, acc); }
-    }
-    for (; c < total; c += stride) {
-        const f4 a = ld(at(c));
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const double x = (double)a[j]; acc = fma(x, x, acc); }
-    }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    __shared__ double ws[NTHREADS / 64];
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
-}
-
-void adam_segmented(hipStream_t s, float* p, const float* g, float* m, float* v, const AdamSegs& T, float b1, float b2, float eps,
-                    const GuardCtl* ctl) {
-    const uint32_t total = T.pre[T.n];
-    if (!total) return;
-    if (ctl) hipLaunchKernelGGL((adam_seg_kernel<true>), dim3(ew_blocks(total)), dim3(NTHREADS), 0, s, p, g, m, v, T, b1, b2, eps, ctl);
-    else hipLaunchKernelGGL((adam_seg_kernel<false>), dim3(ew_blocks(total)), dim3(NTHREADS), 0, s, p, g, m, v, T, b1, b2, eps, ctl);
-}
-
-void grad_guard_segmented(hipStream_t s, const float* g, const AdamSegs& T, int64_t n_end, double* part, GuardCtl* ctl, float clip,
-                          int skip_nonfinite, int count, bool nontemporal) {
-    if (nontemporal) hipLaunchKernelGGL((grad_sumsq_seg_kernel<true>), dim3(GUARD_BLOCKS), dim3(NTHREADS), 0, s, g, T, n_end, part);
-    else hipLaunchKernelGGL((grad_sumsq_seg_kernel<false>), dim3(GUARD_BLOCKS), dim3(NTHREADS), 0, s, g, T, n_end, part);
-    hipLaunchKernelGGL(grad_guard_final_kernel, dim3(1), dim3(NTHREADS), 0, s, part, ctl, clip, skip_nonfinite, count);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Gradient accumulation (ctx_accum_*): the sum of several micro-batches' gradients beside the arena.  One elementwise pass over 16-byte
-// groups in three modes -- SET acc = g, ADD acc = acc + g, FOLD g = acc + g -- so an accumulation of k micro-batches leaves
-// ((g1 + g2) + ...) + gk in the gradient arena: one f32 add per element and micro-batch, nothing a compiler could contract, the same
-// bits on every device.  SEG: the trainable runs of an lr-scale mask only (adam_seg_kernel's walk); what lies between them is neither
-// read nor written, in the accumulator or in g.  NT: the loads of FOLD as nontemporal ones (its output is read next by the guard or
-// by Adam; which form is faster is measured, ctx_engine.cpp: ACCUM_NT).
-// ------------------------------------------------------------------------------------------------
-template <int MODE, bool NT>
-__device__ __forceinline__ void grad_accum_group(float* __restrict__ acc, float* __restrict__ g, int64_t i) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    f4* a4 = reinterpret_cast<f4*>(acc + i);
-    f4* g4 = reinterpret_cast<f4*>(g + i);
-    if (MODE == ACCUM_SET) { *a4 = *g4; return; }
-    const f4 a = NT ? __builtin_nontemporal_load(a4) : *a4;
-    const f4 x = NT ? __builtin_nontemporal_load(g4) : *g4;
-    const f4 sum = a + x;
-    if (MODE == ACCUM_ADD) *a4 = sum;
-    else *g4 = sum;
-}
-
-template <int MODE, bool NT>
-__global__ __launch_bounds__(NTHREADS) void grad_accum_kernel(float* __restrict__ acc, float* __restrict__ g, int64_t n4) {
-    for (int64_t c = (int64_t)blockIdx.x * NTHREADS + threadIdx.x; c < n4; c += (int64_t)gridDim.x * NTHREADS)
-        grad_accum_group<MODE, NT>(acc, g, c * 4);
-}
-
-template <int MODE, bool NT>
-__global__ __launch_bounds__(NTHREADS) void grad_accum_seg_kernel(float* __restrict__ acc, float* __restrict__ g, const AdamSegs T) {
-    __shared__ SegTable L;
-    seg_table_load(L, T);
-    const uint32_t total = L.pre[ADAM_SEG_MAX];
-    int run = 0;
-    for (uint32_t c = blockIdx.x * NTHREADS + threadIdx.x; c < total; c += gridDim.x * NTHREADS) {
-        while (c >= L.pre[run + 1]) ++run;
-        grad_accum_group<MODE, NT>(acc, g, ((int64_t)L.first[run] + (c - L.pre[run])) * 4);
-    }
-}
-
-void grad_accum(hipStream_t s, float* acc, float* g, int64_t n, int mode, bool nontemporal) {
-    const int64_t n4 = (n + 3) / 4;      // whole 16-byte groups: the caller's buffers reach the next multiple of 4 (the arena's slots are padded to 64)
-    if (n4 <= 0) return;
-    const dim3 grid(ew_blocks(n4)), block(NTHREADS);
-    if (mode == ACCUM_SET) hipLaunchKernelGGL((grad_accum_kernel<ACCUM_SET, false>), grid, block, 0, s, acc, g, n4);
-    else if (mode == ACCUM_ADD) hipLaunchKernelGGL((grad_accum_kernel<ACCUM_ADD, false>), grid, block, 0, s, acc, g, n4);
-    else if (nontemporal) hipLaunchKernelGGL((grad_accum_kernel<ACCUM_FOLD, true>), grid, block, 0, s, acc, g, n4);
-    else hipLaunchKernelGGL((grad_accum_kernel<ACCUM_FOLD, false>), grid, block, 0, s, acc, g, n4);
-}
-
-void grad_accum_segmented(hipStream_t s, float* acc, float* g, const AdamSegs& T, int mode, bool nontemporal) {
-    const uint32_t total = T.pre[T.n];
-    if (!total) return;
-    const dim3 grid(ew_blocks(total)), block(NTHREADS);
-    if (mode == ACCUM_SET) hipLaunchKernelGGL((grad_accum_seg_kernel<ACCUM_SET, false>), grid, block, 0, s, acc, g, T);
-    else if (mode == ACCUM_ADD) hipLaunchKernelGGL((grad_accum_seg_kernel<ACCUM_ADD, false>), grid, block, 0, s, acc, g, T);
-    else if (nontemporal) hipLaunchKernelGGL((grad_accum_seg_kernel<ACCUM_FOLD, true>), grid, block, 0, s, acc, g, T);
-    else hipLaunchKernelGGL((grad_accum_seg_kernel<ACCUM_FOLD, false>), grid, block, 0, s, acc, g, T);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Exponential moving average of the parameters (ctx_ema_*): the shadow e beside the arena, one elementwise pass over 16-byte groups
-// after Adam.  e = fmaf(c, p - e, e) with c = 1 - decay from the host -- TF's  shadow -= (1 - decay) * (shadow - var)  with the one
-// contraction spelled out, so no compiler picks another: e == p stays e exactly (p - e = 0), c == 0 leaves e exactly.  Streaming
-// like Adam (nontemporal 16-byte loads and stores, no atomics); ctl (nullable): a step the guard skipped (apply == 0) returns at
-// once, uniformly, as adam_guarded_kernel does.  SEG walk: adam_seg_kernel's, so a frozen tensor costs no traffic and keeps its bits.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void ema_group(float* __restrict__ e, const float* __restrict__ p, int64_t i, float c) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    const f4 pp = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p + i));
-    f4 ee = __builtin_nontemporal_load(reinterpret_cast<const f4*>(e + i));
-#pragma unroll
-    for (int k = 0; k < 4; ++k) ee[k] = __builtin_fmaf(c, pp[k] - ee[k], ee[k]);
-    __builtin_nontemporal_store(ee, reinterpret_cast<f4*>(e + i));
-}
-
-__global__ __launch_bounds__(NTHREADS) void ema_update_kernel(float* __restrict__ e, const float* __restrict__ p, int64_t n4, float c,
-                                                              const GuardCtl* __restrict__ ctl) {
-    if (ctl && ctl->apply == 0) return;        // (uniform) a skipped step leaves the shadow untouched too
-    for (int64_t g = (int64_t)blockIdx.x * NTHREADS + threadIdx.x; g < n4; g += (int64_t)gridDim.x * NTHREADS) ema_group(e, p, g * 4, c);
-}
-
-__global__ __launch_bounds__(NTHREADS) void ema_update_seg_kernel(float* __restrict__ e, const float* __restrict__ p, const AdamSegs T,
-                                                                  float c, const GuardCtl* __restrict__ ctl) {
-    if (ctl && ctl->apply == 0) return;        // (uniform)
-    __shared__ SegTable L;
-    seg_table_load(L, T);
-    const uint32_t total = L.pre[ADAM_SEG_MAX];
-    int run = 0;
-    for (uint32_t g = blockIdx.x * NTHREADS + threadIdx.x; g < total; g += gridDim.x * NTHREADS) {
-        while (g >= L.pre[run + 1]) ++run;
-        ema_group(e, p, ((int64_t)L.first[run] + (g - L.pre[run])) * 4, c);
-    }
-}
-
-// p <-> e over whole 16-byte groups: pure moves, so two swaps restore every bit
-__global__ __launch_bounds__(NTHREADS) void ema_swap_kernel(float* __restrict__ p, float* __restrict__ e, int64_t n4) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    for (int64_t g = (int64_t)blockIdx.x * NTHREADS + threadIdx.x; g < n4; g += (int64_t)gridDim.x * NTHREADS) {
-        f4* p4 = reinterpret_cast<f4*>(p) + g;
-        f4* e4 = reinterpret_cast<f4*>(e) + g;
-        const f4 pp = __builtin_nontemporal_load(p4), ee = __builtin_nontemporal_load(e4);
-        __builtin_nontemporal_store(ee, p4);
-        __builtin_nontemporal_store(pp, e4);
-    }
-}
-
-void ema_update(hipStream_t s, float* e, const float* p, int64_t n, float c, const GuardCtl* ctl) {
-    const int64_t n4 = n / 4;                  // n = Ppad, a multiple of 64
-    if (n4 <= 0) return;
-    hipLaunchKernelGGL(ema_update_kernel, dim3(ew_blocks(n4)), dim3(NTHREADS), 0, s, e, p, n4, c, ctl);
-}
-
-void ema_update_segmented(hipStream_t s, float* e, const float* p, const AdamSegs& T, float c, const GuardCtl* ctl) {
-    const uint32_t total = T.pre[T.n];
-    if (!total) return;
-    hipLaunchKernelGGL(ema_update_seg_kernel, dim3(ew_blocks(total)), dim3(NTHREADS), 0, s, e, p, T, c, ctl);
-}
-
-void ema_swap(hipStream_t s, float* p, float* e, int64_t n) {
-    const int64_t n4 = n / 4;
-    if (n4 <= 0) return;
-    hipLaunchKernelGGL(ema_swap_kernel, dim3(ew_blocks(n4)), dim3(NTHREADS), 0, s, p, e, n4);
-}
 
 // {loss, simloss, recon1, recon2} of a micro-batch into the accumulation's f64 slots: the recon sums add, simloss -- a mean over the
 // micro-batch's rows -- enters with the weight rows / total; slot 0 stays unused (`loss` is formed from the other three at the end).

@@ -1,5 +1,5 @@
 // launch.h -- host-callable launchers of every HIP kernel in libctxtrans (all enqueue on `s`, none
-// synchronise).  Definitions: gemm_*.hip (implicit-GEMM instantiations) and kernels.hip.
+// synchronise).  Definitions: gemm_*.hip (implicit-GEMM instantiations), kernels.hip and optim.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -258,27 +258,10 @@ void vjp_recon_tgt(hipStream_t s, float* g, const float* out, const float* out2,
 // g *= (act >= 0 ? 1 : 0.2)
 void lrelu_mask(hipStream_t s, float* g, const float* act, int64_t n);
 
-// TF Adam (scripts/train_script.py:124-128): lr_t precomputed on the host
-void adam(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float b1, float b2,
-          float eps);
-
-// Guarded Adam (ctx_set_grad_guard).  grad_guard: sum of g[0, n)^2 in f64 through `part` (GUARD_BLOCKS doubles), then {norm, factor,
-// apply} and -- `count` -- the counters into *ctl; adam_guarded: adam() on g * ctl->factor, or nothing at all when ctl->apply == 0.
-constexpr int GUARD_BLOCKS = 1024;   // grid of the sum: a constant, so that the order of the sum (the bits of the norm) is the same on every device
-struct GuardCtl {
-    double sumsq, norm;
-    float factor;
-    uint32_t apply;
-    int64_t steps_skipped, steps_clipped;
-};
-void grad_guard(hipStream_t s, const float* g, int64_t n, double* part, GuardCtl* ctl, float clip, int skip_nonfinite, int count,
-                bool nontemporal);
-void adam_guarded(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float b1, float b2, float eps,
-                  const GuardCtl* ctl);
-
-// Adam and the guard's sum on a SUBSET of the arena (ctx_set_param_lr_scale): the trainable tensors as runs of 16-byte groups in arena
-// order, each with its own lr_t.  The table is a kernel argument (488 B), so a step's values reach the device with the launch itself.
-// A kernel numbers the trainable groups 0 .. pre[n) and finds group c in run s with pre[s] <= c < pre[s + 1] at arena group
+// ---- the optimizer's passes over the arena (optim.hip) ----------------------------------------------------------------------------
+// A pass under an lr-scale mask (ctx_set_param_lr_scale) covers a SUBSET of the arena: the trainable tensors as runs of 16-byte groups
+// in arena order, each with its own lr_t.  The table is a kernel argument (488 B), so a step's values reach the device with the launch
+// itself.  A kernel numbers the trainable groups 0 .. pre[n) and finds group c in run s with pre[s] <= c < pre[s + 1] at arena group
 // first[s] + c - pre[s]: what lies between the runs (frozen tensors) is neither read nor written.
 constexpr int ADAM_SEG_MAX = 40;     // >= the tensors of any model (38)
 struct AdamSegs {
@@ -287,32 +270,49 @@ struct AdamSegs {
     uint32_t first[ADAM_SEG_MAX] = {};   // first arena group of run s
     float lr_t[ADAM_SEG_MAX] = {};
 };
-// adam() / adam_guarded() (ctl != nullptr) on the runs of T: one launch whatever the mask; nothing is launched for an empty table
-void adam_segmented(hipStream_t s, float* p, const float* g, float* m, float* v, const AdamSegs& T, float b1, float b2, float eps,
-                    const GuardCtl* ctl);
-// grad_guard() over the runs of T; of a group that reaches past float n_end (the end of the last tensor) only the floats in front of it
-void grad_guard_segmented(hipStream_t s, const float* g, const AdamSegs& T, int64_t n_end, double* part, GuardCtl* ctl, float clip,
-                          int skip_nonfinite, int count, bool nontemporal);
+// What a pass covers: the runs of a mask, or (runs == nullptr) the floats [0, n) of the pointers it gets -- n as each pass documents.
+struct Span {
+    const AdamSegs* runs;
+    int64_t n;                           // with runs: the end of the last tensor, which only grad_guard reads
+    float lr_t;                          // dense Adam's; a run has its own
+};
+inline unsigned ew_blocks(int64_t work) {    // grid of a grid-strided elementwise kernel
+    int64_t b = (work + NTHREADS - 1) / NTHREADS;
+    return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
+}
+
+// TF Adam (scripts/train_script.py:124-128), lr_t precomputed on the host, over [0, n) (n a multiple of 4) or the runs: one launch
+// whatever the mask.  ctl (nullable, ctx_set_grad_guard): on g * ctl->factor, or nothing at all when ctl->apply == 0.
+// grad_guard: the sum of g^2 over [0, n) (any n) or the runs -- of a group that reaches past n only the floats in front of it -- in f64
+// through `part` (GUARD_BLOCKS doubles), then {norm, factor, apply} and -- `count` -- the counters into *ctl.
+constexpr int GUARD_BLOCKS = 1024;   // grid of the sum: a constant, so that the order of the sum (the bits of the norm) is the same on every device
+struct GuardCtl {
+    double sumsq, norm;
+    float factor;
+    uint32_t apply;
+    int64_t steps_skipped, steps_clipped;
+};
+void adam(hipStream_t s, float* p, const float* g, float* m, float* v, const Span& sp, float b1, float b2, float eps, const GuardCtl* ctl);
+void grad_guard(hipStream_t s, const float* g, const Span& sp, double* part, GuardCtl* ctl, float clip, int skip_nonfinite, int count,
+                bool nontemporal);
 
 // Gradient accumulation (ctx_accum_*).  grad_accum: one elementwise pass over the 16-byte groups of acc / g [0, n) (n rounded up to 4:
-// both buffers reach that far) -- SET acc = g, ADD acc = acc + g, FOLD g = acc + g, plain f32 adds; _segmented: over the runs of T
-// only, nothing between them read or written.  nontemporal: the load form of FOLD.
+// both buffers reach that far) or of the runs -- SET acc = g, ADD acc = acc + g, FOLD g = acc + g, plain f32 adds.  nontemporal: the
+// load form of FOLD.
 // scalars_accum: a micro-batch's f32 {loss, simloss, recon1, recon2} into slots[5] (f64: [1] += simloss * rows / total, [2], [3] +=
 // the recon sums, [4] += *nn when given; first: = in place of +=); scalars_finish: the f32 scalars of the sum, `loss` from `terms`.
 enum { ACCUM_SET = 0, ACCUM_ADD = 1, ACCUM_FOLD = 2 };
 constexpr int ACCUM_SLOTS = 5;
-void grad_accum(hipStream_t s, float* acc, float* g, int64_t n, int mode, bool nontemporal);
-void grad_accum_segmented(hipStream_t s, float* acc, float* g, const AdamSegs& T, int mode, bool nontemporal);
+void grad_accum(hipStream_t s, float* acc, float* g, const Span& sp, int mode, bool nontemporal);
 void scalars_accum(hipStream_t s, const float* scalars, double* slots, int rows, int total, bool first, const double* nn);
 void scalars_finish(hipStream_t s, const double* slots, float* scalars, int terms);
 // the tgt slot of gather_triples alone: out[b] = vdata[(b0 + b) % T][ctgt[b]], b < B (the whole batch's tgt rows for nn_err)
 void gather_tgt(hipStream_t s, const uint8_t* vdata, int T, int N, int64_t npi, const int* ctgt, int B, int b0, const float* lut, float* out);
 
 // Exponential moving average of the parameters (ctx_ema_*).  ema_update: e = fmaf(c, p - e, e) over the 16-byte groups of [0, n)
-// (n a multiple of 4), c = 1 - decay; _segmented: over the runs of T only, nothing between them read or written.  ctl (nullable):
-// nothing at all when ctl->apply == 0 (a step the guard skipped).  ema_swap: p <-> e over [0, n), pure moves.
-void ema_update(hipStream_t s, float* e, const float* p, int64_t n, float c, const GuardCtl* ctl);
-void ema_update_segmented(hipStream_t s, float* e, const float* p, const AdamSegs& T, float c, const GuardCtl* ctl);
+// (n a multiple of 4) or of the runs, c = 1 - decay.  ctl (nullable): nothing at all when ctl->apply == 0 (a step the guard skipped).
+// ema_swap: p <-> e over [0, n), pure moves.
+void ema_update(hipStream_t s, float* e, const float* p, const Span& sp, float c, const GuardCtl* ctl);
 void ema_swap(hipStream_t s, float* p, float* e, int64_t n);
 
 }  // namespace ctx

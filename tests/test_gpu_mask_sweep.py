@@ -54,7 +54,7 @@ MI355X with this module and the 32 tests of tests/test_gpu_lr_scales.py):
                                                      added: no other model here reads the 4-channel copy of d out.
   dy = q.dec[k][0] || q.dec_dx[k] (the layer's bias  test_sweep[skip32], test_sweep[skip32_c4] ("only deconv/d_h1/biases": every entry
   forgotten in the decoder's chain)                  is the previous step's); tests/test_gpu_lr_scales.py passes.
-  adam_seg_kernel ending one run early               21 tests here -- all of test_every_tensor_its_own_run, test_fragmented_mask and
+  adam_kernel<AdamSegs, .> ending one run early      21 tests here -- all of test_every_tensor_its_own_run, test_fragmented_mask and
                                                      test_accumulation_under_a_checkerboard, both test_mask_changes_on_a_live_handle --
                                                      and 18 of tests/test_gpu_lr_scales.py.
 """

@@ -8,7 +8,7 @@ and of translate at 25 frames directly after a swap -- packed filters stale, the
     python tools/bench_ema.py --off-only     the first form alone, touching no ctx_ema_* entry: runs in a checkout of an older commit
                                              as well (copy this file there), for the step time of a library that has no average
     python tools/bench_ema.py --trace        a few steps with the average on, nothing else: what
-                                             `rocprofv3 --kernel-trace --stats -f csv --` wraps (ema_update_kernel's us per launch)"""
+                                             `rocprofv3 --kernel-trace --stats -f csv --` wraps (ema_update_kernel<...>'s us per launch)"""
 import argparse
 import os
 import sys

@@ -12,6 +12,7 @@ synchronise; medians and interquartile ranges over --rounds rounds.
 import argparse
 import csv
 import os
+import re
 import sys
 import time
 
@@ -24,7 +25,8 @@ H = W = 64
 D, F = 64, 1024
 FORMS = (("guard off", None), ("guard on, no clipping", dict(clip_norm=None, skip_nonfinite=True)),
          ("guard on, clipping", dict(clip_norm=1e-3, skip_nonfinite=True)))
-KERNELS = ("grad_sumsq_kernel", "grad_guard_final_kernel", "adam_guarded_kernel", "adam_kernel")
+# (patterns on demangled names: the guarded and the unguarded Adam are instantiations of one template, apart by its last argument)
+KERNELS = ("grad_sumsq_kernel", "grad_guard_final_kernel", r"adam_kernel<[^>]*true>", r"adam_kernel<[^>]*false>")
 
 
 def stats(path, n_params):
@@ -35,7 +37,7 @@ def stats(path, n_params):
     print(f"{'kernel':34s} {'launches':>9s} {'us/launch':>10s} {'GB/s of 4 P bytes':>18s}")
     for key in KERNELS:
         for r in rows:
-            if key in r[name]:
+            if re.search(key, r[name]):
                 c, t = int(r[calls]), float(r[total])
                 us = t / c / 1e3
                 gbs = f"{4.0 * n_params / (us * 1e-6) / 1e9:18.0f}" if key == "grad_sumsq_kernel" else f"{'':18s}"
