@@ -43,6 +43,17 @@ class CtxProfEntry(ctypes.Structure):
                 ("ms", ctypes.c_float), ("useful_frac", ctypes.c_float)]
 
 
+class CtxTensorStat(ctypes.Structure):
+    """ctx_tensor_stat of include/ctxtrans.h: one tensor's row of ctx_tensor_stats_get (48 bytes)."""
+    _fields_ = [(n, ctypes.c_double) for n in ("g_sumsq", "p_sumsq", "u_sumsq")] + \
+               [(n, ctypes.c_float) for n in ("g_absmax", "p_absmax", "u_absmax")] + \
+               [(n, ctypes.c_uint32) for n in ("g_nonfinite", "p_nonfinite", "flags")]
+
+
+CTX_TSTAT_PARAMS, CTX_TSTAT_GRADS = 1, 2
+CTX_TSTAT_F_TRAINABLE, CTX_TSTAT_F_GRADS, CTX_TSTAT_F_UPDATE, CTX_TSTAT_F_PARAMS = 1, 2, 4, 8
+
+
 class CtxDiscConfig(ctypes.Structure):
     """ctx_disc_config of include/ctxtrans.h."""
     _fields_ = [(n, ctypes.c_int32) for n in ("variant", "H", "W", "C", "max_batch")]
@@ -176,6 +187,11 @@ SIGNATURES = {
     "ctx_ema_state": (_c.c_int, [_P, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _F, _c.POINTER(_c.c_int64)]),
     "ctx_get_ema": (_c.c_int, [_P, _F, _c.c_int64, _c.POINTER(_c.c_int64)]),
     "ctx_set_ema": (_c.c_int, [_P, _F, _c.c_int64, _c.c_int64]),
+    "ctx_tensor_stats_enable": (_c.c_int, [_P, _c.c_int]),
+    "ctx_tensor_stats_disable": (_c.c_int, [_P]),
+    "ctx_tensor_stats_compute": (_c.c_int, [_P, _c.c_int]),
+    "ctx_tensor_stats_get": (_c.c_int, [_P, _c.POINTER(CtxTensorStat), _c.c_int, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int64),
+                                        _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
     "ctx_profile_step": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_float, _c.c_int, _c.POINTER(CtxProfEntry), _c.c_int,
                                     _c.POINTER(_c.c_int)]),
     "ctx_debug_read": (_c.c_int, [_P, _c.c_char_p, _F, _c.c_size_t]),

@@ -155,6 +155,7 @@ void ctx_destroy(ctx_handle* h) {
     if (h->nn_dist) (void)hipFree(h->nn_dist);
     if (h->nn_tgt) (void)hipFree(h->nn_tgt);
     if (h->ema) (void)hipFree(h->ema);
+    tstat_free(h);
     for (auto& kv : h->graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
     delete h->gen;
     dp_teardown(h);
@@ -1105,6 +1106,59 @@ int ctx_set_ema(ctx_handle* h, const float* in, int64_t n, int64_t updates) {
     if (h->ema_swapped) return ema_refuse(h, "ctx_set_ema");
     TRY(arena_io(h, SLOT_EMA, nullptr, in, (size_t)n));
     h->ema_t = updates;
+    return CTX_OK;
+}
+
+// ---- per-tensor statistics (include/ctxtrans.h; the table and the launches: ctx_engine.cpp tstat_*, from adam_end) ---------------------
+static_assert(sizeof(ctx_tensor_stat) == sizeof(TStatRow) && sizeof(ctx_tensor_stat) == 48, "a row of the kernels is a ctx_tensor_stat");
+static_assert(CTX_TSTAT_F_GRADS == TSTAT_G && CTX_TSTAT_F_UPDATE == TSTAT_U && CTX_TSTAT_F_PARAMS == TSTAT_P, "the row's flag bits");
+
+int ctx_tensor_stats_enable(ctx_handle* h, int every) {
+    if (!h) return CTX_E_INVALID;
+    if (every < 1) return fail(h, CTX_E_INVALID, "ctx_tensor_stats_enable: every must be >= 1");
+    HIP_TRY(h, hipSetDevice(h->device));
+    TRY(tstat_alloc(h));
+    h->tstat_every = every;
+    return CTX_OK;
+}
+
+int ctx_tensor_stats_disable(ctx_handle* h) {
+    if (!h) return CTX_E_INVALID;
+    h->tstat_every = 0;
+    if (!h->tstat_rows) return CTX_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));      // a table in flight still writes the buffers
+    tstat_free(h);
+    return CTX_OK;
+}
+
+int ctx_tensor_stats_compute(ctx_handle* h, int what) {
+    if (!h) return CTX_E_INVALID;
+    if (what <= 0 || (what & ~(CTX_TSTAT_PARAMS | CTX_TSTAT_GRADS))) return fail(h, CTX_E_INVALID, "ctx_tensor_stats_compute: what is CTX_TSTAT_PARAMS | CTX_TSTAT_GRADS");
+    if ((what & CTX_TSTAT_GRADS) && !h->have_grads) return fail(h, CTX_E_STATE, "ctx_tensor_stats_compute of gradients before any backward");
+    HIP_TRY(h, hipSetDevice(h->device));
+    TRY(tstat_alloc(h));
+    tstat_enqueue(h, (what & CTX_TSTAT_PARAMS ? TSTAT_P : 0u) | (what & CTX_TSTAT_GRADS ? TSTAT_G : 0u), false);
+    HIP_TRY(h, hipGetLastError());
+    return CTX_OK;
+}
+
+int ctx_tensor_stats_get(ctx_handle* h, ctx_tensor_stat* rows, int cap, int* n, int64_t* adam_step, int* applied, int* has_update) {
+    if (!h || !rows) return CTX_E_INVALID;
+    if (!h->tstat_rows || h->tstat_step < 0) return fail(h, CTX_E_STATE, "ctx_tensor_stats_get before any table was taken: ctx_tensor_stats_enable and a step, or ctx_tensor_stats_compute");
+    const int np = h->tstat_tab.n;
+    if (cap < np) return fail(h, CTX_E_INVALID, "ctx_tensor_stats_get: room for %d rows, the handle has %d tensors", cap, np);
+    HIP_TRY(h, hipSetDevice(h->device));
+    std::vector<unsigned char> buf(TSTAT_ROWS_BYTES);
+    HIP_TRY(h, hipMemcpyAsync(buf.data(), h->tstat_rows, buf.size(), hipMemcpyDeviceToHost, h->stream));
+    TRY(finish(h));
+    TStatHead hd;
+    memcpy(&hd, buf.data() + (size_t)ADAM_SEG_MAX * sizeof(TStatRow), sizeof hd);
+    memcpy(rows, buf.data(), (size_t)np * sizeof(ctx_tensor_stat));
+    if (n) *n = np;
+    if (adam_step) *adam_step = h->tstat_step;
+    if (applied) *applied = (int)hd.applied;
+    if (has_update) *has_update = (int)hd.has_update;
     return CTX_OK;
 }
 

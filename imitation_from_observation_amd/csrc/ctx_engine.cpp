@@ -329,11 +329,16 @@ void adam_launch(ctx_handle* h, hipStream_t s, int64_t first, int64_t end) {
     float *p = h->arena + first, *g = p + h->Ppad, *m = g + h->Ppad, *v = m + h->Ppad;
     adam(s, p, g, m, v, span_of(h, end - first), 0.9f, 0.999f, 1e-8f, guard_on(h) ? h->guard_ctl : nullptr);   // (ctx_set_grad_guard, below)
 }
+// Adam's rate at update adam_t for the learning rate lr_
+static float adam_lr_t_of(const ctx_handle* h, float lr_) {
+    const double b1 = 0.9, b2 = 0.999;
+    return (float)((double)lr_ * std::sqrt(1.0 - std::pow(b2, (double)h->adam_t)) / (1.0 - std::pow(b1, (double)h->adam_t)));
+}
 void adam_begin(ctx_handle* h, float lr) {
     const bool env_on = h->opt.v[OPT_EARLY_ADAM] != 0;
-    const double b1 = 0.9, b2 = 0.999;
     h->adam_t += 1;
-    auto lr_t_of = [&](float lr_) { return (float)((double)lr_ * std::sqrt(1.0 - std::pow(b2, (double)h->adam_t)) / (1.0 - std::pow(b1, (double)h->adam_t))); };
+    auto lr_t_of = [&](float lr_) { return adam_lr_t_of(h, lr_); };
+    h->adam_lr = lr;
     h->adam_lr_t = lr_t_of(lr);
     // under a mask every run has its own: the f32 product lr * scale through the same expression, so a tensor at scale s steps exactly
     // as an unmasked handle steps it at the learning rate float(lr * s)
@@ -362,6 +367,7 @@ int tensor_spans(ctx_handle* h) {
         if (h->span[i].first % 4 || h->span[i].second <= h->span[i].first)
             return fail(h, CTX_E_INVALID, "parameter %s does not start on a 16-byte group of the arena", h->params[i].name.c_str());
     }
+    tstat_plan(h);
     return CTX_OK;
 }
 
@@ -372,6 +378,7 @@ void plan_mask(ctx_handle* h) {
     h->prune = Prune{};
     h->prof_entries.clear();         // ctx_profile_step names its entries at their first run: another mask is another sequence
     h->prof_ms.clear();
+    tstat_plan(h);                   // (which tensors the statistics read g, m and v of)
     if (!masked(h)) return;
     AdamSegs& T = h->segs;
     uint32_t total = 0;
@@ -492,6 +499,8 @@ void adam_end(ctx_handle* h) {
     }
     // the averaged copy follows every Adam update (ctx_ema_enable): behind the join, so the early slices' parameters are complete
     if (ema_on(h)) ema_enqueue(h, guard_on(h));
+    // ... and so does a table of per-tensor statistics on every tstat_every-th update (ctx_tensor_stats_enable), the last work of all
+    if (h->tstat_every > 0 && h->adam_t % h->tstat_every == 0) tstat_enqueue(h, TSTAT_G | TSTAT_P | TSTAT_U, guard_on(h));
     h->adam_early_on = false;
     h->adam_done.clear();
     h->pack.version++;               // nothing packed while the update was in flight (adam_begin .. here) may pass as current afterwards
@@ -522,6 +531,60 @@ int ema_reset(ctx_handle* h) {
     HIP_TRY(h, hipMemcpyAsync(h->ema, h->arena, (size_t)h->Ppad * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
     h->ema_t = 0;
     return CTX_OK;
+}
+
+// ---- per-tensor statistics (ctx_tensor_stats_*) --------------------------------------------------------------------------------------
+// What the optimizer tail did, per tensor, without the arena leaving the device: kernels and the order of their sums in optim.hip, the
+// table in launch.h.  tstat_plan fills everything of the table but `what` and lr_t from h->span -- a tensor's TRUE end is the next
+// tensor's first float and, for the last one, grad_end (not the padded group span[] ends on) -- and from the mask; it runs at create
+// and wherever plan_mask does.  Every tensor has its chunks whatever the mask: a frozen tensor's p is still read.
+// tstat_enqueue adds the step's lr_t per tensor -- float(lr * scale) through adam_begin's own expression, so a tensor's u is measured at
+// the rate its run was updated at -- and launches the two stages on h->stream.  The buffers are small (47.6 M floats: 11.6 k partials of
+// 48 B) and the library's own, as the average's.
+void tstat_plan(ctx_handle* h) {
+    TStatTable& T = h->tstat_tab;
+    T = TStatTable{};
+    const size_t n = h->span.size();
+    if (n > (size_t)ADAM_SEG_MAX || grad_end(h) >= (1ll << 32)) return;       // (n = 0: the statistics refuse such a handle)
+    uint32_t chunks = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t first = h->span[i].first, end = i + 1 < n ? h->span[i + 1].first : grad_end(h);
+        T.first[i] = (uint32_t)first; T.end[i] = (uint32_t)end;
+        T.cpre[i] = chunks;
+        chunks += (uint32_t)((end - first + TSTAT_CHUNK - 1) / TSTAT_CHUNK);
+        T.flags[i] = !masked(h) || h->lr_scale[i] != 0.f ? 1u : 0u;
+    }
+    T.cpre[n] = chunks;
+    T.n = (int32_t)n;
+}
+int tstat_alloc(ctx_handle* h) {
+    if (h->tstat_rows) return CTX_OK;
+    if (h->tstat_tab.n <= 0) return fail(h, CTX_E_INVALID, "the statistics' table holds %d tensors of an arena below 2^32 floats", ADAM_SEG_MAX);
+    const size_t part_bytes = (size_t)h->tstat_tab.cpre[h->tstat_tab.n] * sizeof(TStatRow);
+    void *a = nullptr, *b = nullptr;
+    hipError_t e = hipMalloc(&a, part_bytes);
+    if (e == hipSuccess) e = hipMalloc(&b, TSTAT_ROWS_BYTES);
+    if (e != hipSuccess) {
+        if (a) (void)hipFree(a);
+        return fail(h, CTX_E_NOMEM, "hipMalloc(%zu bytes) for the per-tensor statistics: %s", part_bytes + TSTAT_ROWS_BYTES, hipGetErrorString(e));
+    }
+    h->tstat_part = (TStatRow*)a; h->tstat_rows = (TStatRow*)b;
+    return CTX_OK;
+}
+void tstat_free(ctx_handle* h) {
+    if (h->tstat_part) (void)hipFree(h->tstat_part);
+    if (h->tstat_rows) (void)hipFree(h->tstat_rows);
+    h->tstat_part = h->tstat_rows = nullptr;
+    h->tstat_step = -1;
+}
+void tstat_enqueue(ctx_handle* h, uint32_t what, bool guarded) {
+    TStatTable& T = h->tstat_tab;
+    T.what = what;
+    for (int i = 0; i < T.n; ++i)
+        T.lr_t[i] = !(what & TSTAT_U) || !(T.flags[i] & 1u) ? 0.f : masked(h) ? adam_lr_t_of(h, h->adam_lr * h->lr_scale[i]) : h->adam_lr_t;
+    const float *p = h->arena, *g = p + h->Ppad, *m = g + h->Ppad, *v = m + h->Ppad;
+    tensor_stats(h->stream, p, g, m, v, T, 1e-8f, guarded ? h->guard_ctl : nullptr, h->tstat_part, h->tstat_rows);
+    h->tstat_step = h->adam_t;
 }
 
 // the tail of the gradient arena [first, Ppad) (translate/*, deconv/*: arena order is conv_context, conv, translate, deconv) is final

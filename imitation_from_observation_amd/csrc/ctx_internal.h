@@ -279,6 +279,16 @@ struct ctx_handle {
     float ema_decay = 0.f;
     bool ema_warm = false, ema_swapped = false;
     int64_t ema_t = 0;
+    // per-tensor statistics (ctx_tensor_stats_*; tstat_every == 0 = the automatic form is off: no extra launch).  tstat_tab = the
+    // per-tensor table of the kernels (launch.h), rebuilt by plan_mask from span and lr_scale; tstat_part = one partial per chunk,
+    // tstat_rows = the rows and the head behind them: the library's OWN allocations (not in `allocs`: ctx_tensor_stats_disable frees
+    // them), made at enable or at the first ctx_tensor_stats_compute.  adam_end enqueues a table as its last work on every
+    // tstat_every-th update.  tstat_step = the Adam step count the last table was taken at on the host's side (-1: none yet).
+    TStatTable tstat_tab;
+    TStatRow *tstat_part = nullptr, *tstat_rows = nullptr;
+    int tstat_every = 0;
+    int64_t tstat_step = -1;
+    float adam_lr = 0.f;          // the lr of the last adam_begin: a tensor's lr_t is formed from it as a run's is
     // tf.nn.dropout (CTX_VARIANT_REAL with keep_prob < 1): on only while a TRAINING step (forward + backward) is being enqueued
     bool drop_on = false;
     uint64_t drop_seed = 0;
@@ -370,6 +380,12 @@ inline bool ema_on(const ctx_handle* h) { return h->ema != nullptr; }
 int ema_refuse(ctx_handle* h, const char* what);
 void ema_enqueue(ctx_handle* h, bool guarded);
 int ema_reset(ctx_handle* h);
+// per-tensor statistics (ctx_engine.cpp): the table from span / lr_scale | the buffers | one table enqueued on h->stream: `what` of
+// TSTAT_G / _P / _U, guarded: under the guard's skip decision | the buffers freed
+void tstat_plan(ctx_handle* h);
+int tstat_alloc(ctx_handle* h);
+void tstat_enqueue(ctx_handle* h, uint32_t what, bool guarded);
+void tstat_free(ctx_handle* h);
 int dp_wait(ctx_handle* h);                                           // ctx_dp.cpp
 int stage_frames(ctx_handle* h, const float* d_src, const float* d_ctx, const float* d_tgt, int B);   // ctx_abi.cpp
 int nn_err_enqueue(ctx_handle* h, const float* tgt, int Bt, int nlen, int j0);                       // ctx_abi.cpp: h->nn_res[0]

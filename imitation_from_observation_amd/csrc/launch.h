@@ -315,4 +315,33 @@ void gather_tgt(hipStream_t s, const uint8_t* vdata, int T, int N, int64_t npi, 
 void ema_update(hipStream_t s, float* e, const float* p, const Span& sp, float c, const GuardCtl* ctl);
 void ema_swap(hipStream_t s, float* p, float* e, int64_t n);
 
+// Per-tensor statistics (ctx_tensor_stats_*): one TStatRow per tensor from a two-stage reduction whose order is fixed by the table alone.
+// Tensor t owns the arena floats [first[t], end[t]) -- end = the next tensor's first, the last tensor's its TRUE end -- cut into chunks of
+// TSTAT_CHUNK floats from its first float on, chunks cpre[t] .. cpre[t + 1) of the handle.  Stage 1 writes chunk c's partial to part[c];
+// stage 2, one block per tensor, adds that tensor's partials in index order and writes rows[t], and block 0 the head behind the rows.
+// A chunk belongs to one tensor and every tensor has its chunks whatever the mask, so a row's bits depend neither on the grid nor on
+// which other tensors are frozen.  `what`: TSTAT_G / _P / _U select the sections read; of a tensor whose flag bit 0 is clear (frozen)
+// only p is.  u = adam_update(lr_t[t], m, v, eps), and exactly 0 where ctl (nullable) says the step was skipped.  The table is a kernel
+// argument (812 B), as AdamSegs is.
+constexpr int TSTAT_CHUNK = 4096;    // floats: 4 16-byte groups per thread of a block
+constexpr uint32_t TSTAT_G = 2, TSTAT_P = 8, TSTAT_U = 4;     // = the row's flag bits beside bit 0 (trainable)
+struct TStatTable {
+    int32_t n = 0;
+    uint32_t what = 0;
+    uint32_t cpre[ADAM_SEG_MAX + 1] = {};
+    uint32_t first[ADAM_SEG_MAX] = {}, end[ADAM_SEG_MAX] = {};
+    float lr_t[ADAM_SEG_MAX] = {};       // 0 for a frozen tensor
+    uint32_t flags[ADAM_SEG_MAX] = {};   // bit 0: trainable
+};
+struct TStatRow {
+    double g_sumsq, p_sumsq, u_sumsq;
+    float g_absmax, p_absmax, u_absmax;
+    uint32_t g_nonfinite, p_nonfinite, flags;
+};
+static_assert(sizeof(TStatRow) == 48 && alignof(TStatRow) == 8, "ctx_tensor_stat (include/ctxtrans.h) is 48 bytes: 3 f64, 3 f32, 3 u32");
+struct TStatHead { uint32_t applied, has_update, pad[2]; };   // behind the rows, at rows[ADAM_SEG_MAX]
+constexpr size_t TSTAT_ROWS_BYTES = (size_t)ADAM_SEG_MAX * sizeof(TStatRow) + sizeof(TStatHead);
+void tensor_stats(hipStream_t s, const float* p, const float* g, const float* m, const float* v, const TStatTable& T, float eps,
+                  const GuardCtl* ctl, TStatRow* part, TStatRow* rows);
+
 }  // namespace ctx

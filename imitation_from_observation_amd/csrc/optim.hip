@@ -1,5 +1,5 @@
-// optim.hip -- the optimizer's elementwise passes over the flat arena: Adam, the guard's sum of squares, gradient accumulation and the
-// parameter average.  Each has ONE body in ONE kernel template, instantiated over the two walks below.  Launchers: launch.h (Span).
+// optim.hip -- the optimizer's elementwise passes over the flat arena: Adam, the guard's sum of squares, gradient accumulation, the
+// parameter average and the per-tensor statistics.  Each has ONE body in ONE kernel template, instantiated over the two walks below.  Launchers: launch.h (Span).
 #include "launch.h"
 namespace ctx {
 typedef float f4 __attribute__((ext_vector_type(4)));
@@ -55,6 +55,8 @@ template <class A> __device__ __forceinline__ typename Walk<A>::index grid_step(
 // updated exactly as an unmasked handle updates it at the learning rate lr * s.  The contractions  b1 m + c1 g  and  b2 v + c2 (g g)  are
 // spelled out (ISA: v_pk_mul c1 g, v_pk_fma b1 m; v_pk_mul g g, v_pk_mul c2 ., v_pk_fma b2 v), so no instantiation rounds otherwise,
 // whatever stands in front of them: with factor = 1 the guarded update is the unguarded one bit for bit, and the masked the dense.
+// the update one element moves by -- adam_kernel subtracts it, the statistics pass (below) measures it: one expression for both
+__device__ __forceinline__ float adam_update(float lr_t, float m, float v, float eps) { return lr_t * m / (sqrtf(v) + eps); }
 template <class A, bool GUARD>
 __global__ __launch_bounds__(NTHREADS) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                         const A span, float b1, float b2, float eps, const GuardCtl* __restrict__ ctl) {
@@ -75,7 +77,7 @@ __global__ __launch_bounds__(NTHREADS) void adam_kernel(float* __restrict__ p, c
         for (int k = 0; k < 4; ++k) {
             mm[k] = __builtin_fmaf(b1, mm[k], c1 * gg[k]);
             vv[k] = __builtin_fmaf(b2, vv[k], c2 * (gg[k] * gg[k]));
-            pp[k] = pp[k] - lr_t * mm[k] / (sqrtf(vv[k]) + eps);
+            pp[k] = pp[k] - adam_update(lr_t, mm[k], vv[k], eps);
         }
         __builtin_nontemporal_store(mm, reinterpret_cast<f4*>(m + i));
         __builtin_nontemporal_store(vv, reinterpret_cast<f4*>(v + i));
@@ -199,6 +201,115 @@ __global__ __launch_bounds__(NTHREADS) void ema_swap_kernel(float* __restrict__ 
     }
 }
 
+// ---- per-tensor statistics (ctx_tensor_stats_*): sums of squares, largest magnitudes and non-finite counts of g, p and u per tensor -----
+// Two stages whose order of summation is fixed by the table (launch.h: TStatTable) and by nothing else.  Stage 1: a block takes whole
+// chunks of TSTAT_CHUNK floats grid-strided; a thread adds its 4 16-byte groups of the chunk, element by element in index order, in f64
+// (the square of an f32 is exact there) over the FINITE elements only, a wave64 tree joins the lanes, the four wave results are joined in
+// order and the chunk's partial goes to part[chunk] -- a slot of the chunk, not of the block.  Stage 2: one block per tensor, a thread adds
+// the tensor's partials c0 + tid, c0 + tid + NTHREADS, ... in index order, then the same tree.  No atomics, no last-block hand-over.
+// Depth of the sum of one tensor: 16 + 6 + 3 in stage 1, ceil(chunks / NTHREADS) + 6 + 3 in stage 2.
+// A frozen tensor's g, m and v are never read (a pruned backward never wrote that g), nor any float at or past a tensor's end: the
+// group that reaches past it is read float by float.  The loads are nontemporal: nothing in the step reads the arena after this pass.
+struct TStatAcc {
+    double s; float mx; uint32_t nf;                 // (plain data: it lives in LDS too; start from {})
+    __device__ __forceinline__ void add(float x) {
+        if (isfinite(x)) { const double d = (double)x; s = fma(d, d, s); mx = fmaxf(mx, fabsf(x)); }
+        else ++nf;
+    }
+    __device__ __forceinline__ void join(const TStatAcc& b) { s += b.s; mx = fmaxf(mx, b.mx); nf += b.nf; }
+};
+// the block's result, in every thread; ws[NTHREADS / 64] is free again on return
+__device__ __forceinline__ TStatAcc tstat_block(TStatAcc a, TStatAcc* ws) {
+    for (int off = 32; off > 0; off >>= 1) {
+        TStatAcc b;
+        b.s = __shfl_down(a.s, off, 64); b.mx = __shfl_down(a.mx, off, 64); b.nf = __shfl_down(a.nf, off, 64);
+        a.join(b);
+    }
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = a;
+    __syncthreads();
+    TStatAcc r = ws[0];
+    for (int w = 1; w < NTHREADS / 64; ++w) r.join(ws[w]);
+    __syncthreads();
+    return r;
+}
+__device__ __forceinline__ f4 tstat_ld(const float* __restrict__ x, int64_t i, int64_t end) {     // floats at and past `end` read as 0
+    if (i + 4 <= end) return __builtin_nontemporal_load(reinterpret_cast<const f4*>(x + i));
+    f4 a = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) if (i + j < end) a[j] = x[i + j];
+    return a;
+}
+// what a tensor's row says was read: bit 0 trainable, then the sections (launch.h)
+__device__ __forceinline__ uint32_t tstat_flags(const TStatTable& T, int t) {
+    const uint32_t tr = T.flags[t] & 1u;
+    return tr | (T.what & TSTAT_P) | (tr ? T.what & (TSTAT_G | TSTAT_U) : 0u);
+}
+__device__ __forceinline__ TStatRow tstat_row(const TStatAcc& g, const TStatAcc& p, const TStatAcc& u, uint32_t flags) {
+    TStatRow r;
+    r.g_sumsq = g.s; r.p_sumsq = p.s; r.u_sumsq = u.s;
+    r.g_absmax = g.mx; r.p_absmax = p.mx; r.u_absmax = u.mx;
+    r.g_nonfinite = g.nf; r.p_nonfinite = p.nf; r.flags = flags;
+    return r;
+}
+__global__ __launch_bounds__(NTHREADS) void tensor_stats_chunk_kernel(const float* __restrict__ p, const float* __restrict__ g, const float* __restrict__ m,
+                                                                      const float* __restrict__ v, const TStatTable T, float eps,
+                                                                      const GuardCtl* __restrict__ ctl, TStatRow* __restrict__ part) {
+    __shared__ TStatAcc ws[NTHREADS / 64];
+    const bool applied = !ctl || ctl->apply != 0;        // a skipped step moved nothing: u is exactly 0 and m, v are not read
+    const uint32_t total = T.cpre[T.n];
+    int t = 0;
+    for (uint32_t c = blockIdx.x; c < total; c += gridDim.x) {           // (everything about the chunk is uniform over the block)
+        while (c >= T.cpre[t + 1]) ++t;
+        const uint32_t flags = tstat_flags(T, t);
+        const bool rp = flags & TSTAT_P, rg = flags & TSTAT_G, ru = (flags & TSTAT_U) && applied;
+        const float lr_t = T.lr_t[t];
+        const int64_t end = T.end[t], base = (int64_t)T.first[t] + (int64_t)(c - T.cpre[t]) * TSTAT_CHUNK + (int64_t)threadIdx.x * 4;
+        TStatAcc ag = {}, ap = {}, au = {};
+        constexpr int K = TSTAT_CHUNK / (4 * NTHREADS);
+        f4 xg[K] = {}, xp[K] = {}, xm[K] = {}, xv[K] = {};
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int64_t i = base + (int64_t)k * 4 * NTHREADS;
+            if (i >= end) continue;
+            if (rg) xg[k] = tstat_ld(g, i, end);
+            if (rp) xp[k] = tstat_ld(p, i, end);
+            if (ru) { xm[k] = tstat_ld(m, i, end); xv[k] = tstat_ld(v, i, end); }
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {                // (what was not read is 0: finite, adds 0 to a sum and to a maximum; u of m = v = 0 is 0)
+                ag.add(xg[k][j]);
+                ap.add(xp[k][j]);
+                if (ru) au.add(adam_update(lr_t, xm[k][j], xv[k][j], eps));
+            }
+        au.nf = 0;                                       // (u has no count: its non-finite elements are only left out)
+        ag = tstat_block(ag, ws); ap = tstat_block(ap, ws); au = tstat_block(au, ws);
+        if (threadIdx.x == 0) part[c] = tstat_row(ag, ap, au, flags);
+    }
+}
+__global__ __launch_bounds__(NTHREADS) void tensor_stats_final_kernel(const TStatRow* __restrict__ part, const TStatTable T, const GuardCtl* __restrict__ ctl,
+                                                                      TStatRow* __restrict__ rows) {
+    __shared__ TStatAcc ws[NTHREADS / 64];
+    const int t = blockIdx.x;
+    TStatAcc ag = {}, ap = {}, au = {};
+    for (uint32_t c = T.cpre[t] + threadIdx.x; c < T.cpre[t + 1]; c += NTHREADS) {      // a tensor may have more chunks than the block threads
+        const TStatRow r = part[c];
+        ag.s += r.g_sumsq; ag.mx = fmaxf(ag.mx, r.g_absmax); ag.nf += r.g_nonfinite;
+        ap.s += r.p_sumsq; ap.mx = fmaxf(ap.mx, r.p_absmax); ap.nf += r.p_nonfinite;
+        au.s += r.u_sumsq; au.mx = fmaxf(au.mx, r.u_absmax);
+    }
+    ag = tstat_block(ag, ws); ap = tstat_block(ap, ws); au = tstat_block(au, ws);
+    if (threadIdx.x != 0) return;
+    rows[t] = tstat_row(ag, ap, au, tstat_flags(T, t));
+    if (t == 0) {
+        TStatHead hd = {};
+        hd.applied = !ctl || ctl->apply != 0 ? 1u : 0u;
+        hd.has_update = T.what & TSTAT_U ? 1u : 0u;
+        *reinterpret_cast<TStatHead*>(rows + ADAM_SEG_MAX) = hd;
+    }
+}
+
 // ---- launchers -----------------------------------------------------------------------------------------------------------------------
 // A dense span's n, per pass: Adam and the average get a multiple of 4 (whole groups); the accumulation rounds n up to whole groups (the
 // caller's buffers reach the next multiple of 4: the arena's slots are padded to 64); the sum takes any n.  Nothing is launched for an
@@ -250,5 +361,14 @@ void ema_swap(hipStream_t s, float* p, float* e, int64_t n) {
     const int64_t n4 = n / 4;
     if (n4 <= 0) return;
     hipLaunchKernelGGL(ema_swap_kernel, dim3(ew_blocks(n4)), dim3(NTHREADS), 0, s, p, e, n4);
+}
+
+void tensor_stats(hipStream_t s, const float* p, const float* g, const float* m, const float* v, const TStatTable& T, float eps,
+                  const GuardCtl* ctl, TStatRow* part, TStatRow* rows) {
+    if (T.n <= 0) return;
+    const uint32_t chunks = T.cpre[T.n];
+    // (the grid only spreads the chunks: a partial's slot and its bits are the chunk's.  2048 blocks = 8 per CU of 256)
+    hipLaunchKernelGGL(tensor_stats_chunk_kernel, dim3(chunks < 2048u ? chunks : 2048u), dim3(NTHREADS), 0, s, p, g, m, v, T, eps, ctl, part);
+    hipLaunchKernelGGL(tensor_stats_final_kernel, dim3((unsigned)T.n), dim3(NTHREADS), 0, s, part, T, ctl, rows);
 }
 }  // namespace ctx

@@ -159,9 +159,12 @@ class RcclTrainer:
     torch.distributed group is initialised it is broadcast through that group (any backend)."""
 
     def __init__(self, H=64, W=64, df_dim=64, featsize=1024, max_batch=256, device=0, seed=1234, rank=None, world=None,
-                 unique_id=None, precision=None, grad_clip=None, skip_nonfinite=False, var_list=None, lr_scales=None, ema_decay=None,
-                 accum_steps=1):
+                 unique_id=None, precision=None, grad_clip=None, skip_nonfinite=False, var_list=None, lr_scales=None,
+                 tensor_stats_every=None, ema_decay=None, accum_steps=1):
         """precision: "f32" | "bf16x3" | "fp16x3" | "fp16x3d" (Translator.__init__); None = the translator's default.
+        tensor_stats_every: k >= 1 takes per-tensor statistics of the REDUCED gradient, the parameters and the update on every rank's
+        device behind every k-th Adam update (Translator.set_tensor_stats); replicas hold identical tables, read rank 0's with
+        self.translator.tensor_stats() and write it with trainer.append_tensor_stats_csv (this class keeps no files).  Default: none.
         ema_decay: a decay in [0, 1) keeps an exponential moving average of the parameters on every rank's device (Translator.set_ema
         with the warm-up schedule): replicas hold identical parameters, so their averages are identical too.  Default: none.
         accum_steps: k > 1 -- step() takes a shard of up to `max_batch` rows and runs it in k micro-batches (trainer.micro_slices) with
@@ -178,6 +181,8 @@ class RcclTrainer:
         if world is None:
             world = _world()
         self.rank, self.world = rank, world
+        from .trainer import check_tensor_stats_every
+        tensor_stats_every = check_tensor_stats_every(tensor_stats_every)
         if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError(f"ema_decay = {ema_decay} must lie in [0, 1)")
         self.accum_steps = int(accum_steps)
@@ -201,6 +206,9 @@ class RcclTrainer:
             self.translator.set_lr_scales(lr_scales)
         if ema_decay is not None:
             self.translator.set_ema(float(ema_decay))
+        self.tensor_stats_every = tensor_stats_every
+        if tensor_stats_every is not None:
+            self.translator.set_tensor_stats(tensor_stats_every)
 
     def step(self, src, ctx, tgt, lr=1e-4, scalars=False):
         """src / ctx / tgt: contiguous float32 cuda tensors [B,H,W,3] of this rank's shard (ready on the device: the library's

@@ -114,13 +114,35 @@ def on_u8_lattice(vdata):
     return k.astype(np.uint8), True
 
 
+TENSOR_STATS_COLUMNS = ("itr", "step", "applied", "name", "trainable", "g_norm", "g_rms", "g_absmax", "g_nonfinite", "p_norm", "p_absmax",
+                        "p_nonfinite", "u_norm", "u_absmax", "update_ratio")
+
+
+def check_tensor_stats_every(every):
+    """The trainers' tensor_stats_every keyword: None, or an int >= 1 (ValueError otherwise, before anything touches a device)."""
+    if every is None:
+        return None
+    if isinstance(every, bool) or int(every) != every or int(every) < 1:
+        raise ValueError(f"tensor_stats_every = {every} must be an integer >= 1")
+    return int(every)
+
+
+def append_tensor_stats_csv(path, itr, stats):
+    """One line per tensor of a Translator.tensor_stats() table, in param_info order, appended to `path` (TENSOR_STATS_COLUMNS)."""
+    with open(path, "a", newline="") as f:
+        w = csv.writer(f)
+        for name, t in stats["tensors"].items():
+            w.writerow([itr, stats["step"], int(stats["applied"]), name, int(t["trainable"])] + [repr(t[k]) for k in TENSOR_STATS_COLUMNS[5:]])
+
+
 class ModelTrainer:
     MODELS = {"ContextSkipNew": "skipnew", "ContextAEReal": "real", "ContextAEInception": "inception2"}
 
     def __init__(self, idims, nvideos, ntrain, batch_size, model, nitr, save_every, nlen, nskip, rescale=True, inception=False,
                  strides=None, kernels=None, filters=None, *, vdata=None, basedir="model/", device=0, seed=0, translator=None,
                  precision=None, log=print, rank=0, world=1, dp_unique_id=None, videos=None, device_resize=False,
-                 grad_clip=None, skip_nonfinite=False, var_list=None, lr_scales=None, ema_decay=None, ema_eval=False, accum_steps=1):
+                 grad_clip=None, skip_nonfinite=False, var_list=None, lr_scales=None, tensor_stats_every=None, ema_decay=None, ema_eval=False,
+                 accum_steps=1):
         """The reference's 14 positional arguments (train_script.py:29-30; the launchers omit the last five, SURVEY.md 3.4-b,
         hence the defaults), then: vdata (array or .npy path of the demo tensor), basedir (logger._snapshot_dir), device,
         seed of the parameter initialiser, an optional ready-made translator (tests), the arithmetic (precision: "f32" | "bf16x3" | "fp16x3" | "fp16x3d",
@@ -136,6 +158,10 @@ class ModelTrainer:
         var_list / lr_scales: which variables Adam trains (`minimize(loss, var_list=...)`, train_script.py:126-128).  var_list: fnmatch
         patterns on the TF variable names ("deconv/*") -- Translator.set_trainable, everything else is frozen; lr_scales: {pattern:
         scale} -- Translator.set_lr_scales.  One of the two; set once before the first step.  Defaults: every variable, as before.
+        tensor_stats_every: k >= 1 takes per-tensor gradient, parameter and update statistics on the device behind every k-th Adam
+        update (Translator.set_tensor_stats, two extra launches then) and appends one line per tensor to `<basedir>tensor_stats.csv`
+        (TENSOR_STATS_COLUMNS, no header line; rank 0 only), and with skip_nonfinite the log line of a skipped step names the tensors
+        whose gradient held non-finite elements.  Default: none; logs, CSV and checkpoints as before.
         ema_decay: a decay in [0, 1) keeps an exponential moving average of the parameters on the device (Translator.set_ema with the
         warm-up schedule, one extra launch per Adam update) and writes, at every `save_every`, a second file `model_ema_<itr>` beside
         the usual checkpoint: the AVERAGED weights under the variable names (Translator.save(weights="ema")), which the reward hook
@@ -167,6 +193,7 @@ class ModelTrainer:
             raise ValueError(f"rank {rank} / world {world}")
         if self.world > 1 and batch_size % self.world:
             raise ValueError(f"batch_size {batch_size} (the GLOBAL batch) must be a multiple of world = {world}")
+        self.tensor_stats_every = check_tensor_stats_every(tensor_stats_every)
         if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError(f"ema_decay = {ema_decay} must lie in [0, 1)")
         if ema_eval and ema_decay is None:
@@ -344,17 +371,29 @@ class ModelTrainer:
             core.set_lr_scales(self.lr_scales)
         if self.ema_decay is not None:
             core.set_ema(self.ema_decay)
+        if self.tensor_stats_every is not None:
+            core.set_tensor_stats(self.tensor_stats_every)
+        stats_step = None                                      # the Adam step of the last table written
         skipped = 0
         rows = []
         for itr in range(1, self.nitr):
             choicesrc = np.random.choice(ntrain, B)
             choicetgt = np.random.choice(ntrain, B)
             sc = train_step(choicesrc, choicetgt, want_err=itr % 4 == 0)
+            if self.tensor_stats_every is not None and rank == 0 and itr % self.tensor_stats_every == 0:
+                st = core.tensor_stats()                       # (the table the step left behind its update; an on-demand one has no update)
+                if st["has_update"] and st["step"] != stats_step:
+                    stats_step = st["step"]
+                    append_tensor_stats_csv(basedir + "tensor_stats.csv", itr, st)
             if guarded and self.skip_nonfinite:                # (the step has synchronised for its scalars: the counters are final)
                 now = core.guard_stats()["steps_skipped"]
                 if now > skipped:
                     skipped = now
-                    log("%s skipped: non-finite gradient, parameters and Adam moments unchanged (%s so far)" % (itr, skipped))
+                    msg = "%s skipped: non-finite gradient, parameters and Adam moments unchanged (%s so far)" % (itr, skipped)
+                    if self.tensor_stats_every is not None and rank == 0:      # the gradient arena still holds the offending gradient
+                        bad = [n for n, t in core.tensor_stats(compute="grads")["tensors"].items() if t["g_nonfinite"] > 0]
+                        msg += "; non-finite in: " + (", ".join(bad) if bad else "none of the trainable tensors")
+                    log(msg)
             if itr % 4 == 0:
                 if accum:                                      # summed over the micro-batches on the device
                     err = sc["nn_err"]

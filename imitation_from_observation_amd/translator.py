@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import math
 import os
 from collections import OrderedDict
 
@@ -804,6 +805,48 @@ class Translator:
             yield self
         finally:
             self.ema_swap()
+
+    # ------------------------------------------------------------------ per-tensor statistics (include/ctxtrans.h: ctx_tensor_stats_*)
+    _TSTAT_WHAT = {"params": _lib.CTX_TSTAT_PARAMS, "grads": _lib.CTX_TSTAT_GRADS, "both": _lib.CTX_TSTAT_PARAMS | _lib.CTX_TSTAT_GRADS}
+
+    def set_tensor_stats(self, every=1):
+        """Take a table of per-tensor gradient, parameter and update statistics on the device behind every `every`-th Adam update of
+        this handle (two launches, nothing synchronised; read it with tensor_stats()).  Off by default."""
+        if int(every) < 1:
+            raise ValueError("every must be >= 1")
+        self._ck(self._lib.ctx_tensor_stats_enable(self._h, int(every)))
+
+    def tensor_stats_off(self):
+        """Stop taking tables and free their buffers: the handle then behaves as if set_tensor_stats had never been called."""
+        self._ck(self._lib.ctx_tensor_stats_disable(self._h))
+
+    def tensor_stats(self, compute=None):
+        """The last table taken, as {"step", "applied", "has_update", "tensors": {name: {...}}}.  compute = "params" | "grads" | "both"
+        first takes one of the arena as it stands (no update fields: has_update is False); None reads the one the last period left
+        (CtxError CTX_E_STATE when there is none yet).  Per tensor: g_norm, p_norm, u_norm (sqrt, in float64, of the device's float64
+        sums over the finite elements), g_rms over the tensor's element count, update_ratio = u_norm / p_norm, g_absmax, p_absmax,
+        u_absmax, g_nonfinite, p_nonfinite, trainable (False: frozen -- its gradient and update fields are zero, not read).
+        `step` is the Adam step count the table was taken at, `applied` False for a step the guard skipped.  Synchronises."""
+        if compute is not None:
+            if compute not in self._TSTAT_WHAT:
+                raise ValueError('compute must be None, "params", "grads" or "both"')
+            self._ck(self._lib.ctx_tensor_stats_compute(self._h, self._TSTAT_WHAT[compute]))
+        info = self.param_info()
+        rows = (_lib.CtxTensorStat * len(info))()
+        n, step, applied, has_u = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int(), ctypes.c_int()
+        self._ck(self._lib.ctx_tensor_stats_get(self._h, rows, len(info), ctypes.byref(n), ctypes.byref(step), ctypes.byref(applied),
+                                                ctypes.byref(has_u)))
+        tensors = OrderedDict()
+        for (name, shape, _), r in zip(info, rows):
+            count = int(np.prod(shape))
+            g_norm, p_norm, u_norm = math.sqrt(r.g_sumsq), math.sqrt(r.p_sumsq), math.sqrt(r.u_sumsq)
+            tensors[name] = dict(
+                g_norm=g_norm, p_norm=p_norm, u_norm=u_norm, g_rms=math.sqrt(r.g_sumsq / count) if count else 0.0,
+                update_ratio=u_norm / p_norm if p_norm > 0.0 else 0.0,
+                g_absmax=float(r.g_absmax), p_absmax=float(r.p_absmax), u_absmax=float(r.u_absmax),
+                g_nonfinite=int(r.g_nonfinite), p_nonfinite=int(r.p_nonfinite), trainable=bool(r.flags & _lib.CTX_TSTAT_F_TRAINABLE),
+                g_sumsq=float(r.g_sumsq), p_sumsq=float(r.p_sumsq), u_sumsq=float(r.u_sumsq), flags=int(r.flags))
+        return dict(step=int(step.value), applied=bool(applied.value), has_update=bool(has_u.value), tensors=tensors)
 
     # ------------------------------------------------------------------ guarded Adam (include/ctxtrans.h: ctx_set_grad_guard)
     def set_grad_guard(self, clip_norm=None, skip_nonfinite=True):

@@ -52,7 +52,7 @@ extern "C" {
                                ctx_resize_u8_dev / _v, ctx_cnn_*_dev_u8, ctx_disc_stream / _data_begin / _reward_paths_dev;
                                ctx_reconstruct / _f32 / _dev, ctx_reward_costs_recon / _dev;
                                ctx_set_grad_guard, ctx_grad_norm, ctx_grad_guard_stats; ctx_accum_* / ctx_dp_accum_*;
-                               ctx_ema_*, ctx_get_ema, ctx_set_ema */
+                               ctx_ema_*, ctx_get_ema, ctx_set_ema; ctx_tensor_stat, ctx_tensor_stats_* */
 
 enum {
     CTX_OK = 0,
@@ -662,6 +662,54 @@ int ctx_ema_swap(ctx_handle* h);
 int ctx_ema_state(ctx_handle* h, int* enabled, int* swapped, float* decay, int64_t* updates);
 int ctx_get_ema(ctx_handle* h, float* out, int64_t n, int64_t* updates);
 int ctx_set_ema(ctx_handle* h, const float* in, int64_t n, int64_t updates);
+
+/* ---- per-tensor gradient, parameter and update statistics, taken on the device (new here) --------------------------------------------
+ * One row per tensor of ctx_param_info, in its order, from a deterministic two-stage f64 reduction over the arena:
+ * the sums of squares of gradient g, parameter p and Adam update u = lr_t m / (sqrtf(v) + eps) in f64, their largest magnitudes in
+ * f32 -- all over the FINITE elements only -- and the counts of non-finite elements of g and of p.  The bits of a row depend neither
+ * on the device nor on which other tensors are frozen.  Off by default: a handle that never enables it runs exactly the launches of
+ * one that has never heard of it.
+ *   ctx_tensor_stats_enable(h, every)   every >= 1, else CTX_E_INVALID.  From here on every `every`-th Adam update of the handle (the
+ *                                       updates listed for ctx_ema_* above; counted by the Adam step count) is followed by one
+ *                                       table: two launches behind the update and behind the average's, nothing synchronised.  g is
+ *                                       the gradient that update consumed (reduced on a ctx_dp_* step, the folded sum under an
+ *                                       accumulation), p the parameters and u the update as the step left them.  A step the guard
+ *                                       skipped has u exactly 0 and reports applied = 0.  Allocates the library's own buffers
+ *                                       (ctx_arena_bytes is unchanged); a later call changes only the period.
+ *   ctx_tensor_stats_disable(h)         stops the automatic form and frees the buffers and the table taken; a handle without them
+ *                                       is left as it is (CTX_OK).
+ *   ctx_tensor_stats_compute(h, what)   a table of the arena as it stands, what = CTX_TSTAT_PARAMS | CTX_TSTAT_GRADS (anything else,
+ *                                       or 0: CTX_E_INVALID): fields not asked for are zero, so are the u fields, has_update is 0 and
+ *                                       applied 1.  CTX_TSTAT_GRADS before any backward: CTX_E_STATE.  Reads only, so it is allowed
+ *                                       while the averaged weights are swapped in -- p is then the AVERAGE (the arena holds it) --
+ *                                       and while an accumulation is open -- g is then the LAST micro-batch's gradient alone, the
+ *                                       sum of the earlier ones lies beside the arena.  Works without ctx_tensor_stats_enable.
+ *                                       Asynchronous.
+ *   ctx_tensor_stats_get(h, rows, cap, &n, &adam_step, &applied, &has_update)   synchronises and copies the last table taken: n =
+ *                                       ctx_param_count rows (cap < n: CTX_E_INVALID), the Adam step count it was taken at, whether
+ *                                       that step was applied (0: the guard skipped it) and whether the u fields were computed.
+ *                                       Every out-pointer but rows is nullable.  CTX_E_STATE when no table has been taken yet.
+ *   - mask (ctx_set_param_lr_scale): a frozen tensor's gradient and moments are NOT read (a pruned backward never wrote that
+ *     gradient): its g and u fields are zero and flag bit 0 is clear; its p fields are filled.  u uses the tensor's own lr_t.
+ *   - floats between two tensors and past the end of the last one are never read.
+ * A NULL handle is CTX_E_INVALID and nothing is written through the out-pointers. */
+typedef struct ctx_tensor_stat {
+    double g_sumsq, p_sumsq, u_sumsq;
+    float g_absmax, p_absmax, u_absmax;
+    uint32_t g_nonfinite, p_nonfinite;
+    uint32_t flags;       /* CTX_TSTAT_F_* */
+} ctx_tensor_stat;        /* 48 bytes */
+enum { CTX_TSTAT_PARAMS = 1, CTX_TSTAT_GRADS = 2 };
+enum {
+    CTX_TSTAT_F_TRAINABLE = 1,   /* bit 0: the tensor is trainable -- its g and u fields are valid (where the table took them) */
+    CTX_TSTAT_F_GRADS = 2,       /* the table took gradients and this tensor's were read */
+    CTX_TSTAT_F_UPDATE = 4,      /* ... the update, from this tensor's moments */
+    CTX_TSTAT_F_PARAMS = 8       /* the table took parameters */
+};
+int ctx_tensor_stats_enable(ctx_handle* h, int every);
+int ctx_tensor_stats_disable(ctx_handle* h);
+int ctx_tensor_stats_compute(ctx_handle* h, int what);
+int ctx_tensor_stats_get(ctx_handle* h, ctx_tensor_stat* rows, int cap, int* n, int64_t* adam_step, int* applied, int* has_update);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* One entry per launch group of a train step (a layer's forward, input gradient, filter gradient,
