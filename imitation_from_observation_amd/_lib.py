@@ -148,6 +148,8 @@ SIGNATURES = {
     "ctx_grad_guard_stats": (_c.c_int, [_P, _c.POINTER(_c.c_double), _F, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
     "ctx_set_param_lr_scale": (_c.c_int, [_P, _F, _c.c_int]),
     "ctx_get_param_lr_scale": (_c.c_int, [_P, _F, _c.c_int]),
+    "ctx_set_param_weight_decay": (_c.c_int, [_P, _F, _c.c_int]),
+    "ctx_get_param_weight_decay": (_c.c_int, [_P, _F, _c.c_int]),
     "ctx_dev_scalars": (_c.c_int, [_P, _F]),
     "ctx_dev_params": (_P, [_P]),
     "ctx_dev_grads": (_P, [_P]),

@@ -238,26 +238,39 @@ int ctx_get_grads(ctx_handle* h, float* flat, size_t n) {
 }
 
 // ---- training a subset of the parameters (include/ctxtrans.h; the plan and the launches: ctx_engine.cpp plan_mask, adam_end) ----------
-int ctx_set_param_lr_scale(ctx_handle* h, const float* scale, int n) {
-    if (!h) return CTX_E_INVALID;
-    if (!scale) { h->lr_scale.clear(); plan_mask(h); return CTX_OK; }
+// one non-negative finite value per tensor into `dst`, which stays empty when every value is `neutral` (or v == NULL): a handle whose
+// launches are those of one that never called; then the plan again.  `what`: the value's name in messages.
+static int set_per_tensor(ctx_handle* h, std::vector<float>& dst, const float* v, int n, float neutral, const char* what) {
+    if (!v) { dst.clear(); plan_mask(h); return CTX_OK; }
     const int np = (int)h->params.size();
-    if (n != np) return fail(h, CTX_E_INVALID, "expected %d scales (ctx_param_count), got %d", np, n);
+    if (n != np) return fail(h, CTX_E_INVALID, "expected %d %ss (ctx_param_count), got %d", np, what, n);
     if (np > ADAM_SEG_MAX || h->Ppad >= (1ll << 32)) return fail(h, CTX_E_INVALID, "the segmented Adam kernel holds %d tensors of an arena below 2^32 floats", ADAM_SEG_MAX);
-    bool ones = true;
+    bool all_neutral = true;
     for (int i = 0; i < n; ++i) {
-        if (!(scale[i] >= 0.f) || !std::isfinite(scale[i])) return fail(h, CTX_E_INVALID, "scale[%d] of %s must be finite and >= 0", i, h->params[i].name.c_str());
-        ones = ones && scale[i] == 1.f;
+        if (!(v[i] >= 0.f) || !std::isfinite(v[i])) return fail(h, CTX_E_INVALID, "%s[%d] of %s must be finite and >= 0", what, i, h->params[i].name.c_str());
+        all_neutral = all_neutral && v[i] == neutral;
     }
-    if (ones) h->lr_scale.clear();       // every tensor at 1 IS no mask: the launches of a handle that never heard of one
-    else h->lr_scale.assign(scale, scale + n);
+    if (all_neutral) dst.clear();
+    else dst.assign(v, v + n);
     plan_mask(h);
     return CTX_OK;
 }
+// (every tensor at 1 IS no mask)
+int ctx_set_param_lr_scale(ctx_handle* h, const float* scale, int n) { return h ? set_per_tensor(h, h->lr_scale, scale, n, 1.f, "scale") : CTX_E_INVALID; }
 
 int ctx_get_param_lr_scale(const ctx_handle* h, float* scale, int n) {
     if (!h || !scale || n != (int)h->params.size()) return CTX_E_INVALID;
     for (int i = 0; i < n; ++i) scale[i] = h->lr_scale.empty() ? 1.f : h->lr_scale[i];
+    return CTX_OK;
+}
+
+// ---- decoupled weight decay (include/ctxtrans.h; the runs and the launch: ctx_engine.cpp plan_mask, adam_begin, adam_launch) -----------
+// (every tensor at 0 IS no decay)
+int ctx_set_param_weight_decay(ctx_handle* h, const float* decay, int n) { return h ? set_per_tensor(h, h->weight_decay, decay, n, 0.f, "decay") : CTX_E_INVALID; }
+
+int ctx_get_param_weight_decay(const ctx_handle* h, float* decay, int n) {
+    if (!h || !decay || n != (int)h->params.size()) return CTX_E_INVALID;
+    for (int i = 0; i < n; ++i) decay[i] = h->weight_decay.empty() ? 0.f : h->weight_decay[i];
     return CTX_OK;
 }
 

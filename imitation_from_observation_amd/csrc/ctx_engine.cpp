@@ -324,10 +324,12 @@ struct Side {
 // pointers the pass gets.  Under a mask n is the end of the last tensor, as the guard's sum wants it.
 static int64_t grad_end(const ctx_handle* h) { return h->gen ? h->gen->pend : h->P; }       // the gradient arena a backward writes: [0, here)
 static Span span_of(const ctx_handle* h, int64_t n) { return masked(h) ? Span{&h->segs, grad_end(h), 0.f} : Span{nullptr, n, h->adam_lr_t}; }
-// [first, end): a dense range over offset pointers; a masked handle's one launch (first == 0, adam_end) covers its runs instead
+// [first, end): a dense range over offset pointers; a masked handle's one launch (first == 0, adam_end) covers its runs instead, and
+// so does a decayed handle's -- the runs of wd_segs, which only this launch ever sees: every other pass keeps span_of's
 void adam_launch(ctx_handle* h, hipStream_t s, int64_t first, int64_t end) {
     float *p = h->arena + first, *g = p + h->Ppad, *m = g + h->Ppad, *v = m + h->Ppad;
-    adam(s, p, g, m, v, span_of(h, end - first), 0.9f, 0.999f, 1e-8f, guard_on(h) ? h->guard_ctl : nullptr);   // (ctx_set_grad_guard, below)
+    const Span sp = decayed(h) ? Span{&h->wd_segs, grad_end(h), 0.f, true} : span_of(h, end - first);
+    adam(s, p, g, m, v, sp, 0.9f, 0.999f, 1e-8f, guard_on(h) ? h->guard_ctl : nullptr);   // (ctx_set_grad_guard, below)
 }
 // Adam's rate at update adam_t for the learning rate lr_
 static float adam_lr_t_of(const ctx_handle* h, float lr_) {
@@ -343,13 +345,20 @@ void adam_begin(ctx_handle* h, float lr) {
     // under a mask every run has its own: the f32 product lr * scale through the same expression, so a tensor at scale s steps exactly
     // as an unmasked handle steps it at the learning rate float(lr * s)
     for (int s = 0; s < h->segs.n; ++s) { const float lr_s = lr * h->seg_scale[s]; h->segs.lr_t[s] = lr_t_of(lr_s); }
+    // decoupled weight decay (ctx_set_param_weight_decay): the run's decay per step is the f32 product of that same lr_s -- the RAW
+    // rate, not the bias-corrected lr_t (torch.optim.AdamW's convention) -- and its lambda
+    for (int s = 0; s < h->wd_segs.n; ++s) {
+        const float lr_s = lr * h->wd_scale[s];
+        h->wd_segs.lr_t[s] = lr_t_of(lr_s);
+        h->wd_segs.wd_t[s] = lr_s * h->wd_lambda[s];
+    }
     h->adam_done.clear();
     h->pack.version++;               // the parameters change in this step: packed filters are stale from here on
     // (only where the update is worth hiding: ContextAEReal's 1.2 M parameters are a 7 us update, and the slices' events and queue hops
     // among its 5-30 us launches cost 0.4 ms of a 2.6 ms step -- bench.py's secondary leg against forward_backward + adam on one box: 3.00 -> 2.58 ms, round 5)
     // (and never under a guard: the clip factor and the skip decision exist only after the last gradient is written; nor under a
-    // mask: its update is ONE launch over the trainable runs at the end of the step)
-    h->adam_early_on = env_on && h->adam_stream && use_lanes(h) && h->P >= (4ll << 20) && !guard_on(h) && !masked(h);
+    // mask or a weight decay: the update is ONE launch over the trainable runs at the end of the step)
+    h->adam_early_on = env_on && h->adam_stream && use_lanes(h) && h->P >= (4ll << 20) && !guard_on(h) && !masked(h) && !decayed(h);
 }
 
 // ---- training a subset of the parameters (ctx_set_param_lr_scale) ------------------------------------------------------------------
@@ -371,30 +380,42 @@ int tensor_spans(ctx_handle* h) {
     return CTX_OK;
 }
 
-// From h->lr_scale: the trainable runs of the optimizer passes (adjacent tensors of equal scale are one run) and which launch groups
-// a plain backward keeps (Prune, ctx_internal.h).
-void plan_mask(ctx_handle* h) {
-    h->segs = AdamSegs{};
-    h->prune = Prune{};
-    h->prof_entries.clear();         // ctx_profile_step names its entries at their first run: another mask is another sequence
-    h->prof_ms.clear();
-    tstat_plan(h);                   // (which tensors the statistics read g, m and v of)
-    if (!masked(h)) return;
-    AdamSegs& T = h->segs;
+// The trainable tensors as runs: a run is a maximal stretch of adjacent tensors of equal (scale, lambda) and a non-zero scale.  scale /
+// lambda: per tensor, nullptr = 1 / 0 everywhere; seg_scale / seg_lambda (nullable): per run.
+static void plan_runs(const ctx_handle* h, AdamSegs& T, const float* scale, const float* lambda, float* seg_scale, float* seg_lambda) {
+    T = AdamSegs{};
     uint32_t total = 0;
     int64_t last_end = -1;
+    float sc0 = 0.f, wd0 = 0.f;      // of the run being built
     for (size_t i = 0; i < h->params.size(); ++i) {
-        const float sc = h->lr_scale[i];
+        const float sc = scale ? scale[i] : 1.f, wd = lambda ? lambda[i] : 0.f;
         if (sc == 0.f) continue;
         const int64_t g0 = h->span[i].first / 4, g1 = (h->span[i].second + 3) / 4;
-        if (!(T.n && last_end == g0 && h->seg_scale[T.n - 1] == sc)) {
-            T.first[T.n] = (uint32_t)g0; T.pre[T.n] = total; h->seg_scale[T.n] = sc;
+        if (!(T.n && last_end == g0 && sc0 == sc && wd0 == wd)) {
+            T.first[T.n] = (uint32_t)g0; T.pre[T.n] = total; seg_scale[T.n] = sc0 = sc;
+            if (seg_lambda) seg_lambda[T.n] = wd;
+            wd0 = wd;
             ++T.n;
         }
         total += (uint32_t)(g1 - g0);
         T.pre[T.n] = total;
         last_end = g1;
     }
+}
+// From h->lr_scale: the trainable runs of the optimizer passes (adjacent tensors of equal scale are one run) and which launch groups
+// a plain backward keeps (Prune, ctx_internal.h).  From h->weight_decay and h->lr_scale: the runs of the decayed Adam launch, wd_segs --
+// the mask's runs cut again where lambda changes.  Decay does not make a handle masked: with no mask wd_segs covers every tensor at
+// scale 1, and the backward, the guard's sum, the accumulation and the average keep their dense spans.
+void plan_mask(ctx_handle* h) {
+    h->segs = AdamSegs{};
+    h->wd_segs = AdamSegs{};
+    h->prune = Prune{};
+    h->prof_entries.clear();         // ctx_profile_step names its entries at their first run: another mask is another sequence
+    h->prof_ms.clear();
+    tstat_plan(h);                   // (which tensors the statistics read g, m and v of)
+    if (decayed(h)) plan_runs(h, h->wd_segs, masked(h) ? h->lr_scale.data() : nullptr, h->weight_decay.data(), h->wd_scale, h->wd_lambda);
+    if (!masked(h)) return;
+    plan_runs(h, h->segs, h->lr_scale.data(), nullptr, h->seg_scale, nullptr);
     Prune& q = h->prune;
     q.on = true;
     auto tr = [&](const std::string& name) {

@@ -263,6 +263,12 @@ struct ctx_handle {
     AdamSegs segs;
     float seg_scale[ADAM_SEG_MAX] = {};
     ctxi::Prune prune;
+    // decoupled weight decay (ctx_set_param_weight_decay; weight_decay empty = off: every launch is the one without this feature).
+    // wd_segs = the runs of the ONE decayed Adam launch, equal (scale, lambda) per run (wd_scale, wd_lambda), lr_t and wd_t written by
+    // adam_begin.  No other pass reads it: decay does not make a handle masked.
+    std::vector<float> weight_decay;
+    AdamSegs wd_segs;
+    float wd_scale[ADAM_SEG_MAX] = {}, wd_lambda[ADAM_SEG_MAX] = {};
     // gradient accumulation (ctx_accum_*): `accum` = the sum of the micro-batches' gradients so far, Ppad floats BESIDE the arena
     // (allocated at the first ctx_accum_begin); accum_slots = ACCUM_SLOTS doubles, the scalars' sums and the nn_err sum.  Open while
     // accum_total > 0: accum_share = the rows this handle adds (total / world under ctx_dp_init), accum_rows of them seen in
@@ -356,8 +362,9 @@ inline bool guard_on(const ctx_handle* h) { return h->guard_clip > 0.f || h->gua
 int guard_alloc(ctx_handle* h);
 void guard_enqueue(ctx_handle* h, int which, float clip, bool skip, bool count);   // norm of the gradient arena -> guard_ctl[which]
 inline bool masked(const ctx_handle* h) { return !h->lr_scale.empty(); }
+inline bool decayed(const ctx_handle* h) { return !h->weight_decay.empty(); }
 int tensor_spans(ctx_handle* h);   // fill h->span at create; CTX_E_INVALID if a tensor does not start on a 16-byte group
-void plan_mask(ctx_handle* h);     // h->lr_scale -> h->segs / seg_scale / prune
+void plan_mask(ctx_handle* h);     // h->lr_scale -> h->segs / seg_scale / prune; with h->weight_decay -> h->wd_segs / wd_scale / wd_lambda
 bool d_h4_direct(const ctx_handle* h, int c1, int c2, int hs, int ws, int stride);
 void join(ctx_handle* h, int lane);
 void fork(ctx_handle* h, int lane);

@@ -260,7 +260,8 @@ void lrelu_mask(hipStream_t s, float* g, const float* act, int64_t n);
 
 // ---- the optimizer's passes over the arena (optim.hip) ----------------------------------------------------------------------------
 // A pass under an lr-scale mask (ctx_set_param_lr_scale) covers a SUBSET of the arena: the trainable tensors as runs of 16-byte groups
-// in arena order, each with its own lr_t.  The table is a kernel argument (488 B), so a step's values reach the device with the launch
+// in arena order, each with its own lr_t and -- read by the decayed Adam alone (ctx_set_param_weight_decay), whose table cuts the runs
+// where the decay changes too -- its own wd_t.  The table is a kernel argument (648 B), so a step's values reach the device with the launch
 // itself.  A kernel numbers the trainable groups 0 .. pre[n) and finds group c in run s with pre[s] <= c < pre[s + 1] at arena group
 // first[s] + c - pre[s]: what lies between the runs (frozen tensors) is neither read nor written.
 constexpr int ADAM_SEG_MAX = 40;     // >= the tensors of any model (38)
@@ -269,12 +270,14 @@ struct AdamSegs {
     uint32_t pre[ADAM_SEG_MAX + 1] = {}; // trainable groups in front of run s; pre[n] = all of them
     uint32_t first[ADAM_SEG_MAX] = {};   // first arena group of run s
     float lr_t[ADAM_SEG_MAX] = {};
+    float wd_t[ADAM_SEG_MAX] = {};       // decoupled weight decay per step: lr * scale * lambda of the run, 0 = none
 };
 // What a pass covers: the runs of a mask, or (runs == nullptr) the floats [0, n) of the pointers it gets -- n as each pass documents.
 struct Span {
     const AdamSegs* runs;
     int64_t n;                           // with runs: the end of the last tensor, which only grad_guard reads
     float lr_t;                          // dense Adam's; a run has its own
+    bool decay = false;                  // Adam only, runs only: apply the runs' wd_t
 };
 inline unsigned ew_blocks(int64_t work) {    // grid of a grid-strided elementwise kernel
     int64_t b = (work + NTHREADS - 1) / NTHREADS;
@@ -282,7 +285,8 @@ inline unsigned ew_blocks(int64_t work) {    // grid of a grid-strided elementwi
 }
 
 // TF Adam (scripts/train_script.py:124-128), lr_t precomputed on the host, over [0, n) (n a multiple of 4) or the runs: one launch
-// whatever the mask.  ctl (nullable, ctx_set_grad_guard): on g * ctl->factor, or nothing at all when ctl->apply == 0.
+// whatever the mask.  ctl (nullable, ctx_set_grad_guard): on g * ctl->factor, or nothing at all when ctl->apply == 0.  sp.decay: p is
+// first shrunk by the run's wd_t, p' = fmaf(-wd_t, p, p) - update (a run at wd_t == 0 exactly as without).
 // grad_guard: the sum of g^2 over [0, n) (any n) or the runs -- of a group that reaches past n only the floats in front of it -- in f64
 // through `part` (GUARD_BLOCKS doubles), then {norm, factor, apply} and -- `count` -- the counters into *ctl.
 constexpr int GUARD_BLOCKS = 1024;   // grid of the sum: a constant, so that the order of the sum (the bits of the norm) is the same on every device

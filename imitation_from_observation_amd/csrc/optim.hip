@@ -1,25 +1,31 @@
 // optim.hip -- the optimizer's elementwise passes over the flat arena: Adam, the guard's sum of squares, gradient accumulation, the
 // parameter average and the per-tensor statistics.  Each has ONE body in ONE kernel template, instantiated over the two walks below.  Launchers: launch.h (Span).
 #include "launch.h"
+#include <type_traits>
 namespace ctx {
 typedef float f4 __attribute__((ext_vector_type(4)));
 
 // ---- the walk ------------------------------------------------------------------------------------------------------------------------
 // A kernel numbers the 16-byte groups it visits 0 .. total grid-strided; at(c) is the arena float offset of group c, lr_t() the Adam rate
-// of the group the last at() returned.  Two walks, named by their kernel argument:
+// and wd_t() the decay rate of the group the last at() returned.  Two walks, named by their kernel argument:
 //   DenseGroups  groups 0 .. n4 of the pointers the kernel is launched on: a few scalars, a 64-bit index, no LDS.
 //   AdamSegs     the TRAINABLE groups 0 .. pre[n) of a mask (launch.h): a frozen tensor costs neither traffic nor iterations.  A thread's
 //                c only grows, so it finds c's run by stepping `run` forward from its last group's (at most n steps per thread in all).
 //                The table is copied to LDS once per block: lanes of a wave that straddles two runs index it apart.  CUT: the last
-//                group may reach past the end of the last tensor (only the sum cares: it reads that group masked).
+//                group may reach past the end of the last tensor (only the sum cares: it reads that group masked).  WD: the pass
+//                reads wd_t() -- the decayed Adam alone, which says so with the tag WithDecay; every other pass (NoDecay, the
+//                default) is built without the copy of that column.
 struct DenseGroups { int64_t n4; float lr_t; };
-struct SegTable { uint32_t pre[ADAM_SEG_MAX + 1], first[ADAM_SEG_MAX]; float lr_t[ADAM_SEG_MAX]; };
-__device__ inline void seg_table_load(SegTable& L, const AdamSegs& T) {
+struct SegTable { uint32_t pre[ADAM_SEG_MAX + 1], first[ADAM_SEG_MAX]; float lr_t[ADAM_SEG_MAX], wd_t[ADAM_SEG_MAX]; };
+struct NoDecay {};
+struct WithDecay {};                                     // Walk<A>(span, WithDecay{}): wd_t() will be read
+template <bool WD> __device__ inline void seg_table_load(SegTable& L, const AdamSegs& T) {
     for (int i = threadIdx.x; i < ADAM_SEG_MAX; i += NTHREADS) {
         // (past the runs in use: pre = the total, so no search ever steps beyond run n - 1)
         L.pre[i] = i <= T.n ? T.pre[i] : T.pre[T.n];
         L.first[i] = T.first[i];
         L.lr_t[i] = T.lr_t[i];
+        if (WD) L.wd_t[i] = T.wd_t[i];
     }
     if (threadIdx.x == 0) L.pre[ADAM_SEG_MAX] = T.pre[T.n];
     __syncthreads();
@@ -28,22 +34,25 @@ template <class A> struct Walk;
 template <> struct Walk<DenseGroups> {
     typedef int64_t index; static constexpr bool CUT = false;
     const index total; const float lr;
-    __device__ Walk(const DenseGroups& a) : total(a.n4), lr(a.lr_t) {}
+    __device__ Walk(const DenseGroups& a, NoDecay = {}) : total(a.n4), lr(a.lr_t) {}
     __device__ int64_t at(index c) const { return c * 4; }
     __device__ float lr_t() const { return lr; }
+    __device__ float wd_t() const { return 0.f; }        // (a dense walk has no per-tensor value: no decayed kernel is built over it)
 };
 template <> struct Walk<AdamSegs> {
     typedef uint32_t index; static constexpr bool CUT = true;
     SegTable& L;
     index total; int run = 0;
     static __device__ SegTable& table() { __shared__ SegTable L; return L; }
-    __device__ Walk(const AdamSegs& T) : L(table()) { seg_table_load(L, T); total = L.pre[ADAM_SEG_MAX]; }
+    __device__ Walk(const AdamSegs& T, NoDecay = {}) : L(table()) { seg_table_load<false>(L, T); total = L.pre[ADAM_SEG_MAX]; }
+    __device__ Walk(const AdamSegs& T, WithDecay) : L(table()) { seg_table_load<true>(L, T); total = L.pre[ADAM_SEG_MAX]; }
     __device__ int64_t at(index c) {                     // calls with growing c
         --run;                                           // "while c is past this run, ++run" as the bottom-tested loop a compiler makes of
         do ++run; while (c >= L.pre[run + 1]);           // it inside a kernel's own loop: one LDS read where the run does not change
         return ((int64_t)L.first[run] + (c - L.pre[run])) * 4;
     }
     __device__ float lr_t() const { return L.lr_t[run]; }
+    __device__ float wd_t() const { return L.wd_t[run]; }
 };
 // a thread's groups: for (auto c = grid_first<A>(); c < w.total; c += grid_step<A>())
 template <class A> __device__ __forceinline__ typename Walk<A>::index grid_first() { return (typename Walk<A>::index)blockIdx.x * NTHREADS + threadIdx.x; }
@@ -55,19 +64,23 @@ template <class A> __device__ __forceinline__ typename Walk<A>::index grid_step(
 // updated exactly as an unmasked handle updates it at the learning rate lr * s.  The contractions  b1 m + c1 g  and  b2 v + c2 (g g)  are
 // spelled out (ISA: v_pk_mul c1 g, v_pk_fma b1 m; v_pk_mul g g, v_pk_mul c2 ., v_pk_fma b2 v), so no instantiation rounds otherwise,
 // whatever stands in front of them: with factor = 1 the guarded update is the unguarded one bit for bit, and the masked the dense.
+// DECAY (ctx_set_param_weight_decay; runs only): decoupled weight decay, p' = q - update with q = fmaf(-d, p, p), d = the run's wd_t --
+// on the parameter as it was before the step and never times the clip factor; ONE fma, spelled with the builtin.  A run at d == 0 takes
+// q = p by a select, not by the fma (fmaf(-0, p, p) turns -0 into +0 and inf into NaN): it is updated bit for bit as without DECAY.
+// The pass reads and writes what it did: the same seven streams.
 // the update one element moves by -- adam_kernel subtracts it, the statistics pass (below) measures it: one expression for both
 __device__ __forceinline__ float adam_update(float lr_t, float m, float v, float eps) { return lr_t * m / (sqrtf(v) + eps); }
-template <class A, bool GUARD>
+template <class A, bool GUARD, bool DECAY>
 __global__ __launch_bounds__(NTHREADS) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                         const A span, float b1, float b2, float eps, const GuardCtl* __restrict__ ctl) {
     if (GUARD && ctl->apply == 0) return;      // (uniform) a skipped step reads and writes nothing
-    Walk<A> w(span);
+    Walk<A> w(span, std::conditional_t<DECAY, WithDecay, NoDecay>{});
     const float factor = GUARD ? ctl->factor : 1.f, c1 = 1.f - b1, c2 = 1.f - b2;
     // streaming: every element is touched once per step and the arena (0.76 GB) is larger than any cache -- nontemporal loads and
     // stores (1.334 GB in 0.231 ms = 5.8 TB/s against 0.245 ms with plain accesses; deeper unrolling measured slower, round 4)
     for (auto c = grid_first<A>(); c < w.total; c += grid_step<A>()) {
         const int64_t i = w.at(c);
-        const float lr_t = w.lr_t();
+        const float lr_t = w.lr_t(), d = DECAY ? w.wd_t() : 0.f;
         f4 gg = __builtin_nontemporal_load(reinterpret_cast<const f4*>(g + i));
         if (GUARD) gg = gg * factor;
         f4 mm = __builtin_nontemporal_load(reinterpret_cast<const f4*>(m + i));
@@ -77,7 +90,8 @@ __global__ __launch_bounds__(NTHREADS) void adam_kernel(float* __restrict__ p, c
         for (int k = 0; k < 4; ++k) {
             mm[k] = __builtin_fmaf(b1, mm[k], c1 * gg[k]);
             vv[k] = __builtin_fmaf(b2, vv[k], c2 * (gg[k] * gg[k]));
-            pp[k] = pp[k] - adam_update(lr_t, mm[k], vv[k], eps);
+            const float q = DECAY && d != 0.f ? __builtin_fmaf(-d, pp[k], pp[k]) : pp[k];
+            pp[k] = q - adam_update(lr_t, mm[k], vv[k], eps);
         }
         __builtin_nontemporal_store(mm, reinterpret_cast<f4*>(m + i));
         __builtin_nontemporal_store(vv, reinterpret_cast<f4*>(v + i));
@@ -323,9 +337,15 @@ void adam(hipStream_t s, float* p, const float* g, float* m, float* v, const Spa
     const int64_t groups = span_groups(sp, sp.n / 4);
     if (groups <= 0) return;
     const dim3 grid(ew_blocks(groups)), block(NTHREADS);
+    if (sp.decay) {                                      // (the engine hands decay over the runs only)
+        const AdamSegs& a = *sp.runs;
+        if (ctl) hipLaunchKernelGGL((adam_kernel<AdamSegs, true, true>), grid, block, 0, s, p, g, m, v, a, b1, b2, eps, ctl);
+        else hipLaunchKernelGGL((adam_kernel<AdamSegs, false, true>), grid, block, 0, s, p, g, m, v, a, b1, b2, eps, ctl);
+        return;
+    }
     with_walk(sp, groups, [&](auto a) {
-        if (ctl) hipLaunchKernelGGL((adam_kernel<decltype(a), true>), grid, block, 0, s, p, g, m, v, a, b1, b2, eps, ctl);
-        else hipLaunchKernelGGL((adam_kernel<decltype(a), false>), grid, block, 0, s, p, g, m, v, a, b1, b2, eps, ctl);
+        if (ctl) hipLaunchKernelGGL((adam_kernel<decltype(a), true, false>), grid, block, 0, s, p, g, m, v, a, b1, b2, eps, ctl);
+        else hipLaunchKernelGGL((adam_kernel<decltype(a), false, false>), grid, block, 0, s, p, g, m, v, a, b1, b2, eps, ctl);
     });
 }
 

@@ -160,7 +160,7 @@ class RcclTrainer:
 
     def __init__(self, H=64, W=64, df_dim=64, featsize=1024, max_batch=256, device=0, seed=1234, rank=None, world=None,
                  unique_id=None, precision=None, grad_clip=None, skip_nonfinite=False, var_list=None, lr_scales=None,
-                 tensor_stats_every=None, ema_decay=None, accum_steps=1):
+                 weight_decay=None, tensor_stats_every=None, ema_decay=None, accum_steps=1):
         """precision: "f32" | "bf16x3" | "fp16x3" | "fp16x3d" (Translator.__init__); None = the translator's default.
         tensor_stats_every: k >= 1 takes per-tensor statistics of the REDUCED gradient, the parameters and the update on every rank's
         device behind every k-th Adam update (Translator.set_tensor_stats); replicas hold identical tables, read rank 0's with
@@ -173,7 +173,9 @@ class RcclTrainer:
         grad_clip / skip_nonfinite: Translator.set_grad_guard -- clip by the global norm of the REDUCED gradient, skip a step whose
         reduced gradient is non-finite; every rank takes the same decision on the device.  Defaults: no guard.
         var_list / lr_scales: Translator.set_trainable / set_lr_scales (one of the two) -- Adam and the guard's norm of the reduced
-        gradient cover the trainable tensors only; the backward and the all-reduce stay whole.  Defaults: every variable."""
+        gradient cover the trainable tensors only; the backward and the all-reduce stay whole.  Defaults: every variable.
+        weight_decay: Translator.set_weight_decay -- decoupled weight decay (AdamW) inside the Adam pass, a float lambda for the kernels
+        and matrices or {pattern: lambda}; every rank must be given the same, replicas then stay bit-identical.  Default: none."""
         if var_list is not None and lr_scales is not None:
             raise ValueError("var_list and lr_scales are two spellings of one mask: give one")
         if rank is None:
@@ -204,6 +206,8 @@ class RcclTrainer:
             self.translator.set_trainable(var_list)
         elif lr_scales is not None:
             self.translator.set_lr_scales(lr_scales)
+        if weight_decay is not None:
+            self.translator.set_weight_decay(weight_decay)
         if ema_decay is not None:
             self.translator.set_ema(float(ema_decay))
         self.tensor_stats_every = tensor_stats_every

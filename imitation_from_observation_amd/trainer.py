@@ -141,8 +141,8 @@ class ModelTrainer:
     def __init__(self, idims, nvideos, ntrain, batch_size, model, nitr, save_every, nlen, nskip, rescale=True, inception=False,
                  strides=None, kernels=None, filters=None, *, vdata=None, basedir="model/", device=0, seed=0, translator=None,
                  precision=None, log=print, rank=0, world=1, dp_unique_id=None, videos=None, device_resize=False,
-                 grad_clip=None, skip_nonfinite=False, var_list=None, lr_scales=None, tensor_stats_every=None, ema_decay=None, ema_eval=False,
-                 accum_steps=1):
+                 grad_clip=None, skip_nonfinite=False, var_list=None, lr_scales=None, weight_decay=None, lr_schedule=None, tensor_stats_every=None,
+                 ema_decay=None, ema_eval=False, accum_steps=1):
         """The reference's 14 positional arguments (train_script.py:29-30; the launchers omit the last five, SURVEY.md 3.4-b,
         hence the defaults), then: vdata (array or .npy path of the demo tensor), basedir (logger._snapshot_dir), device,
         seed of the parameter initialiser, an optional ready-made translator (tests), the arithmetic (precision: "f32" | "bf16x3" | "fp16x3" | "fp16x3d",
@@ -173,7 +173,13 @@ class ModelTrainer:
         max_batch = ceil(batch_size / world / k), so the batch no longer has to fit one launch sequence.  Logs, progress.csv,
         checkpoints and clips are as before (validation batches are evaluated in the same slices and their scalars combined).
         Needs the device-resident sampler (a demo tensor on the uint8 lattice).  Out of scope: inception=True -- the front end would
-        have to run on every tgt frame first for the global nn_err -- which raises ValueError.  Default 1: the code path as before."""
+        have to run on every tgt frame first for the global nn_err -- which raises ValueError.  Default 1: the code path as before.
+        weight_decay: decoupled weight decay (AdamW) inside the fused Adam pass -- Translator.set_weight_decay: a float lambda for every
+        kernel and matrix (not the biases) or {pattern: lambda}; set once before the first step, beside the mask.  Default: none; logs,
+        files and draws as before.
+        lr_schedule: a callable itr -> learning rate used in place of the constant 1e-4 (train_script.py:163,167) at iteration itr
+        (from 1); a negative or non-finite value raises before that step.  The decay per step is lr * lambda, so it follows the
+        schedule by itself.  Default: the constant rate."""
         if model not in self.MODELS:
             raise ValueError(f"model must be one of {sorted(self.MODELS)}")
         self.idims, self.nvideos, self.ntrain, self.batch_size = tuple(idims), nvideos, ntrain, batch_size
@@ -186,6 +192,9 @@ class ModelTrainer:
         if var_list is not None and lr_scales is not None:
             raise ValueError("var_list and lr_scales are two spellings of one mask: give one")
         self.var_list, self.lr_scales = var_list, lr_scales
+        if lr_schedule is not None and not callable(lr_schedule):
+            raise ValueError("lr_schedule must be a callable itr -> learning rate")
+        self.weight_decay, self.lr_schedule = weight_decay, lr_schedule
         self.videos = videos       # decoded demo videos (arrays [51, H, W, 3] uint8 or callables returning them): train_script.py:59-96
         self.translator, self.precision, self.log = translator, precision, log
         self.rank, self.world, self.dp_unique_id = int(rank), int(world), dp_unique_id
@@ -323,18 +332,26 @@ class ModelTrainer:
                              "(k / 127.5 - 1, what train_script.py:16-19 makes of video frames)")
         micro = -(-Bl // self.accum_steps)                         # rows of a micro-batch (the last may be short: micro_slices)
 
-        def train_step(cs, ct, want_err=False):
+        def train_step(cs, ct, want_err=False, lr=LEARNING_RATE):
             if accum:                                              # GLOBAL scalars, and nn_err of the whole batch from the device
                 step = tr.dp_train_step_sampled_accum if dp else tr.train_step_sampled_accum
-                return step(cs, ct, micro, lr=LEARNING_RATE, nlen=nlen if want_err else None)
+                return step(cs, ct, micro, lr=lr, nlen=nlen if want_err else None)
             if dp:
-                return tr.dp_train_step_sampled(cs, ct, lr=LEARNING_RATE)          # GLOBAL scalars
+                return tr.dp_train_step_sampled(cs, ct, lr=lr)                     # GLOBAL scalars
             if resident:
-                return tr.train_step_sampled(cs, ct, lr=LEARNING_RATE)
+                return tr.train_step_sampled(cs, ct, lr=lr)
             src, ctx, tgt = self._batch(traindata, cs, ct)
             if self.inception:
-                return tr.train_step_u8(src, ctx, tgt, lr=LEARNING_RATE)
-            return tr.train_step(src, ctx, tgt, lr=LEARNING_RATE)
+                return tr.train_step_u8(src, ctx, tgt, lr=lr)
+            return tr.train_step(src, ctx, tgt, lr=lr)
+
+        def lr_at(itr):
+            if self.lr_schedule is None:
+                return LEARNING_RATE
+            lr = float(self.lr_schedule(itr))
+            if not (np.isfinite(lr) and lr >= 0.0):
+                raise ValueError(f"lr_schedule({itr}) = {lr}: the learning rate must be finite and >= 0")
+            return lr
 
         def evaluate(cs, ct):
             """loss, sim, r1, r2, out, out2, tgt of a validation batch (indices into validdata)."""
@@ -369,6 +386,8 @@ class ModelTrainer:
             core.set_trainable(self.var_list)
         elif self.lr_scales is not None:
             core.set_lr_scales(self.lr_scales)
+        if self.weight_decay is not None:
+            core.set_weight_decay(self.weight_decay)
         if self.ema_decay is not None:
             core.set_ema(self.ema_decay)
         if self.tensor_stats_every is not None:
@@ -379,7 +398,7 @@ class ModelTrainer:
         for itr in range(1, self.nitr):
             choicesrc = np.random.choice(ntrain, B)
             choicetgt = np.random.choice(ntrain, B)
-            sc = train_step(choicesrc, choicetgt, want_err=itr % 4 == 0)
+            sc = train_step(choicesrc, choicetgt, want_err=itr % 4 == 0, lr=lr_at(itr))
             if self.tensor_stats_every is not None and rank == 0 and itr % self.tensor_stats_every == 0:
                 st = core.tensor_stats()                       # (the table the step left behind its update; an on-demand one has no update)
                 if st["has_update"] and st["step"] != stats_step:

@@ -101,6 +101,36 @@ def resolve_lr_scales(names, spec):
     return out
 
 
+def resolve_weight_decay(names, shapes, spec):
+    """One decoupled weight-decay rate (lambda of torch.optim.AdamW) per TF variable name, in the order of `names`.  `spec`: a float
+    applies to every tensor with ndim >= 2 (kernels and matrices, not biases); a dict maps fnmatch patterns to rates and is applied IN
+    ORDER -- a later pattern overrides an earlier one -- and tensors no pattern matches are 0.  ValueError: a pattern that matches no
+    name, a negative or non-finite rate (the rules of resolve_lr_scales)."""
+    import fnmatch
+    names, shapes = list(names), list(shapes)
+    if len(names) != len(shapes):
+        raise ValueError(f"{len(names)} names but {len(shapes)} shapes")
+
+    def rate(what, wd):
+        wd = float(wd)
+        if not (np.isfinite(wd) and wd >= 0.0):
+            raise ValueError(f"weight decay of {what} must be finite and >= 0, got {wd}")
+        return wd
+
+    out = np.zeros(len(names), np.float32)
+    if not isinstance(spec, dict):
+        wd = rate("the matrices", spec)
+        out[[i for i, sh in enumerate(shapes) if len(tuple(sh)) >= 2]] = wd
+        return out
+    for pat, wd in spec.items():
+        wd = rate(repr(pat), wd)
+        hit = [i for i, n in enumerate(names) if fnmatch.fnmatchcase(n, pat)]
+        if not hit:
+            raise ValueError(f"pattern {pat!r} matches none of the {len(names)} variables")
+        out[hit] = wd
+    return out
+
+
 class Translator:
     """One ContextSkipNew model (gym/envs/mujoco/arm_shaping.py:1260-1354) resident on one MI355X.
 
@@ -896,6 +926,27 @@ class Translator:
         sc = np.empty(len(names), np.float32)
         self._ck(self._lib.ctx_get_param_lr_scale(self._h, _fp(sc), sc.size))
         return OrderedDict((n, float(s)) for n, s in zip(names, sc))
+
+    # ------------------------------------------------------------------ decoupled weight decay (include/ctxtrans.h: ctx_set_param_weight_decay)
+    def set_weight_decay(self, spec):
+        """Decoupled weight decay (AdamW) for every later Adam update of this handle, inside the fused Adam pass: `spec` = a float
+        lambda for every tensor with ndim >= 2 (kernels and matrices, not biases), or {fnmatch pattern on the TF variable name:
+        lambda}, applied in order, unmatched tensors 0 (resolve_weight_decay).  p is shrunk by lr * lambda per step (lr times the
+        tensor's lr scale; the raw rate, torch's convention) before the Adam term is subtracted; frozen tensors are not decayed, a
+        step the guard skips does not decay.  None or 0 (or every rate 0) = off, the default.  Not saved in checkpoints."""
+        if spec is None or (not isinstance(spec, dict) and float(spec) == 0.0):
+            self._ck(self._lib.ctx_set_param_weight_decay(self._h, None, 0))
+            return
+        info = self.param_info()
+        wd = resolve_weight_decay([n for n, _, _ in info], [sh for _, sh, _ in info], spec)
+        self._ck(self._lib.ctx_set_param_weight_decay(self._h, _fp(wd), wd.size))
+
+    def get_weight_decay(self):
+        """OrderedDict name -> lambda (0.0 everywhere without decay)."""
+        names = [n for n, _, _ in self.param_info()]
+        wd = np.empty(len(names), np.float32)
+        self._ck(self._lib.ctx_get_param_weight_decay(self._h, _fp(wd), wd.size))
+        return OrderedDict((n, float(x)) for n, x in zip(names, wd))
 
     def dev_scalars(self):
         sc = np.empty(4, np.float32)

@@ -462,6 +462,36 @@ int ctx_grad_guard_stats(ctx_handle* h, double* last_norm, float* last_factor, i
  *   - ctx_dev_backward_vjp ignores the mask: frame and code gradients need the whole chain. */
 int ctx_set_param_lr_scale(ctx_handle* h, const float* scale, int n);
 int ctx_get_param_lr_scale(const ctx_handle* h, float* scale, int n);
+/* ---- decoupled weight decay: one rate per tensor (Loshchilov & Hutter's AdamW, torch.optim.AdamW) ----
+ * decay[i] = lambda of tensor i of ctx_param_info (n == ctx_param_count(h)).  decay == NULL (n ignored) or every rate 0 = off, the
+ * default: every launch is then the one of a handle that never called this.  CTX_E_INVALID: NULL handle, wrong n, a negative or
+ * non-finite rate.  Like ctx_set_param_lr_scale it never answers CTX_E_STATE: the rates only take effect at the next Adam update, also
+ * when set inside an open accumulation or while the averaged weights are swapped in.  The rates are handle state; checkpoints do not hold them.
+ * They cover every Adam update of the handle (ctx_train_step*, ctx_dev_train_step, ctx_dev_adam, ctx_accum_adam, ctx_dp_train_step*),
+ * in ONE launch per step, inside the Adam pass -- no further traffic.  Per element, with lr_i = (float)(lr * scale[i]) and
+ * d = (float)(lr_i * decay[i]), both products taken in f32:
+ *     m' = b1 m + (1 - b1) g ;  v' = b2 v + (1 - b2) g g          (as without; g already times the clip factor under a guard)
+ *     q  = d != 0 ? fmaf(-d, p, p) : p                             (ONE rounding)
+ *     p' = q - lr_t m' / (sqrt(v') + eps)                          (lr_t: the bias-corrected rate formed from lr_i, as without)
+ *   - d is formed from the RAW rate lr_i, not from lr_t (torch's convention), so the decay follows a learning-rate schedule by
+ *     itself.  It acts on the parameter as it was before the step; it is not part of the gradient, so it enters neither m nor v.
+ *     (Coupled L2, lambda p added to g, is NOT offered.)
+ *   - a tensor at decay 0 inside a decayed step is updated bit for bit as on a handle without decay, -0 and non-finite values
+ *     included; m and v of EVERY tensor are those of the undecayed step.
+ *   - guard (ctx_set_grad_guard): the clip factor scales g only, never the decay; norm, factor and skip decision are bit for bit the
+ *     undecayed handle's.  A step the guard skips does not decay.
+ *   - mask (ctx_set_param_lr_scale): a scaled tensor decays at lr_i -- bit for bit the update of an unmasked handle stepped at
+ *     (float)(lr * scale[i]) with the same lambda.  A frozen tensor is not decayed and keeps every bit of p, m and v, whatever its
+ *     lambda.  Decay alone does NOT make a handle masked: the backward stays whole, the guard's norm, the accumulation and the average
+ *     keep their dense extent and ctx_get_grads is unchanged.
+ *   - the early Adam slices are not used, as under a guard or a mask (the value of option "early_adam" is not changed).
+ *   - accumulation (ctx_accum_*): one decay per UPDATE, not per micro-batch.  Average (ctx_ema_*): follows the decayed parameters.
+ *   - statistics (ctx_tensor_stats_*): unchanged; u stays the Adam term lr_t m / (sqrt(v) + eps).  The decay's own step is d |p|.
+ *   - data parallel: every rank must set the same rates, as with the mask; the update is deterministic, replicas stay bit-identical.
+ *   - channel pads and the floats between two tensors are exact zeros and stay exact zeros (fmaf(-d, 0, 0) = +0).
+ *   - ctx_dev_forward_vjp / ctx_dev_backward_vjp ignore the rates: they compute gradients, not updates. */
+int ctx_set_param_weight_decay(ctx_handle* h, const float* decay, int n);
+int ctx_get_param_weight_decay(const ctx_handle* h, float* decay, int n);
 /* Synchronises and copies {loss, simloss, recon1, recon2} of the last forward. */
 int ctx_dev_scalars(ctx_handle* h, float scalars[4]);
 /* Device pointer to the parameters (flat, ctx_param_info order).  WRITABLE: a caller may update the weights through it (its own
