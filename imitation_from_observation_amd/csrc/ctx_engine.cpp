@@ -196,7 +196,7 @@ int alloc_tail(ctx_handle* h, int64_t slab_floats, int64_t maxc) {
     return CTX_OK;
 }
 
-// ... and share in the middle: the activations of translate MLP, d_h0_lin and d_h1 .. d_h3 with their gradients (sized by h->dec)
+// ... and share in the middle: the activations of translate MLP, d_h0_lin and d_h1 .. d_h3 with their gradients (sized by h->plan)
 int alloc_middle(ctx_handle* h) {
     const int64_t B = h->Bm, F = h->Fp;
     TRY(dev_alloc(h, &h->th0, B * F));
@@ -205,7 +205,7 @@ int alloc_middle(ctx_handle* h) {
     TRY(dev_alloc(h, &h->dz, 2 * B * h->D0));
     TRY(dev_alloc(h, &h->dDz, 2 * B * h->D0));
     for (int k = 1; k <= 3; ++k) {   // e[k]: output of d_hk = the input grid and width of the encoder layer 4 - k it mirrors
-        const int64_t n = (int64_t)h->dec.g[4 - k].hb * h->dec.g[4 - k].wb * h->dec.co[4 - k];
+        const int64_t n = (int64_t)h->plan.g[4 - k].hb * h->plan.g[4 - k].wb * h->plan.co[4 - k];
         TRY(dev_alloc(h, &h->e[k], 2 * B * n));
         TRY(dev_alloc(h, &h->dE[k], 2 * B * n));
     }
@@ -427,7 +427,7 @@ void plan_mask(ctx_handle* h) {
     q.tz[0] = tr("translate/trans_z/Matrix"); q.tz[1] = tr("translate/trans_z/bias");
     q.th0[0] = tr("translate/trans_h0/Matrix"); q.th0[1] = tr("translate/trans_h0/bias");
     bool skip_grad[4];               // someone needs d loss / d (ctx skip h_gi): a trainable tensor of conv_context's h0 .. h_gi
-    if (h->gen) {                    // gen_backward's encoder loop is not pruned: it reads every code and skip gradient
+    if (h->gen) {                    // not done yet for the table-driven models: their encoder backward runs whole (encoder_bwd would prune it by these entries)
         for (int e = 0; e < 2; ++e) { q.enc_any[e] = true; for (int l = 0; l < 6; ++l) q.enc_dx[e][l] = q.enc[e][l][0] = q.enc[e][l][1] = true; }
         for (bool& b : skip_grad) b = true;
     } else {
@@ -925,23 +925,11 @@ void convt3(ctx_handle* h, const std::string& name, const Geo& g, const Cat& in,
     else convt3_gather_s1_t(h->stream, h->P3, b, out, nimg, hs, ws);
 }
 
-Scope scope_of(const ctx_handle* h, const std::string& sc) {
-    Scope s;
-    auto at = [&](const std::string& name, float*& w, float*& g) {
-        w = h->arena + h->find((sc + name).c_str()); g = w + h->Ppad;
-    };
-    for (int k = 0; k < 4; ++k) {
-        at("/h" + std::to_string(k) + "_conv/w", s.w[k], s.gw[k]);
-        at("/h" + std::to_string(k) + "_conv/biases", s.b[k], s.gb[k]);
-    }
-    at("/h4_lin/Matrix", s.w4, s.gw4); at("/h4_lin/bias", s.b4, s.gb4);
-    at("/hz_lin/Matrix", s.wz, s.gwz); at("/hz_lin/bias", s.bz, s.gbz);
-    return s;
-}
+const char* enc_name(int set) { return set ? "conv_context" : "conv"; }
 
-// ContextSkipNew's share of ctx_create: the record of the shared sequences and the two encoders' parameters, by name, once
+// ContextSkipNew's share of ctx_create: the record of the shared sequences, its parameters looked up by name, once
 void skip_plan(ctx_handle* h) {
-    DecoderPlan& p = h->dec;
+    Plan& p = h->plan;
     for (int gi = 0; gi < 4; ++gi) {
         p.g[gi] = Geo{h->hh[gi], h->ww[gi], h->hh[gi + 1], h->ww[gi + 1], 2, 1, 5};   // encoder h_gi and its mirror: 5x5 stride 2 from the grid H >> gi
         p.ch[gi] = h->d << gi;
@@ -953,24 +941,18 @@ void skip_plan(ctx_handle* h) {
     p.th0w = h->find("translate/trans_h0/Matrix"); p.th0b = h->find("translate/trans_h0/bias");
     p.tzw = h->find("translate/trans_z/Matrix"); p.tzb = h->find("translate/trans_z/bias");
     p.d0w = h->find("deconv/d_h0_lin/Matrix"); p.d0b = h->find("deconv/d_h0_lin/bias");
-    h->enc_conv = scope_of(h, "conv");
-    h->enc_ctx = scope_of(h, "conv_context");
-}
-
-// arm_shaping.py:1282-1288 / :1290-1307: four conv+lrelu, h4_lin+lrelu, hz_lin (+lrelu for `conv`)
-void encoder_fwd(ctx_handle* h, const std::string& scn, const Scope& sc, const float* x, int nimg, float* const act[5], float* z,
-                 int z_lrelu) {
-    const int d = h->d, F = h->F;
-    const float* in = x;
-    for (int k = 0; k < 4; ++k) {
-        const int ca = k ? d << (k - 1) : 3;
-        conv(h, scn + "/h" + std::to_string(k) + "_conv fwd", h->dec.g[k], in, ca, nimg, sc.w[k], d << k, epi_act(act[k], d << k, sc.b[k], 1),
-             ca == 3 && h->rt.direct3);
-        in = act[k];
+    for (int set = 0; set < 2; ++set) {
+        const std::string sc = enc_name(set);
+        EncParams& e = p.enc[set];
+        for (int k = 0; k < 4; ++k) {
+            e.w[k] = h->find((sc + "/h" + std::to_string(k) + "_conv/w").c_str());
+            e.b[k] = h->find((sc + "/h" + std::to_string(k) + "_conv/biases").c_str());
+        }
+        e.w4 = h->find((sc + "/h4_lin/Matrix").c_str()); e.b4 = h->find((sc + "/h4_lin/bias").c_str());
+        e.wz = h->find((sc + "/hz_lin/Matrix").c_str()); e.bz = h->find((sc + "/hz_lin/bias").c_str());
+        e.z_lrelu = set == 0;         // arm_shaping.py:1290-1307: conv_context's hz_lin is linear
     }
-    const int K3 = h->hh[4] * h->ww[4] * 8 * d;   // NHWC flatten, arm_shaping.py:1287
-    fc_layer(h, scn + "/h4_lin", km(act[3], K3, nimg, K3), nimg, K3, sc.w4, sc.b4, F, 1, act[4]);
-    fc_layer(h, scn + "/hz_lin", km(act[4], F, nimg, F), nimg, F, sc.wz, sc.bz, F, z_lrelu, z);
+    p.enc_early = true;
 }
 
 
@@ -1016,13 +998,143 @@ void frame_grads3(ctx_handle* h, const float* dA0, int c, int slot0, int nimg, i
     }
 }
 
+// ---- the encoders (arm_shaping.py:1282-1288 / :1290-1307): four conv+lrelu, h4_lin+lrelu, hz_lin (+lrelu per set) --------------------
+// One forward and one backward sequence for every variant, on h->plan and a description of the images they run on.  The engines own
+// the buffers (ContextSkipNew: s / c / cz and their gradients, the table-driven models: GenState::a / dA) and say which rows go in.
+
+// images through encoder `set`; every pointer is already at this part's first image
+struct EncPart {
+    int set;                     // 0 = conv, 1 = conv_context: whose parameters (Plan::enc) and whose name
+    const float* x;              // input frames / feature maps
+    int nimg;
+    float *act[5], *dact[5];     // outputs of h0..h3_conv, [4] = h4, and their gradients
+    float *z, *dz;               // the code rows hz_lin writes; the code-gradient rows its backward reads
+    bool skips;                  // context images: their input gradients add both decoder passes' dSk
+    int lane;                    // side lane of the filter / Matrix / bias gradients (LANE_DW), or -1: the current stream
+    int prune;                   // index into Prune::enc*
+    int slot0;                   // first image slot of [tgt | src | ctx] (frame gradients of a VJP)
+    int64_t row0;                // first row in the dropout buffers of sites 1 and 2
+};
+
+// fc false: the four convs only (the caller runs the FC layers: rchain_fwd)
+void encoder_fwd(ctx_handle* h, const EncPart& q, bool drop = false, bool fc = true) {
+    const Plan& p = h->plan;
+    const EncParams& e = p.enc[q.set];
+    const float* P = h->arena;
+    const std::string sc = enc_name(q.set);
+    const float* in = q.x;
+    for (int k = 0; k < 4; ++k) {
+        conv(h, sc + "/h" + std::to_string(k) + "_conv fwd", p.g[k], in, p.co[k], q.nimg, P + e.w[k], p.ch[k], epi_act(q.act[k], p.ch[k], P + e.b[k], 1),
+             p.direct[k]);
+        in = q.act[k];
+    }
+    if (!fc) return;
+    const int F = h->Fp, D0 = (int)h->D0;      // NHWC flatten, arm_shaping.py:1287
+    // sites 1 and 2: flatten(h3) * M1 feeds h4_lin, h4 * M2 feeds hz_lin (arm_shaping.py:1637-1638)
+    if (drop) { float* x1 = h->x1d + q.row0 * D0; ew_mul(h->stream, x1, D0, in, D0, h->dM[1] + q.row0 * D0, D0, q.nimg, D0); in = x1; }
+    fc_layer(h, sc + "/h4_lin", km(in, D0, q.nimg, D0), q.nimg, D0, P + e.w4, P + e.b4, F, 1, q.act[4]);
+    in = q.act[4];
+    if (drop) { float* x2 = h->x2d + q.row0 * F; ew_mul(h->stream, x2, F, in, F, h->dM[2] + q.row0 * F, F, q.nimg, F); in = x2; }
+    fc_layer(h, sc + "/hz_lin", km(in, F, q.nimg, F), q.nimg, F, P + e.wz, P + e.bz, F, e.z_lrelu, q.z);
+}
+
+// VJP frame / feature-map gradients of part `a`, one launch per image slot the caller asked for.  3-channel frames: frame_grads3.
+// Feature maps (ContextAEInception2, C a multiple of 32): the transposed conv of the deeper layers' input gradients, no lrelu';
+// out = decode + tgtctx adds d out + d out2 to the ctx maps.  The tgt slot adds recon_tgt_term in either case.
+void frame_grads(ctx_handle* h, int B, const EncPart& a) {
+    const Plan& p = h->plan;
+    const Geo& g = p.g[0];
+    const int C = p.co[0], cb = p.ch[0];
+    const float* w = h->arena + p.enc[a.set].w[0];
+    if (C == 3) { frame_grads3(h, a.dact[0], cb, a.slot0, a.nimg, g.hs, g.ws, g.s, w); return; }
+    for (int j = 0; j < a.nimg / B; ++j) {
+        const int slot = a.slot0 + j;
+        float* o = vjp_frame_out(h, slot);
+        if (!o) continue;
+        Epi ed;
+        ed.out1 = o; ed.ld1 = C;
+        if (slot == 2 && p.residual) { ed.add1 = h->dout; ed.lda1 = C; ed.add2 = h->dout + (int64_t)B * h->npi; ed.lda2 = C; }
+        convt(h, std::string(slot == 0 ? "tgt" : slot == 1 ? "src" : "ctx") + " frames dx", g, Cat{a.dact[0] + (int64_t)j * B * g.hs * g.ws * cb, cb}, B, w, C, ed,
+              p.direct[0], false);
+        if (slot == 0) recon_tgt_term(h, o);
+    }
+}
+
+// Backward of the encoders, layer-major: per layer hz_lin, h4_lin, h3..h0_conv first the filter / Matrix / bias gradients of every
+// w-part, each on its side lane, then the input gradient of every x-part (the x-parts' rows are contiguous, in order).  The two lists
+// cover the same images and differ where one set of parameters serves rows with and without the ctx-skip term (table-driven models:
+// ctxtrans_gen.inc); ContextSkipNew calls this once per encoder with one part for both.  dz of the parts holds d z with hz_lin's
+// lrelu' applied.  fc false: from h3_conv on (rchain_bwd did the FC layers).
+// A masked plain backward (pruning) runs a part's group iff one of its results reaches a trainable tensor: a part whose layer-l input
+// gradient has no reader takes no part in the layers in front of l.
+void encoder_bwd(ctx_handle* h, int B, const EncPart* wparts, int nw, const EncPart* xparts, int nx, bool drop = false, bool fc = true) {
+    const Plan& p = h->plan;
+    const Prune* q = pruning(h);
+    const float* P = h->arena;
+    float* G = h->arena + h->Ppad;
+    const int F = h->Fp, D0 = (int)h->D0;
+    bool live[2] = {true, true};                                  // by Prune index
+    // layer l = h0..h3_conv, h4_lin, hz_lin: part a's own gradients [0] filter / Matrix, [1] bias; its input gradient
+    auto on = [&](const EncPart& a, int l, int j) { return !q || q->enc[a.prune][l][j]; };
+    auto dx = [&](const EncPart& a, int l) { return live[a.prune] = live[a.prune] && (!q || q->enc_dx[a.prune][l]); };
+    for (int l = fc ? 5 : 3; l >= 0; --l) {
+        const int k = std::min(l, 3);                             // the conv layers' entry of the plan (l < 4)
+        const Geo& g = p.g[k];
+        const int ca = p.co[k], cb = p.ch[k];
+        auto name = [&](const EncPart& a) { return enc_name(a.set) + (l == 5 ? std::string("/hz_lin") : l == 4 ? "/h4_lin" : "/h" + std::to_string(l) + "_conv"); };
+        for (int i = 0; i < nw; ++i) {
+            const EncPart& a = wparts[i];
+            const EncParams& e = p.enc[a.set];
+            if (!live[a.prune] || !(on(a, l, 0) || on(a, l, 1))) continue;
+            Side sd(h, a.lane);                                   // this part's bias and filter / Matrix gradient: off the dx chain
+            if (l == 5) fc_dw(h, name(a), nm(drop ? h->x2d + a.row0 * F : a.act[4], F, F, a.nimg), F, a.dz, a.nimg, F, G + e.wz, G + e.bz, on(a, l, 0), on(a, l, 1));
+            else if (l == 4) fc_dw(h, name(a), nm(drop ? h->x1d + a.row0 * D0 : a.act[3], D0, D0, a.nimg), D0, a.dact[4], a.nimg, F, G + e.w4, G + e.b4, on(a, l, 0), on(a, l, 1));
+            else wgrad(h, name(a), g, l ? a.act[l - 1] : a.x, ca, Cat{a.dact[l], cb}, a.nimg, G + e.w[l], G + e.b[l], p.direct[l]);
+        }
+        if (l == 0) {                                             // the training step has no gradient w.r.t. the frames / features
+            for (int i = 0; i < nw && h->vjp; ++i) frame_grads(h, B, wparts[i]);
+            break;
+        }
+        int rows = 0;
+        for (int i = 0; i < nx; ++i) {
+            const EncPart& a = xparts[i];
+            const EncParams& e = p.enc[a.set];
+            rows += a.nimg;
+            if (!dx(a, l)) continue;
+            // the layer's input: act[l - 1] with ld columns per row (conv layers: per pixel), per_img floats per image
+            const int ld = l == 5 ? F : l == 4 ? D0 : ca;
+            const int64_t per_img = l == 5 ? F : l == 4 ? D0 : (int64_t)g.hb * g.wb * ca;
+            float* raw = l == 4 && drop ? h->graw + a.row0 * D0 : nullptr;       // site 1: the product alone first (below)
+            Epi ed;
+            ed.out1 = raw ? raw : a.dact[l - 1]; ed.ld1 = ld;
+            if (!raw) { ed.mask = a.act[l - 1]; ed.ldm = ld; }
+            if (!raw && a.skips && l < 5) {                       // + d loss / d (ctx skip h_(l-1)) of both decoder passes
+                ed.add1 = h->dSk[l - 1]; ed.lda1 = ld; ed.add2 = h->dSk[l - 1] + (int64_t)B * per_img; ed.lda2 = ld;
+            }
+            if (l == 5) fc_dx(h, name(a), a.dz, a.nimg, F, P + e.wz, F, ed);
+            else if (l == 4) fc_dx(h, name(a), a.dact[4], a.nimg, F, P + e.w4, D0, ed);
+            else convt(h, name(a) + " dx", g, Cat{a.dact[l], cb}, a.nimg, P + e.w[l], ca, ed, p.direct[l], false);     // conv2d_transpose of dact[l], the filter read [K,K,ca,cb]
+            // site 1: d h3 = ((h4_lin's input gradient) * M1 + the skip gradients) * lrelu'(h3)
+            if (raw) drop_fin(h->stream, a.dact[3], raw, h->dM[1] + a.row0 * D0, a.skips ? h->dSk[3] : nullptr, a.skips ? h->dSk[3] + (int64_t)B * D0 : nullptr,
+                              a.act[3], (int64_t)a.nimg * D0);
+            if (l == 4 && p.enc_early) {   // h4_lin / hz_lin of this encoder (2/3 of its parameters) are done with
+                const int64_t lin1 = e.w4 + (int64_t)D0 * F + F + (int64_t)F * F + F;
+                if (h->dp_in_step) dp_bucket(h, e.w4, lin1, a.lane);
+                else if (!h->bucket_fn) adam_early(h, e.w4, lin1, a.lane);
+            }
+        }
+        // site 2 (commutes with lrelu' of h4): one launch over the x-parts' rows
+        if (l == 5 && drop) ew_mul(h->stream, xparts[0].dact[4], F, xparts[0].dact[4], F, h->dM[2] + xparts[0].row0 * F, F, rows, F);
+    }
+}
+
 // ---- the part of the net every variant shares: translate MLP, d_h0_lin, d_h1 .. d_h4 -------------------------------------------
-// One launch sequence each, on the handle's buffers and h->dec; what depends on the call is an argument: the context code rows, the
+// One launch sequence each, on the handle's buffers and h->plan; what depends on the call is an argument: the context code rows, the
 // ctx skips (skip[gi] from image skip0 on), row counts, `drop` (this step applies dropout: only a handle with masks is asked to).
 
 // translate (arm_shaping.py:1309-1312): trans_h0 on concat([src_z, ctx_z], 1), then trans_z into Z rows [0, B); nc == 1: ONE context code for all rows
 void translate_fwd(ctx_handle* h, int B, const float* ctx_z, int nc, bool drop) {
-    const DecoderPlan& p = h->dec;
+    const Plan& p = h->plan;
     const float* P = h->arena;
     const int F = h->Fp;
     const float* src_z = h->Z + 2ll * B * F;
@@ -1039,7 +1151,7 @@ void translate_fwd(ctx_handle* h, int B, const float* ctx_z, int nc, bool drop) 
 // decoder (arm_shaping.py:1321-1330, :1334-1343) over nd rows: dz = d_h0_lin(zin) -- zin null: dz is there already (rchain wrote it) --
 // then d_h1 .. d_h4; row r reads the ctx skips of image skip0 + r % nc of skip[gi]
 void decoder_fwd(ctx_handle* h, int B, const float* zin, int nd, const float* const skip[4], int skip0, int nc, bool infer, bool rec, bool drop) {
-    const DecoderPlan& p = h->dec;
+    const Plan& p = h->plan;
     const float* P = h->arena;
     const int F = h->Fp, D0 = (int)h->D0;
     if (zin && drop) { ew_mul(h->stream, h->zd, F, zin, F, h->dM[5], F, nd, F); zin = h->zd; }     // site 5: z * M5 feeds d_h0_lin (:1660)
@@ -1066,7 +1178,7 @@ void decoder_fwd(ctx_handle* h, int B, const float* zin, int nd, const float* co
 
 // d_h4 .. d_h1 backward, both passes at once (2B rows) from h->dout: per layer the filter gradient on the side lane, then the input gradient
 void decoder_bwd(ctx_handle* h, int B, const float* const skip[4], int skip0, bool drop) {
-    const DecoderPlan& p = h->dec;
+    const Plan& p = h->plan;
     const Prune* q = pruning(h);      // a masked plain backward: a group runs iff a trainable tensor's gradient depends on it
     float* G = h->arena + h->Ppad;
     const float* dy = h->dout;
@@ -1095,7 +1207,7 @@ void decoder_bwd(ctx_handle* h, int B, const float* const skip[4], int skip0, bo
 
 // d_h0_lin, trans_z, trans_h0 backward from dDz into dZ ([trans_z | tgt_z | src_z] rows) and d_ctx_z; translate/*, deconv/* are then final
 void fc_middle_bwd(ctx_handle* h, int B, const float* ctx_z, float* d_ctx_z, bool drop) {
-    const DecoderPlan& p = h->dec;
+    const Plan& p = h->plan;
     const float* P = h->arena;
     float* G = h->arena + h->Ppad;
     const int F = h->Fp, D0 = (int)h->D0;
@@ -1143,6 +1255,15 @@ void fc_middle_bwd(ctx_handle* h, int B, const float* ctx_z, float* d_ctx_z, boo
 #include "ctxtrans_gen.inc"
 namespace ctxi {
 
+// ContextSkipNew's encoder parts: `conv` (set 0) on s / dS with its filter gradients on the side lane, `conv_context` (set 1) on c / dC
+EncPart skip_part(ctx_handle* h, int set, const float* x, int nimg, float* z, float* dz) {
+    EncPart q{};
+    q.set = q.prune = set; q.x = x; q.nimg = nimg; q.z = z; q.dz = dz;
+    for (int k = 0; k < 5; ++k) { q.act[k] = set ? h->c[k] : h->s[k]; q.dact[k] = set ? h->dC[k] : h->dS[k]; }
+    q.skips = set == 1; q.lane = set ? -1 : LANE_DW; q.slot0 = set ? 2 : 0;
+    return q;
+}
+
 // Forward.  TRAIN/EVAL: st = [tgt | src] (2B), decoder = [translated | truth] (2B).
 // TRANSLATE: only what translated_z / out depend on (src encoder, ctx encoder, translate, decoder
 // pass 1) -- the subgraph TF would run for base.py:216-218.  ENCODE: `conv` encoder on src only.
@@ -1170,16 +1291,17 @@ void forward(ctx_handle* h, int B, Mode mode) {
     else pack_c4(h, h->img + B * npi, (mode == MODE_ENCODE ? 1ll : 2ll) * B * h->H * h->W);
     // (inside a captured translate the second branch starts ~70 us behind the first whichever chain is issued first, or layer by layer --
     // measured, profiles/round5_c_reward_latency.txt; with ONE context frame its chain still ends before the 25-frame `conv` chain needs it)
+    const EncPart ctx_p = skip_part(h, 1, ctx_img, nc, h->cz, nullptr);
     if (lanes) {
         fork(h, LANE_CTX);
         LaneSwap sw(h, LANE_CTX);
-        encoder_fwd(h, "conv_context", h->enc_ctx, ctx_img, nc, h->c, h->cz, 0);
+        encoder_fwd(h, ctx_p);
     }
-    if (mode == MODE_TRAIN) encoder_fwd(h, "conv", h->enc_conv, h->img, 2 * B, h->s, h->Z + (int64_t)B * F, 1);
-    else encoder_fwd(h, "conv", h->enc_conv, h->img + B * npi, B, h->s, src_z, 1);
+    if (mode == MODE_TRAIN) encoder_fwd(h, skip_part(h, 0, h->img, 2 * B, h->Z + (int64_t)B * F, nullptr));
+    else encoder_fwd(h, skip_part(h, 0, h->img + B * npi, B, src_z, nullptr));
     if (mode == MODE_ENCODE) return;
     if (lanes) join(h, LANE_CTX);
-    else encoder_fwd(h, "conv_context", h->enc_ctx, ctx_img, nc, h->c, h->cz, 0);
+    else encoder_fwd(h, ctx_p);
     if (!rec) translate_fwd(h, B, h->cz, nc, false);
     // decoder; MODE_RECON: pass 2 alone, on tgtimg_z = input_z
     const int nd = mode == MODE_TRAIN ? 2 * B : B;
@@ -1193,7 +1315,7 @@ void backward(ctx_handle* h, int B, int sim_batch) {
     h->act_serial++;
     g_zeros = h->zeros;
     if (h->gen) { gen_backward(h, B, sim_batch); return; }
-    const int d = h->d, F = h->F;
+    const int F = h->F;
     const int64_t npi = h->npi;
     float* tgt_z = h->Z + (int64_t)B * F;
     // a masked plain backward runs a launch group iff a trainable tensor's gradient depends on one of its results (Prune, ctx_internal.h)
@@ -1204,53 +1326,10 @@ void backward(ctx_handle* h, int B, int sim_batch) {
     // ---- decoder (both passes at once, batch 2B) and FC middle
     decoder_bwd(h, B, h->c, 0, false);
     fc_middle_bwd(h, B, h->cz, h->dcz, false);
-    // ---- encoders
-    auto encoder_bwd = [&](const std::string& scn, const Scope& sc, const float* x, int nimg, float* const act[5], float* dzp, float* const dA[5],
-                           bool with_skips, int dw_lane, int slot0, int e) {
-        const int K3 = h->hh[4] * h->ww[4] * 8 * d;
-        // layer l = h0..h3_conv, h4_lin, hz_lin of encoder e: its own gradients [0] filter / Matrix, [1] bias; its input gradient
-        auto on = [&](int l, int j) { return !q || q->enc[e][l][j]; };
-        auto dx = [&](int l) { return !q || q->enc_dx[e][l]; };
-        if (on(5, 0) || on(5, 1)) { Side sd(h, dw_lane); fc_dw(h, scn + "/hz_lin", nm(act[4], F, F, nimg), F, dzp, nimg, F, sc.gwz, sc.gbz, on(5, 0), on(5, 1)); }
-        if (!dx(5)) return;          // (no trainable tensor in front of this layer: nothing reads its input gradient)
-        Epi e4;
-        e4.out1 = dA[4]; e4.ld1 = F; e4.mask = act[4]; e4.ldm = F;
-        fc_dx(h, scn + "/hz_lin", dzp, nimg, F, sc.wz, F, e4);
-        if (on(4, 0) || on(4, 1)) { Side sd(h, dw_lane); fc_dw(h, scn + "/h4_lin", nm(act[3], K3, K3, nimg), K3, dA[4], nimg, F, sc.gw4, sc.gb4, on(4, 0), on(4, 1)); }
-        if (!dx(4)) return;
-        Epi e3;
-        e3.out1 = dA[3]; e3.ld1 = K3; e3.mask = act[3]; e3.ldm = K3;
-        if (with_skips) { e3.add1 = h->dSk[3]; e3.lda1 = K3; e3.add2 = h->dSk[3] + (int64_t)B * K3; e3.lda2 = K3; }
-        fc_dx(h, scn + "/h4_lin", dA[4], nimg, F, sc.w4, K3, e3);
-        {   // h4_lin / hz_lin of this encoder (2/3 of its parameters) are done with
-            const int64_t lin0 = sc.w4 - h->arena, lin1 = lin0 + (int64_t)K3 * F + F + (int64_t)F * F + F;
-            if (h->dp_in_step) dp_bucket(h, lin0, lin1, dw_lane);
-            else if (!h->bucket_fn) adam_early(h, lin0, lin1, dw_lane);
-        }
-        for (int k = 3; k >= 0; --k) {
-            const Geo g = h->dec.g[k];
-            const int ca = k ? d << (k - 1) : 3, cb = d << k;
-            const std::string ln = scn + "/h" + std::to_string(k) + "_conv";
-            if (on(k, 0) || on(k, 1)) {
-              Side sd(h, dw_lane);
-              wgrad(h, ln, g, k ? act[k - 1] : x, ca, Cat{dA[k], cb}, nimg, sc.gw[k], sc.gb[k], ca == 3 && h->rt.direct3); }
-            if (k == 0) {
-                if (h->vjp) frame_grads3(h, dA[0], cb, slot0, nimg, g.hs, g.ws, 2, sc.w[0]);   // (the training step has no frame gradient)
-                break;
-            }
-            if (!dx(k)) return;
-            // input gradient = conv2d_transpose of dA[k] with the same filter read as [5,5,ca,cb]
-            Epi ed;
-            ed.out1 = dA[k - 1]; ed.ld1 = ca; ed.mask = act[k - 1]; ed.ldm = ca;
-            if (with_skips) {
-                ed.add1 = h->dSk[k - 1]; ed.lda1 = ca;
-                ed.add2 = h->dSk[k - 1] + (int64_t)B * g.hb * g.wb * ca; ed.lda2 = ca;
-            }
-            convt(h, ln + " dx", g, Cat{dA[k], cb}, nimg, sc.w[k], ca, ed, false, false);
-        }
-    };
-    // `conv` on [tgt | src]: code gradients are rows [B, 3B) of dZ; hz_lin has an lrelu
-    float* dSz = h->dZ + (int64_t)B * F;
+    // ---- encoders: `conv` on [tgt | src] (code gradients: rows [B, 3B) of dZ; hz_lin has an lrelu) with its filter gradients on the
+    // side lane, `conv_context` on the contexts
+    const EncPart conv_p = skip_part(h, 0, h->img, 2 * B, tgt_z, h->dZ + (int64_t)B * F);
+    const EncPart ctx_p = skip_part(h, 1, h->img + 2 * B * npi, B, h->cz, h->dcz);
     const bool lanes = use_lanes(h);
     const bool do_conv = !q || q->enc_any[0], do_ctx = !q || q->enc_any[1];     // (an encoder without a trainable tensor is not entered)
     if (lanes && do_ctx) {
@@ -1258,16 +1337,15 @@ void backward(ctx_handle* h, int B, int sim_batch) {
         // everything it reads (dcz, dSk[*], c[*]) was produced before this point
         fork(h, LANE_CTX);
         LaneSwap sw(h, LANE_CTX);
-        encoder_bwd("conv_context", h->enc_ctx, h->img + 2 * B * npi, B, h->c, h->dcz, h->dC, true, -1, 2, 1);
+        encoder_bwd(h, B, &ctx_p, 1, &ctx_p, 1);
     }
     if (do_conv) {
-        { ProfScope ps(h, "conv/hz_lin lrelu'", K_EW, 0.0); lrelu_mask(h->stream, dSz, tgt_z, 2ll * B * F); }
-        encoder_bwd("conv", h->enc_conv, h->img, 2 * B, h->s, dSz, h->dS, false, LANE_DW, 0, 0);
+        { ProfScope ps(h, "conv/hz_lin lrelu'", K_EW, 0.0); lrelu_mask(h->stream, conv_p.dz, tgt_z, 2ll * B * F); }
+        encoder_bwd(h, B, &conv_p, 1, &conv_p, 1);
     }
     if (lanes) { if (do_ctx) join(h, LANE_CTX); join(h, LANE_DW); }
-    else if (do_ctx) encoder_bwd("conv_context", h->enc_ctx, h->img + 2 * B * npi, B, h->c, h->dcz, h->dC, true, -1, 2, 1);
+    else if (do_ctx) encoder_bwd(h, B, &ctx_p, 1, &ctx_p, 1);
     h->have_grads = true;
-
 }
 
 // The reward hook's fetches at small batch are launch-bound (9-40 launches for well under 100 us of GPU work at B = 25):

@@ -1,7 +1,7 @@
 // ctx_internal.h -- what the translation units of libctxtrans.so share: the handle (HBM layout below), the table-driven engine's state,
 // and the entry points of the launch sequences (ctx_engine.cpp) that the C ABI (ctx_abi.cpp) and the RCCL client (ctx_dp.cpp) call.
 // The handle owns what translate MLP and decoder work on in every variant (th0, dz, e[], their gradients, dSk[], dsim2, the dropout
-// masks) and the record `dec` each engine fills at create; GenState keeps the table-driven engine's own tables and encoder activations.
+// masks) and the record `plan` each engine fills at create; GenState keeps the table-driven engine's own tables and encoder activations.
 // Nothing here is part of the public interface (include/ctxtrans.h).
 //
 // Batching (what makes each filter gradient a single launch): the `conv` encoder runs once on the
@@ -50,6 +50,13 @@ struct ParamInfo {
     int64_t size;
 };
 
+// one encoder's parameters: arena offsets (floats) of h0..h3_conv/{w,biases}, h4_lin/{Matrix,bias}, hz_lin/{Matrix,bias}; gradients
+// are offset + Ppad.  z_lrelu: hz_lin has an lrelu (every encoder but ContextSkipNew's conv_context)
+struct EncParams {
+    int64_t w[4], b[4], w4, b4, wz, bz;
+    bool z_lrelu = true;
+};
+
 struct GenState {
     // ---- architecture
     int Kk[4] = {5, 5, 5, 5};    // kernel size (k x k) of encoder layer h0..h3; d_h1..d_h4 mirror them (k4, k3, k2, k1)
@@ -72,12 +79,12 @@ struct GenState {
     std::vector<Seg> segs;
     std::vector<int32_t> real2pad;
     int64_t pend = 0;            // end of the last tensor in the padded arena: [pend, Ppad) belongs to no tensor and no backward writes it
-    // padded parameter offsets (floats into the arena), per encoder set
-    int64_t w[2][4], b[2][4], w4[2], b4[2], wz[2], bz[2], th0w, th0b, tzw, tzb, d0w, d0b, dw[5], db[5];
+    // padded parameter offsets (floats into the arena) as gen_layout lays them out; gen_plan copies them into ctx_handle::plan, which
+    // is what the launch sequences read
+    EncParams enc[2];
+    int64_t th0w, th0b, tzw, tzb, d0w, d0b, dw[5], db[5];
     // ---- activations (NHWC, cp[k] channels) and their gradients
     float *a[5] = {}, *dA[5] = {};           // a[0..3] conv outputs over 3B images [tgt | src | ctx], a[4] = h4 [3B, Fp]
-    // dropout sites 1 and 2 (factors: ctx_handle::dM): the dropped copies h4_lin / hz_lin read, and h4_lin's raw input gradient
-    float *x1d = nullptr, *x2d = nullptr, *graw = nullptr;
     int in_grid_h(int k, int H) const { return k ? gh[k - 1] : H; }
     int in_grid_w(int k, int W) const { return k ? gw[k - 1] : W; }
     int in_ch(int k) const { return k ? cp[k - 1] : C0; }
@@ -100,20 +107,25 @@ struct Routing {
 // a SAME-padded K x K stride-s layer: big grid hb x wb (conv input = transposed-conv output), small grid hs x ws, pad = pad_before
 struct Geo { int hb, wb, hs, ws, s, pad, K; };
 
-// What translate_fwd / decoder_fwd / decoder_bwd / fc_middle_bwd (ctx_engine.cpp) need to know about a model beyond the handle's F (real
-// code width), Fp (code row stride) and D0 (flatten width): plain data, filled at create (skip_plan | gen_plan).  d_h(4-gi) mirrors h_gi.
-struct DecoderPlan {
+// What the shared launch sequences (ctx_engine.cpp: encoder_fwd / encoder_bwd, translate_fwd / decoder_fwd / decoder_bwd /
+// fc_middle_bwd) need to know about a model beyond the handle's F (real code width), Fp (code row stride) and D0 (flatten width): plain
+// data, filled at create (skip_plan | gen_plan).  Encoder layer h_gi and decoder layer d_h(4-gi) mirror each other: one entry for both.
+struct Plan {
     Geo g[4];
-    int ch[4], co[4];            // width of each half of d_h(4-gi)'s input [decoder stream | ctx skip h_gi]; width of its output
+    int ch[4], co[4];            // h_gi: output width, input width.  d_h(4-gi): width of each half of its input [decoder stream | ctx skip h_gi], width of its output
     bool direct[4];              // the layer runs on the direct kernels of dconv.h: narrow || (3-channel side && rt.direct3)
     bool residual = false;       // out = decode(.) + ctx frame
+    int nset = 2;                // encoder sets: 1 = `conv` for src, tgt and ctx; 2 = `conv` (set 0) + `conv_context` (set 1)
+    EncParams enc[2];
+    bool enc_early = false;      // an encoder's h4_lin / hz_lin slice goes to dp_bucket / adam_early once h4_lin's input gradient is enqueued (ContextSkipNew)
     int64_t th0w, th0b, tzw, tzb, d0w, d0b, dw[5], db[5];   // arena offsets (floats) of translate/*, deconv/d_h0_lin/*, deconv/d_hK/{w,biases}
 };
 
 // Which launch groups of a PLAIN backward a parameter mask (ctx_set_param_lr_scale) leaves: a group runs iff one of its results
 // reaches the gradient of a trainable tensor (plan_mask, ctx_engine.cpp).  [0] = Matrix / filter, [1] = bias of a layer.
-// The encoder records hold ContextSkipNew's two encoders (0 = conv, 1 = conv_context), layers h0..h3_conv, h4_lin, hz_lin = 0..5;
-// the table-driven engine's encoder loop stays whole, so for it every input gradient below is set.
+// The encoder records are indexed by an encoder part's Prune index (EncPart::prune: 0 = conv, 1 = conv_context), layers h0..h3_conv,
+// h4_lin, hz_lin = 0..5.  encoder_bwd prunes any handle by them, but plan_mask works them out for ContextSkipNew only so far: for a
+// table-driven handle it sets every encoder entry, so that handle's encoder backward still runs whole under a mask.
 struct Prune {
     bool on = false;                 // a mask is set
     bool dec[5][2] = {}, d0[2] = {}, tz[2] = {}, th0[2] = {};   // own gradients of deconv/d_h1..4, d_h0_lin, translate/*
@@ -121,12 +133,6 @@ struct Prune {
     bool dec_dx[5] = {}, d0_dx = false, tz_dx = false, th0_dx = false;      // the layer's input-gradient launch
     bool enc_any[2] = {}, enc_dx[2][6] = {};
     bool pack_dout = false;          // someone reads the 4-channel copy of d loss / d out
-};
-
-// one ContextSkipNew encoder's parameters and their gradients in the arena (resolved once at create)
-struct Scope {
-    float *w[4], *b[4], *w4, *b4, *wz, *bz;
-    float *gw[4], *gb[4], *gw4, *gb4, *gwz, *gbz;
 };
 
 }  // namespace ctxi
@@ -139,8 +145,7 @@ struct ctx_handle {
     Options opt{};               // this handle's switches (options.h; ctx_set_option): the process defaults (environment) at ctx_create
     GenState* gen = nullptr;     // CTX_VARIANT_REAL / CTX_VARIANT_INCEPTION2 state (ctxtrans_gen.inc)
     Routing rt{};                // conv-layer routing rules of this variant (set_routing, at create)
-    ctxi::DecoderPlan dec{};     // geometry, widths and parameter offsets of the shared translate / decoder sequences (at create)
-    ctxi::Scope enc_conv{}, enc_ctx{};   // ContextSkipNew: the parameters of its `conv` / `conv_context` encoders
+    ctxi::Plan plan{};           // geometry, widths and parameter offsets of the shared encoder / translate / decoder sequences (at create)
     int Fp = 0;                  // row stride of the code buffers Z / dZ (featsize, or featsize padded to 32 for REAL)
     int device = 0;
     hipStream_t stream = nullptr;
@@ -170,9 +175,11 @@ struct ctx_handle {
     float *dout = nullptr, *dE[4] = {}, *dSk[4] = {}, *dDz = nullptr, *dsim2 = nullptr;
     float *dth0 = nullptr, *dcz = nullptr, *dS[5] = {}, *dC[5] = {};
     // tf.nn.dropout of ContextAEReal's training graph (keep_prob < 1 only; arm_shaping.py:1637-1661): per site the factors
-    // mask / keep_prob (dM[1..6]: sites 1 flatten(h3), 2 h4, 3 concat([src_z, ctx_z]), 4 trans_h0, 5 z, 6 reshape(z_)) and, for the sites
-    // of the shared sequences, the dropped copy the next layer reads.  All null on a handle without dropout.
+    // mask / keep_prob (dM[1..6]: sites 1 flatten(h3), 2 h4, 3 concat([src_z, ctx_z]), 4 trans_h0, 5 z, 6 reshape(z_)), the dropped
+    // copy the next layer reads (x1d, x2d: what h4_lin / hz_lin read at sites 1 and 2) and h4_lin's raw input gradient at site 1 (graw).
+    // All null on a handle without dropout.
     float* dM[7] = {};
+    float *x1d = nullptr, *x2d = nullptr, *graw = nullptr;
     float *xcat = nullptr, *th0d = nullptr, *zd = nullptr, *dzd = nullptr;
     float *scratch = nullptr, *slab = nullptr, *scalars = nullptr;
     float* zeros = nullptr;   // 256 B of zeros for the branch-free loaders
@@ -314,7 +321,7 @@ struct ctx_handle {
     std::vector<ctx_prof_entry> prof_entries;
     std::vector<double> prof_ms;
 
-    int64_t find(const char* name) const {   // arena offset of a parameter (create only: the launch sequences use dec / enc_*)
+    int64_t find(const char* name) const {   // arena offset of a parameter (create only: the launch sequences use plan)
         for (auto& p : params)
             if (p.name == name) return p.offset;
         return -1;
@@ -353,7 +360,7 @@ int adam_step(ctx_handle* h, float lr);
 int gen_alloc(ctx_handle* h);
 int alloc_buffers(ctx_handle* h);
 void set_routing(ctx_handle* h);
-void skip_plan(ctx_handle* h);     // fill h->dec (and ContextSkipNew's encoder scopes) at create, after set_routing
+void skip_plan(ctx_handle* h);     // fill h->plan at create, after set_routing
 void gen_plan(ctx_handle* h);
 bool use_lanes(const ctx_handle* h);
 void adam_begin(ctx_handle* h, float lr);

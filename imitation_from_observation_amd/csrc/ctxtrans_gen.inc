@@ -1,6 +1,7 @@
 // ctxtrans_gen.inc -- the table-driven translator engine behind CTX_VARIANT_REAL and CTX_VARIANT_INCEPTION2.
-// Included by ctx_engine.cpp.  Its own here: the models' layout, their encoders, rchain and the frame gradients; translate MLP and
-// decoder are the sequences ContextSkipNew runs too (ctx_engine.cpp: translate_fwd .. fc_middle_bwd), on the record gen_plan fills.
+// Included by ctx_engine.cpp.  Its own here: the models' layout, their buffers, rchain and which image rows go through which encoder
+// set (gen_part); encoders, translate MLP and decoder are the sequences ContextSkipNew runs too (ctx_engine.cpp: encoder_fwd / encoder_bwd,
+// translate_fwd .. fc_middle_bwd), on the record gen_plan fills.
 //
 //   ContextAEReal        gym/envs/mujoco/arm_shaping.py:1599-1684   k 5, strides 1/2/1/2, filters 32/16/16/8, ONE encoder
 //                        (scope "conv") for src, tgt and ctx, 3-channel frames, featsize 100        (names 'real', 'sweep')
@@ -22,9 +23,9 @@
 // gradients 0, padded filter gradients are sums of products with a 0 factor, and Adam maps (g, m, v) = 0 to a 0 update.
 // The C ABI keeps the reference's shapes: ctx_set_params / get_* scatter and gather through `real2pad`.
 // tf.nn.dropout(., keep_prob) in ContextAEReal with the module-level keep_prob = 1.0 (arm_shaping.py:1476) is the identity.
-// Filter / bias gradients run on the LANE_DW side stream beside the input-gradient chain (Side scopes below).
-// Every layer launches through the layer helpers of ctx_engine.cpp (fc_* and conv / convt / wgrad / convt3, with this model's routing
-// record ctx_handle::rt); this file says which buffers the encoders' layers read and write, not which kernel runs them.
+// Filter / bias gradients run on the LANE_DW side stream beside the input-gradient chain (EncPart::lane; the Side scope of rchain_dw).
+// Every layer launches through the shared sequences and layer helpers of ctx_engine.cpp (with this model's routing record
+// ctx_handle::rt); this file says which buffers and rows the encoders read and write, not which kernel runs them.
 
 namespace ctxi {
 
@@ -114,13 +115,13 @@ int gen_layout(const ctx_config& c, GenState& r, std::vector<ParamInfo>& real, i
         const std::string sc = set == 1 ? "conv_context" : "conv";
         for (int k = 0; k < 4; ++k) {
             const int64_t cin = k ? r.nf[k - 1] : c.C, cinp = r.in_ch(k);
-            add(sc + "/h" + std::to_string(k) + "_conv/w", {r.Kk[k], r.Kk[k], cin, r.nf[k]}, {r.Kk[k], r.Kk[k], cinp, r.cp[k]}, nullptr, &r.w[set][k]);
-            add(sc + "/h" + std::to_string(k) + "_conv/biases", {r.nf[k]}, {r.cp[k]}, nullptr, &r.b[set][k]);
+            add(sc + "/h" + std::to_string(k) + "_conv/w", {r.Kk[k], r.Kk[k], cin, r.nf[k]}, {r.Kk[k], r.Kk[k], cinp, r.cp[k]}, nullptr, &r.enc[set].w[k]);
+            add(sc + "/h" + std::to_string(k) + "_conv/biases", {r.nf[k]}, {r.cp[k]}, nullptr, &r.enc[set].b[k]);
         }
-        add(sc + "/h4_lin/Matrix", {pix3 * f3, F}, {r.D0p, Fp}, flat_in, &r.w4[set]);
-        add(sc + "/h4_lin/bias", {F}, {Fp}, nullptr, &r.b4[set]);
-        add(sc + "/hz_lin/Matrix", {F, F}, {Fp, Fp}, nullptr, &r.wz[set]);
-        add(sc + "/hz_lin/bias", {F}, {Fp}, nullptr, &r.bz[set]);
+        add(sc + "/h4_lin/Matrix", {pix3 * f3, F}, {r.D0p, Fp}, flat_in, &r.enc[set].w4);
+        add(sc + "/h4_lin/bias", {F}, {Fp}, nullptr, &r.enc[set].b4);
+        add(sc + "/hz_lin/Matrix", {F, F}, {Fp, Fp}, nullptr, &r.enc[set].wz);
+        add(sc + "/hz_lin/bias", {F}, {Fp}, nullptr, &r.enc[set].bz);
     }
     // concat([src_z, ctx_z]) rows: [0,F) -> [0,F), [F,2F) -> [Fp, Fp+F)
     auto cat_rows = [&](int d, int64_t i) { return d == 0 && i >= F ? i - F + Fp : i; };
@@ -164,8 +165,8 @@ int gen_alloc(ctx_handle* h) {
     TRY(dev_alloc(h, &r.dA[4], 3 * B * Fp));
     TRY(alloc_middle(h));
     if (h->cfg.keep_prob > 0.f && h->cfg.keep_prob < 1.f) {
-        TRY(dev_alloc(h, &h->dM[1], 3 * B * r.D0p)); TRY(dev_alloc(h, &r.x1d, 3 * B * r.D0p)); TRY(dev_alloc(h, &r.graw, 3 * B * r.D0p));
-        TRY(dev_alloc(h, &h->dM[2], 3 * B * Fp)); TRY(dev_alloc(h, &r.x2d, 3 * B * Fp));
+        TRY(dev_alloc(h, &h->dM[1], 3 * B * r.D0p)); TRY(dev_alloc(h, &h->x1d, 3 * B * r.D0p)); TRY(dev_alloc(h, &h->graw, 3 * B * r.D0p));
+        TRY(dev_alloc(h, &h->dM[2], 3 * B * Fp)); TRY(dev_alloc(h, &h->x2d, 3 * B * Fp));
         TRY(dev_alloc(h, &h->dM[3], 2 * B * Fp)); TRY(dev_alloc(h, &h->xcat, 2 * B * Fp));
         TRY(dev_alloc(h, &h->dM[4], B * Fp)); TRY(dev_alloc(h, &h->th0d, B * Fp));
         TRY(dev_alloc(h, &h->dM[5], 2 * B * Fp)); TRY(dev_alloc(h, &h->zd, 2 * B * Fp));
@@ -185,7 +186,7 @@ Geo gen_geo(const GenState& r, int k) { return Geo{r.gh[k] * r.se[k], r.gw[k] * 
 // the table-driven models' share of ctx_create: the record of the shared sequences from the tables of gen_spec / gen_layout
 void gen_plan(ctx_handle* h) {
     const GenState& r = *h->gen;
-    DecoderPlan& p = h->dec;
+    Plan& p = h->plan;
     for (int gi = 0; gi < 4; ++gi) {
         p.g[gi] = gen_geo(r, gi);
         p.ch[gi] = r.cp[gi];
@@ -193,6 +194,8 @@ void gen_plan(ctx_handle* h) {
         p.direct[gi] = r.narrow || (p.co[gi] == 3 && h->rt.direct3);
     }
     p.residual = r.residual;
+    p.nset = r.nset;
+    for (int set = 0; set < r.nset; ++set) p.enc[set] = r.enc[set];      // (lrelu on every z: arm_shaping.py:1638, :1812; no early slices)
     p.th0w = r.th0w; p.th0b = r.th0b; p.tzw = r.tzw; p.tzb = r.tzb; p.d0w = r.d0w; p.d0b = r.d0b;
     for (int k = 1; k <= 4; ++k) { p.dw[k] = r.dw[k]; p.db[k] = r.db[k]; }
     h->D0 = r.D0p;
@@ -210,41 +213,25 @@ bool gen_rchain(const ctx_handle* h, int B) {
     return rchain_ok(r.Fp, r.D0p, r.nset, gen_drop(h), h->cfg.precision) && r.D0p <= 1536 && (int64_t)B * r.D0p <= 300000;
 }
 void gen_rchain_weights(const ctx_handle* h, const float* base, const float* W[10]) {
-    const GenState& r = *h->gen;
-    const int64_t o[10] = {r.w4[0], r.b4[0], r.wz[0], r.bz[0], r.th0w, r.th0b, r.tzw, r.tzb, r.d0w, r.d0b};
+    const Plan& p = h->plan;
+    const int64_t o[10] = {p.enc[0].w4, p.enc[0].b4, p.enc[0].wz, p.enc[0].bz, p.th0w, p.th0b, p.tzw, p.tzb, p.d0w, p.d0b};
     for (int i = 0; i < 10; ++i) W[i] = base + o[i];
 }
 
-// encoder `set` over images [img0, img0 + nimg) of the stacked batch [tgt | src | ctx]
-// (in0 >= 0: the images are read at rows [in0, in0 + nimg) of the frame buffer instead; activations and codes still land at img0)
-void gen_encoder_fwd(ctx_handle* h, int B, int set, int img0, int nimg, bool drop = false, bool fc = true, int in0 = -1) {
+// images [img0, img0 + nimg) of the stacked batch [tgt | src | ctx] through encoder `set`: activations at those rows of a[] / dA[],
+// codes at rows B + img0 of Z / dZ ([trans_z | tgt_z | src_z | ctx_z]), filter gradients on the side lane
+// (in0 >= 0: the images are read at rows [in0, in0 + nimg) of the frame buffer instead)
+EncPart gen_part(ctx_handle* h, int B, int set, int img0, int nimg, bool skips = false, int in0 = -1) {
     GenState& r = *h->gen;
-    const float* P = h->arena;
-    const std::string sc = set == 1 ? "conv_context" : "conv";
-    const float* in = h->img + (int64_t)(in0 >= 0 ? in0 : img0) * h->npi;
-    for (int k = 0; k < 4; ++k) {
-        float* y = r.a[k] + (int64_t)img0 * r.gh[k] * r.gw[k] * r.cp[k];
-        conv(h, sc + "/h" + std::to_string(k) + "_conv fwd", gen_geo(r, k), in, r.in_ch(k), nimg, P + r.w[set][k], r.cp[k],
-             epi_act(y, r.cp[k], P + r.b[set][k], 1), r.narrow);
-        in = y;
+    EncPart q{};
+    q.set = q.prune = set; q.nimg = nimg; q.skips = skips; q.lane = LANE_DW; q.slot0 = img0 / B; q.row0 = img0;
+    q.x = h->img + (int64_t)(in0 >= 0 ? in0 : img0) * h->npi;
+    for (int k = 0; k < 5; ++k) {
+        const int64_t o = img0 * (k < 4 ? (int64_t)r.gh[k] * r.gw[k] * r.cp[k] : r.Fp);
+        q.act[k] = r.a[k] + o; q.dact[k] = r.dA[k] + o;
     }
-    if (!fc) return;                                              // (the caller runs the FC layers: rchain_fwd)
-    const int Fp = r.Fp, D0p = (int)r.D0p;
-    float* a4 = r.a[4] + (int64_t)img0 * Fp;
-    if (drop) {                                                   // site 1: flatten(h3) * M1 feeds h4_lin (arm_shaping.py:1637)
-        float* x1 = r.x1d + (int64_t)img0 * D0p;
-        ew_mul(h->stream, x1, D0p, in, D0p, h->dM[1] + (int64_t)img0 * D0p, D0p, nimg, D0p);
-        in = x1;
-    }
-    fc_layer(h, sc + "/h4_lin", km(in, D0p, nimg, D0p), nimg, D0p, P + r.w4[set], P + r.b4[set], Fp, 1, a4);
-    const float* x2 = a4;
-    if (drop) {                                                   // site 2: h4 * M2 feeds hz_lin (:1638)
-        float* x2d = r.x2d + (int64_t)img0 * Fp;
-        ew_mul(h->stream, x2d, Fp, a4, Fp, h->dM[2] + (int64_t)img0 * Fp, Fp, nimg, Fp);
-        x2 = x2d;
-    }
-    // Z rows: [trans_z | tgt_z | src_z | ctx_z]; lrelu on every z (arm_shaping.py:1638, :1812)
-    fc_layer(h, sc + "/hz_lin", km(x2, Fp, nimg, Fp), nimg, Fp, P + r.wz[set], P + r.bz[set], Fp, 1, h->Z + (int64_t)(B + img0) * Fp);
+    q.z = h->Z + (int64_t)(B + img0) * r.Fp; q.dz = h->dZ + (int64_t)(B + img0) * r.Fp;
+    return q;
 }
 
 void gen_forward(ctx_handle* h, int B, Mode mode) {
@@ -254,7 +241,8 @@ void gen_forward(ctx_handle* h, int B, Mode mode) {
         if (mode == MODE_ENCODE) pack_c4(h, h->img + (int64_t)B * h->npi, (int64_t)B * h->H * h->W);
         else pack_c4(h, h->img, 3ll * B * h->H * h->W);
     }
-    if (mode == MODE_ENCODE) { gen_encoder_fwd(h, B, 0, B, B); return; }     // src slot only, `conv` encoder
+    auto part = [&](int set, int img0, int nimg, int in0 = -1) { return gen_part(h, B, set, img0, nimg, false, in0); };
+    if (mode == MODE_ENCODE) { encoder_fwd(h, part(0, B, B)); return; }       // src slot only, `conv` encoder
     const bool drop = mode == MODE_TRAIN && gen_drop(h);
     if (drop) {                                                               // this step's dropout factors, all six sites
         const float kp = h->cfg.keep_prob;
@@ -283,12 +271,12 @@ void gen_forward(ctx_handle* h, int B, Mode mode) {
     const bool tr = mode == MODE_TRANSLATE || rec;                           // an inference forward
     const int nc = rec ? h->recon_nctx : tr && h->ctx_single ? 1 : B;
     const int skip0 = rec && r.nset == 1 && h->recon_inplace ? B : 2 * B;    // first image row of the context skips in r.a[*]
-    if (rec && r.nset == 1) gen_encoder_fwd(h, B, 0, B, h->recon_inplace ? B : B + nc);
-    else if (rec) { gen_encoder_fwd(h, B, 0, B, B); gen_encoder_fwd(h, B, 1, 2 * B, nc, false, true, h->recon_inplace ? B : 2 * B); }
-    else if (tr && r.nset == 1) gen_encoder_fwd(h, B, 0, B, B + nc);           // img rows [src | ctx] are contiguous
-    else if (tr) { gen_encoder_fwd(h, B, 0, B, B); gen_encoder_fwd(h, B, 1, 2 * B, nc); }
-    else if (r.nset == 1) gen_encoder_fwd(h, B, 0, 0, 3 * B, drop, !chain);
-    else { gen_encoder_fwd(h, B, 0, 0, 2 * B); gen_encoder_fwd(h, B, 1, 2 * B, B); }
+    if (rec && r.nset == 1) encoder_fwd(h, part(0, B, h->recon_inplace ? B : B + nc));
+    else if (rec) { encoder_fwd(h, part(0, B, B)); encoder_fwd(h, part(1, 2 * B, nc, h->recon_inplace ? B : 2 * B)); }
+    else if (tr && r.nset == 1) encoder_fwd(h, part(0, B, B + nc));           // img rows [src | ctx] are contiguous
+    else if (tr) { encoder_fwd(h, part(0, B, B)); encoder_fwd(h, part(1, 2 * B, nc)); }
+    else if (r.nset == 1) encoder_fwd(h, part(0, 0, 3 * B), drop, !chain);
+    else { encoder_fwd(h, part(0, 0, 2 * B)); encoder_fwd(h, part(1, 2 * B, B)); }
     // Z rows: [trans_z | tgt_z | src_z | ctx_z]; RECON: the decoder runs on src_z
     const int nd = tr ? B : 2 * B;
     if (chain) {
@@ -298,30 +286,6 @@ void gen_forward(ctx_handle* h, int B, Mode mode) {
         rchain_fwd(h->stream, B, D0p, r.a[3], r.a[4], h->Z, h->th0, h->dz, W);
     } else if (!rec) translate_fwd(h, B, h->Z + 3ll * B * Fp, nc, drop);
     decoder_fwd(h, B, chain ? nullptr : rec ? h->Z + 2ll * B * Fp : h->Z, nd, r.a, skip0, nc, tr, rec, drop);
-}
-
-// VJP frame / feature-map gradients, one launch per image slot [tgt | src | ctx] the caller asked for.  3-channel frames
-// (ContextAEReal): the direct transposed conv of frame_grads3.  Feature maps (ContextAEInception2, C a multiple of 32): the
-// transposed conv of the deeper layers' input gradients, no lrelu'; out = decode + tgtctx adds d out + d out2 to the ctx maps.  The
-// tgt slot adds the recon terms' direct gradient w.r.t. their target (recon_tgt_term) in either case.
-void gen_frame_grads(ctx_handle* h, int B) {
-    const GenState& r = *h->gen;
-    if (r.C0 == 3) {
-        frame_grads3(h, r.dA[0], r.cp[0], 0, 3 * B, r.gh[0], r.gw[0], r.se[0], h->arena + r.w[0][0]);
-        return;
-    }
-    const Geo g = gen_geo(r, 0);
-    for (int j = 0; j < 3; ++j) {
-        float* o = vjp_frame_out(h, j);
-        if (!o) continue;
-        Epi ed;
-        ed.out1 = o; ed.ld1 = r.C0;
-        if (j == 2 && r.residual) { ed.add1 = h->dout; ed.lda1 = r.C0; ed.add2 = h->dout + (int64_t)B * h->npi; ed.lda2 = r.C0; }
-        const float* w = h->arena + r.w[j == 2 ? r.nset - 1 : 0][0];
-        convt(h, std::string(j == 0 ? "tgt" : j == 1 ? "src" : "ctx") + " frames dx", g, Cat{r.dA[0] + (int64_t)j * B * g.hs * g.ws * r.cp[0], r.cp[0]},
-              B, w, r.C0, ed, r.narrow, false);
-        if (j == 0) recon_tgt_term(h, o);
-    }
 }
 
 void gen_backward(ctx_handle* h, int B, int sim_batch) {
@@ -336,12 +300,10 @@ void gen_backward(ctx_handle* h, int B, int sim_batch) {
     decoder_bwd(h, B, r.a, 2 * B, drop);
     // image ranges.  Weights (and filter gradients): one encoder -> all 3B rows at once; two -> `conv` on [0,2B), `conv_context`
     // on [2B,3B).  Input gradients: rows of tgt/src images have no skip term, ctx rows add both decoder passes' skip gradients.
-    struct Part { int img0, nimg, set; bool skips; };   // images [img0, img0 + nimg) of [tgt | src | ctx] through encoder `set`
-    const Part wparts2[2] = {{0, 2 * B, 0, false}, {2 * B, B, 1, true}};
-    const Part wparts1[1] = {{0, 3 * B, 0, false}};
-    const Part* wparts = r.nset == 2 ? wparts2 : wparts1;
-    const Part xparts[2] = {{0, 2 * B, 0, false}, {2 * B, B, r.nset - 1, true}};
-    auto scn = [](int set) { return std::string(set == 1 ? "conv_context" : "conv"); };
+    const EncPart wparts2[2] = {gen_part(h, B, 0, 0, 2 * B), gen_part(h, B, 1, 2 * B, B, true)};
+    const EncPart wparts1[1] = {gen_part(h, B, 0, 0, 3 * B)};
+    const EncPart* wparts = r.nset == 2 ? wparts2 : wparts1;
+    const EncPart xparts[2] = {gen_part(h, B, 0, 0, 2 * B), gen_part(h, B, r.nset - 1, 2 * B, B, true)};
     const bool chain = gen_rchain(h, B) && !(h->vjp && h->vjp->d_input_z);   // (rchain_bwd has no entry for a d input_z term)
     if (chain) {
         // d_h0_lin .. h4_lin: the input-gradient chain in one launch, then every Matrix / bias gradient in one grouped launch on the side lane
@@ -357,68 +319,12 @@ void gen_backward(ctx_handle* h, int B, int sim_batch) {
           rchain_dw(h->stream, B, D0p, r.a[3], r.a[4], h->Z, h->th0, r.dA[4], h->dZ, h->dth0, h->dDz, Gp); }
         fire_bucket(h, r.th0w);
     } else {
-    fc_middle_bwd(h, B, h->Z + 3ll * B * Fp, h->dZ + 3ll * B * Fp, drop);     // ctx_z, d ctx_z: row block 3
-    // ---- encoders over [tgt | src | ctx] (3B); every z has an lrelu
-    const int n3 = 3 * B;
-    float* dSz = h->dZ + (int64_t)B * Fp;
-    { ProfScope ps(h, "conv/hz_lin lrelu'", K_EW, 0.0); lrelu_mask(h->stream, dSz, h->Z + (int64_t)B * Fp, (int64_t)n3 * Fp); }
-    for (int i = 0; i < r.nset; ++i) {
-        const Part& q = wparts[i];
-        Side sd(h, LANE_DW);
-        fc_dw(h, scn(q.set) + "/hz_lin", nm((drop ? r.x2d : r.a[4]) + (int64_t)q.img0 * Fp, Fp, Fp, q.nimg), Fp, dSz + (int64_t)q.img0 * Fp, q.nimg, Fp,
-              G + r.wz[q.set], G + r.bz[q.set]);
+        fc_middle_bwd(h, B, h->Z + 3ll * B * Fp, h->dZ + 3ll * B * Fp, drop);     // ctx_z, d ctx_z: row block 3
+        ProfScope ps(h, "conv/hz_lin lrelu'", K_EW, 0.0);                        // every z has an lrelu: the codes of all 3B images in one launch
+        lrelu_mask(h->stream, h->dZ + (int64_t)B * Fp, h->Z + (int64_t)B * Fp, 3ll * B * Fp);
     }
-    for (const Part& q : xparts) {
-        Epi e4;
-        e4.out1 = r.dA[4] + (int64_t)q.img0 * Fp; e4.ld1 = Fp; e4.mask = r.a[4] + (int64_t)q.img0 * Fp; e4.ldm = Fp;
-        fc_dx(h, scn(q.set) + "/hz_lin", dSz + (int64_t)q.img0 * Fp, q.nimg, Fp, P + r.wz[q.set], Fp, e4);
-    }
-    if (drop) ew_mul(h->stream, r.dA[4], Fp, r.dA[4], Fp, h->dM[2], Fp, n3, Fp);             // site 2 (commutes with lrelu' of h4)
-    for (int i = 0; i < r.nset; ++i) {
-        const Part& q = wparts[i];
-        Side sd(h, LANE_DW);
-        fc_dw(h, scn(q.set) + "/h4_lin", nm((drop ? r.x1d : r.a[3]) + (int64_t)q.img0 * D0p, D0p, D0p, q.nimg), D0p, r.dA[4] + (int64_t)q.img0 * Fp, q.nimg, Fp,
-              G + r.w4[q.set], G + r.b4[q.set]);
-    }
-    for (const Part& q : xparts) {
-        Epi e3;
-        const int64_t o3 = (int64_t)q.img0 * D0p;
-        if (drop) {     // site 1: d h3 = ((h4_lin's input gradient) * M1 + the skip gradients) * lrelu'(h3): the product comes first
-            e3.out1 = r.graw + o3; e3.ld1 = D0p;
-            fc_dx(h, scn(q.set) + "/h4_lin", r.dA[4] + (int64_t)q.img0 * Fp, q.nimg, Fp, P + r.w4[q.set], D0p, e3);
-            drop_fin(h->stream, r.dA[3] + o3, r.graw + o3, h->dM[1] + o3, q.skips ? h->dSk[3] : nullptr,
-                     q.skips ? h->dSk[3] + (int64_t)B * D0p : nullptr, r.a[3] + o3, (int64_t)q.nimg * D0p);
-            continue;
-        }
-        e3.out1 = r.dA[3] + o3; e3.ld1 = D0p; e3.mask = r.a[3] + o3; e3.ldm = D0p;
-        if (q.skips) { e3.add1 = h->dSk[3]; e3.lda1 = D0p; e3.add2 = h->dSk[3] + (int64_t)B * D0p; e3.lda2 = D0p; }
-        fc_dx(h, scn(q.set) + "/h4_lin", r.dA[4] + (int64_t)q.img0 * Fp, q.nimg, Fp, P + r.w4[q.set], D0p, e3);
-    }
-    }   // (!chain)
-    for (int k = 3; k >= 0; --k) {
-        const Geo g = gen_geo(r, k);
-        const int ca = r.in_ch(k), cb = r.cp[k];
-        const float* xin = k ? r.a[k - 1] : h->img;
-        auto dyk = [&](const Part& q) { return Cat{r.dA[k] + (int64_t)q.img0 * g.hs * g.ws * cb, cb}; };
-        for (int i = 0; i < r.nset; ++i) {
-            const Part& q = wparts[i];
-            Side sd(h, LANE_DW);                              // this part's bias and filter gradient: off the dx chain
-            wgrad(h, scn(q.set) + "/h" + std::to_string(k) + "_conv", g, xin + (int64_t)q.img0 * g.hb * g.wb * ca, ca, dyk(q), q.nimg,
-                  G + r.w[q.set][k], G + r.b[q.set][k], r.narrow);
-        }
-        if (k == 0) {                                            // the training step has no gradient w.r.t. the frames / features
-            if (h->vjp) gen_frame_grads(h, B);
-            break;
-        }
-        // input gradient = conv2d_transpose of dA[k] with the filter read [K,K,ca,cb]
-        for (const Part& q : xparts) {
-            const int64_t bo = (int64_t)q.img0 * g.hb * g.wb * ca;
-            Epi ed;
-            ed.out1 = r.dA[k - 1] + bo; ed.ld1 = ca; ed.mask = r.a[k - 1] + bo; ed.ldm = ca;
-            if (q.skips) { ed.add1 = h->dSk[k - 1]; ed.lda1 = ca; ed.add2 = h->dSk[k - 1] + (int64_t)B * g.hb * g.wb * ca; ed.lda2 = ca; }
-            convt(h, scn(q.set) + "/h" + std::to_string(k) + "_conv dx", g, dyk(q), q.nimg, P + r.w[q.set][k], ca, ed, r.narrow, false);
-        }
-    }
+    // ---- encoders over [tgt | src | ctx] (3B)
+    encoder_bwd(h, B, wparts, r.nset, xparts, 2, drop, !chain);
     if (use_lanes(h)) join(h, LANE_DW);
     h->have_grads = true;
 }

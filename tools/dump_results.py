@@ -18,7 +18,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-# name: (variant, shape, B, precision, keep_prob, options).  The smallest shapes that still reach each route.
+# name: (variant, shape, B, precision, keep_prob, options[, lr-scale spec of set_lr_scales]).  The smallest shapes that still reach each route.
 CASES = {
     "skipnew 16x48 d32 F128 B3": ("skipnew", (16, 48, 32, 128), 3, "f32", None, {}),          # image-major loaders
     "skipnew 32x32 d32 F64 B33": ("skipnew", (32, 32, 32, 64), 33, "f32", None, {}),          # 66 rows: position-major, ragged last tile
@@ -30,6 +30,15 @@ CASES = {
     "inception2 B32": ("inception2", None, 32, "f32", None, {}),
     "skipnew 16x48 d32 F128 B3 fp16x3d": ("skipnew", (16, 48, 32, 128), 3, "fp16x3d", None, {}),
     "real 36x64 B3 fp16x3d": ("real", (36, 64), 3, "fp16x3d", None, {}),
+    # masked plain backwards: an encoder that is not entered | one that stops after h3_conv's filter gradient beside one that skips
+    # hz_lin's own gradients and stops after h4_lin's | a table-driven handle, whose encoder backward runs whole under any mask
+    "skipnew 16x48 d32 F128 B3 conv frozen": ("skipnew", (16, 48, 32, 128), 3, "f32", None, {}, {"conv/*": 0.0}),
+    "skipnew 16x48 d32 F128 B3 ctx h3 + conv h4": ("skipnew", (16, 48, 32, 128), 3, "f32", None, {},
+                                                   {"*": 0.0, "conv_context/h3_conv/*": 1.0, "conv/h4_lin/*": 1.0}),
+    "real 36x64 B3 deconv only": ("real", (36, 64), 3, "f32", None, {}, {"*": 0.0, "deconv/*": 1.0}),
+    # the lanes the default leaves out: ContextSkipNew on one stream, the two encoder sets of ContextAEInception2 on side lanes
+    "skipnew 32x32 d32 F64 B33 overlap 0": ("skipnew", (32, 32, 32, 64), 33, "f32", None, {"overlap": 0}),
+    "inception2 B4 overlap 1": ("inception2", None, 4, "f32", None, {"overlap": 1}),
 }
 
 
@@ -41,7 +50,7 @@ def build(case):
     """(Translator kwargs, parameter tree, f32 frames [src, ctx, tgt], featsize)"""
     from oracle import ctx_oracle as o
     from tests import _spikes
-    variant, shape, B, prec, kp, _ = CASES[case]
+    variant, shape, B, prec, kp = CASES[case][:5]
     if variant == "skipnew":
         H, W, d, F = shape
         p = o.init_params(o.SkipNewConfig(H=H, W=W, df_dim=d, gf_dim=d, featsize=F), 1234, np.float32, stddev=0.05)
@@ -68,6 +77,7 @@ def run_case(case, lib, out):
     from imitation_from_observation_amd import Translator
     kw, p, frames, F = build(case)
     B, opts = CASES[case][2], CASES[case][5]
+    mask = CASES[case][6] if len(CASES[case]) > 6 else None
     src, ctx, tgt = (np.ascontiguousarray(x, np.float32) for x in frames)
     rec = {}
     with Translator(**kw) as tr:
@@ -77,10 +87,13 @@ def run_case(case, lib, out):
         if kw.get("keep_prob"):
             tr.set_dropout_seed(20240)
         tr.set_params(p)
+        if mask:                                         # before the first step; a pruned backward writes the trainable tensors' gradients only
+            tr.set_lr_scales(mask)
         for i in range(2):
             sc = tr.train_step(src, ctx, tgt, lr=1e-3)
             rec[f"train{i} scalars"] = np.array([sc[k] for k in ("loss", "simloss", "recon1", "recon2")], np.float32)
-        rec["train1 grads"] = tr.get_grads_flat()
+        rec["train1 grads"] = tr.get_grads_flat() if not mask else np.concatenate(
+            [g.ravel() for (n, g), sc in zip(tr.get_grads().items(), tr.get_lr_scales().values()) if sc != 0.0])
         rec["train1 params"] = tr.get_params_flat()
         ev = tr.evaluate(src, ctx, tgt)
         rec["eval scalars"] = np.array([ev[k] for k in ("loss", "simloss", "recon1", "recon2")], np.float32)
